@@ -49,6 +49,13 @@ whole-tile replays over the network's own output of the timed step.
 restatement of the network + the C / python restatement of `process()` -- on a bounded sample of the same
 tiles on this box's host cores.  The reference itself is python under /root/reference and cannot travel to
 the GPU box, so kind = "port"; profiles/ holds the reference's own timing taken in the build container.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it makes the checkpoint and the resident
+tiles, warms up W steps, times K steps, writes the last step's results if `--dump-outputs DIR` is given and prints the line.  Everything
+else described above -- the per-stage split, `variants`, `roofline`, the cfg 3 / training / whole-slide legs and `cpu_baseline` -- runs
+only with `--full` (the `--no-*` options then trim that run as before).  `--dump-outputs DIR` writes what the caller of the timed path
+receives from its last step (rank 0: instance maps, per-instance records, instance counts) as float .npy files; the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -68,13 +75,13 @@ def _control_flow_selftest(args, rank, world, dev):
     import torch
     import torch.distributed as dist
 
-    from hover_net_amd import infer_tile
+    from hover_net_amd import infer_tile, post_proc
 
     b, hw, max_inst = args.batch, 80, 80 * 80 // 13 + 1
     gather = infer_tile.gather_to_rank0 if world > 1 else None
 
     def submit():
-        out = (torch.full((b, hw, hw), rank + 1, dtype=torch.int32), torch.zeros((b, max_inst, 56), dtype=torch.uint8),
+        out = (torch.full((b, hw, hw), rank + 1, dtype=torch.int32), torch.zeros((b, max_inst, post_proc._REC_DTYPE.itemsize), dtype=torch.uint8),
                torch.full((b,), rank, dtype=torch.int32))
         return gather(out) if gather is not None else out
 
@@ -99,6 +106,8 @@ def _control_flow_selftest(args, rank, world, dev):
     for _ in range(args.warmup):
         submit()
     dt, out = timed(args.steps)
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, out)
     per_rank = None
     if world > 1:                      # the per-rank diagnosis of main(): every rank's own numbers all_gathered
         mine = torch.tensor([float(rank), 0.0], dtype=torch.float64)
@@ -112,7 +121,7 @@ def _control_flow_selftest(args, rank, world, dev):
     else:
         assert out is None or world == 1
     reps, t_end = 0, time.perf_counter() + min(args.sustain_seconds, 1.0)
-    while True:                                   # the sustained leg's stop vote: every rank leaves in the same iteration
+    while args.full:                              # the sustained leg's stop vote: every rank leaves in the same iteration
         for _ in range(args.steps):
             submit()
         reps += args.steps
@@ -143,6 +152,42 @@ def _self_launch(n):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     return subprocess.call(cmd, env=env)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(dirname, out):
+    """--dump-outputs: the host results of the last timed step, `out` = (instance maps int32 [B,h,w], records uint8 [B,R,48], counts int32
+    [B]) as the pipeline hands them to its caller, written as inst_map.npy (float32: labels are small integers), inst_records.npy (float64
+    [B,R,10], one column per field of post_proc._REC_DTYPE; rows past a tile's count are not results and are written as 0) and
+    inst_counts.npy (float64 [B]).  Over DUMP_LIMIT_BYTES a fixed, seeded sample of tiles is written instead, and tile_index.npy names it."""
+    import numpy as np
+
+    from hover_net_amd import post_proc
+
+    inst, rec, counts = (t.numpy() for t in out)
+    b = inst.shape[0]
+    fields = post_proc._REC_DTYPE.names
+    recs = rec.reshape(b, -1).view(post_proc._REC_DTYPE).reshape(b, -1)
+    table = np.stack([recs[f].astype(np.float64) for f in fields], -1)
+    table[np.arange(table.shape[1])[None, :] >= counts[:, None]] = 0.0
+    arrays = {"inst_map": inst.astype(np.float32), "inst_records": table, "inst_counts": counts.astype(np.float64)}
+    per_tile = sum(a.nbytes for a in arrays.values()) / b
+    if per_tile * b > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(b, max(1, int(DUMP_LIMIT_BYTES // per_tile)), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["tile_index"] = keep.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def _painted_tiles(n, size, seed):
+    """bench.py's timed tiles with a fitted checkpoint (a module-level function: it runs in spawned worker processes, without the GPU)."""
+    from hover_net_amd import synth_fit
+
+    return synth_fit.painted_tiles(n, size, seed, *synth_fit.consep_density(size))[0]
 
 
 def roofline_account(timed, per_ms, batch, dtype, n_prof=5):
@@ -227,6 +272,7 @@ def roofline_account(timed, per_ms, batch, dtype, n_prof=5):
 
 
 def main():
+    t_main = time.perf_counter()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -269,6 +315,11 @@ def main():
     ap.add_argument("--rotate", type=int, default=4,
                     help="distinct resident tile batches per rank the timed loop cycles through (round-5 verdict, next #7: rounds 1-5 timed the SAME 32 "
                          "tiles every step; the instance load then never changes and every cache sees the same addresses)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-stage split, variants, roofline (+ PMC traffic), cfg 3, training and "
+                         "whole-slide legs, CPU baseline (the --no-* options trim this run); off: set-up, warm-up, timed steps, line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) to DIR/<name>.npy as float32 / float64")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(_self_launch(args.gpus))       # no launcher around us: become N ranks
@@ -349,8 +400,27 @@ def main():
     def make_tiles(n, sz, seed):
         if not fitted:
             return synth_tiles(n, sz, seed=seed)
-        return synth_fit.painted_tiles(n, sz, seed, *synth_fit.consep_density(sz))[0]
+        return _painted_tiles(n, sz, seed)
 
+    # the work of one step on this rank: `sub` batches of `args.batch` tiles
+    if args.scaling == "strong":
+        lo, hi = infer_tile.shard_range(args.strong_tiles, rank, world)
+        sub = max(1, -(-(hi - lo) // args.batch))
+        tiles_per_step_global = args.strong_tiles
+    else:
+        sub = 1
+        tiles_per_step_global = world * args.batch
+    rot = max(1, args.rotate)
+    set_seeds = [[1 + rank + 1000 * j + 100000 * r for j in range(sub)] for r in range(rot)]
+    painter = None
+    if fitted:
+        # painting the timed tiles is host work of seconds: spawned CPU-only workers do it while the GPU fits the checkpoint
+        # (same function, same seeds: the same bytes as painting them here afterwards)
+        import concurrent.futures as cf
+        import multiprocessing as mp
+
+        painter = cf.ProcessPoolExecutor(min(4, rot * sub, max(1, 16 // world - 1)), mp_context=mp.get_context("spawn"))
+        painted = [[painter.submit(_painted_tiles, args.batch, size, s) for s in row] for row in set_seeds]
     sd, fit_info = make_checkpoint(args.mode, nt, size)
     if args.quiet_net_output:
         sd["decoder.np.u0.conv.bias"] = torch.tensor([8.0, -8.0])
@@ -369,16 +439,13 @@ def main():
         torch.cuda.synchronize(dev)
         return
     net = make_net()           # the engine's default launch schedule (fp32: two encoder sub-batches + decoder branch streams)
-    # the work of one step on this rank: `sub` batches of `args.batch` tiles
-    if args.scaling == "strong":
-        lo, hi = infer_tile.shard_range(args.strong_tiles, rank, world)
-        sub = max(1, -(-(hi - lo) // args.batch))
-        tiles_per_step_global = args.strong_tiles
+    if painter is not None:
+        sets_np = [[f.result() for f in row] for row in painted]
+        painter.shutdown()
     else:
-        sub = 1
-        tiles_per_step_global = world * args.batch
-    rot = max(1, args.rotate)
-    sets_host = [[torch.from_numpy(make_tiles(args.batch, size, 1 + rank + 1000 * j + 100000 * r)).pin_memory() for j in range(sub)] for r in range(rot)]
+        sets_np = [[make_tiles(args.batch, size, s) for s in row] for row in set_seeds]
+    sets_host = [[torch.from_numpy(a).pin_memory() for a in row] for row in sets_np]
+    del sets_np
     sets_dev = [[t.to(dev) for t in hs] for hs in sets_host]       # `rot` distinct sets of this rank's work, all resident in HBM
     tiles_host, tiles = sets_host[0], sets_dev[0]
     turn = [0]
@@ -444,11 +511,14 @@ def main():
         return dt, out
 
     last_rank_dt = [0.0]
+    setup_s = time.perf_counter() - t_main
     for _ in range(args.warmup):
         step()
     if world > 1:
         pipe.gather_ms()                 # drop the warm-up's gather timings
     dt, out = timed(step, args.steps)
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, out)          # now: the pipeline reuses these host buffers two submits later
     n_inst = int(out[2].sum().item()) if (rank == 0 and out is not None) else 0
     # which replay the marker-controlled watershed of the LAST timed step's network output took on this rank (one of the `rot` resident
     # sets): whole-tile replays are the exact one-lane fallback a mixed-label marker tie forces (csrc/hvn_postproc.hip)
@@ -490,6 +560,7 @@ def main():
                                   "RCCL gather to rank 0, " if world > 1 else ""),
                    "global_batch": tiles_per_step_global, "world_size": world, "batches_per_step_per_rank": sub,
                    "resident_sets_rotated": rot,
+                   "setup_s": setup_s,
                    "instances_last_step": n_inst,
                    "instances_from": "network output" if extra is None else "structured synthetic maps (the network output of this checkpoint: %d instances)" % net_inst,
                    "checkpoint": fit_info,
@@ -514,7 +585,7 @@ def main():
     # ---- per-stage split of one batch (rank 0): each stage ALONE on the launch stream, warmed, median of 5 passes ------
     # (a stage alone is not a share of the pipelined step: there the post-processing of batch i runs under the network of
     #  batch i+1; `network` <= `ms_per_step` holds because the step contains one whole network pass)
-    if rank == 0:
+    if rank == 0 and args.full:
         def med_ms(fn, reps=5, warm=2, inner=1):
             """median over `reps` of (time of `inner` back-to-back calls) / inner: with inner > 1 the host runs ahead of the GPU as
             it does in the pipelined step (a single pass from an idle stream pays ~0.7 ms of launch gaps over ~180 launches)"""
@@ -548,7 +619,7 @@ def main():
 
     # ---- variants (untimed by the driver; same K steps each) ---------------------------------------------------------
     net_rf = None              # the single-stream engine of the same checkpoint (roofline leg, single_stream_schedule variant)
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         variants = {}
         for _ in range(2):
             step(rot_host)            # (the pipeline's two upload slots and its copy stream are made at first use: rounds 3-5 timed that inside this leg, ~2 ms per step over 20 steps)
@@ -726,7 +797,7 @@ def main():
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         if net_rf is None:
             net_rf = make_net((1, 0))
         roof = roofline_of(net_rf, tiles[0], args.batch, args.dtype)
@@ -758,7 +829,7 @@ def main():
         result["config"]["network_share_of_step"] = result["config"]["stage_ms"]["network"] / ms_per_step if sub == 1 else None
 
     # ---- BASELINE cfg 3 as a driver-visible leg: fast mode, 6 types, batch 64, bf16 (rank 0, N = 1) --------------------
-    if rank == 0 and world == 1 and not args.no_variants and not args.no_cfg3 and not (args.mode == "fast" and args.dtype == "bf16"):
+    if rank == 0 and world == 1 and args.full and not args.no_variants and not args.no_cfg3 and not (args.mode == "fast" and args.dtype == "bf16"):
         nt3, b3 = 6, 64
         sd3, fit3 = make_checkpoint("fast", nt3, 256)
         net3 = make_net(None, "fast", nt3, sd3, b3, "bf16")
@@ -794,7 +865,7 @@ def main():
 
     # ---- BASELINE cfg 5 / cfg 4 as driver-visible legs (outside every timed region of the headline) ---------------------------------
     sys.path.insert(0, os.path.join(REPO, "tools"))
-    if not args.no_variants and not args.no_train_leg and not shared_gpu:
+    if args.full and not args.no_variants and not args.no_train_leg and not shared_gpu:
         # training step, both phases of the two-stage schedule (/root/reference/models/hovernet/opt.py:23-142, run_desc.py:12-109):
         # every rank runs it (N > 1: the data-parallel step with the gradient slab's all-reduce), rank 0 reports
         import train_bench
@@ -824,7 +895,7 @@ def main():
                            "atomic_reduce_ms_per_step = the same step with fp32 atomics and timed weight-gradient splits); first-writer stores, the decoder branches on their own "
                            "streams and floating weight gradients as each leg's first_writer_stores / branch_streams / wgrad_stream say (round 6, bit-identical to the single-stream step); N > 1: SUM all-reduce of the loss partial sums and of the "
                            "gradient slab in two buckets inside the step (ms_per_step = slowest rank)" % (world, args.mode, nt))
-    if world > 1 and (args.wsi_leg or not args.no_variants) and not args.no_wsi_leg:
+    if world > 1 and args.full and (args.wsi_leg or not args.no_variants) and not args.no_wsi_leg:
         # BASELINE cfg 4 on all ranks (round-5 verdict, next #4: the row-slab + halo all_to_all path of infer_wsi.py never ran in a bench):
         # per rank stage 1 (own patch rows), the halo exchange, stage 2 (owner-post-processed tiles -> rank 0's sequential merge)
         import wsi_bench
@@ -849,7 +920,7 @@ def main():
                         "post-processes the tiles whose rows it owns and sends the results to rank 0, which applies the sequential three-phase merge "
                         "(stage2_s; infer/wsi.py:449-709).  stage1_s / stage2_s = slowest rank; stage 2 runs on a structured map written into each rank's "
                         "rows (the random-init network emits no nuclei)" % (world, args.wsi_size)}
-    if rank == 0 and world == 1 and (args.wsi_leg or not args.no_variants) and not args.no_wsi_leg:
+    if rank == 0 and world == 1 and args.full and (args.wsi_leg or not args.no_variants) and not args.no_wsi_leg:
         import wsi_bench
 
         w_ = wsi_bench.measure(args.wsi_size, args.mode, nt, args.batch, "fp32", device=dev)
@@ -859,7 +930,7 @@ def main():
                      "structured prediction map of the same size (40 000^2 on one GPU: profiles/r0*_wsi_40k.json)" % args.wsi_size)
 
     # ---- CPU baseline (rank 0, N = 1): the oracle on a bounded sample of the same tiles ------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import net_torch, process_np
 
         cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)

@@ -98,7 +98,7 @@ def test_bench_step_on_two_ranks_sharing_the_gpu(launch):
     # launch = "torchrun": under the launcher, as the driver starts N > 1; "self": `python bench.py --gpus 2` alone -- the script becomes
     # its own launcher (the shape of the driver's N = 1 command).  The default (fitted) checkpoint path: rank 0 fits, the others receive it.
     args = [os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-variants",
-            "--no-roofline", "--fit-steps", "12", "--wsi-leg", "--wsi-size", "4096"]
+            "--no-roofline", "--fit-steps", "12", "--wsi-leg", "--wsi-size", "4096", "--full"]
     cmd = [sys.executable] + (["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                "--master-port", str(port)] if launch == "torchrun" else []) + args
     r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)

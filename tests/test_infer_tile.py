@@ -1,6 +1,7 @@
 """CPU: host logic of the tile path -- patch geometry / stitching against the reference's
-own `_prepare_patching` (run from its source when /root/reference exists) and known answers,
+own `_prepare_patching` (its recorded results in tests/golden, and the function itself where the reference tree exists) and known answers,
 and the N>1 rank sharding + all_gather on 2 gloo processes."""
+import hashlib
 import math
 import os
 import re
@@ -28,14 +29,21 @@ def _ref_prepare():
     return ns["_prepare_patching"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TILE), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("shape,win,msk", [((270, 270), 270, 80), ((256, 256), 256, 164), ((301, 517), 270, 80), ((1000, 731), 256, 164)])
-def test_prepare_patching_matches_reference(shape, win, msk):
+def test_prepare_patching_matches_reference(shape, win, msk, golden_dir):
+    """Against the reference's results recorded in tests/golden/patching.npz (oracle/make_golden_patching.py: padded image shape +
+    SHA-256, patch table), and against the reference itself where its tree exists."""
     img = np.random.default_rng(0).integers(0, 256, shape + (3,), dtype=np.uint8)
-    pad_ref, info_ref = _ref_prepare()(img, win, msk)
     pad, info = T.prepare_patching(img, win, msk)
-    np.testing.assert_array_equal(pad, pad_ref)
-    np.testing.assert_array_equal(info, info_ref)
+    rec = np.load(os.path.join(golden_dir, "patching.npz"))
+    key = "%dx%d_w%d_m%d" % (shape[0], shape[1], win, msk)
+    assert list(pad.shape) == rec[key + "_pad_shape"].tolist()
+    assert hashlib.sha256(np.ascontiguousarray(pad).tobytes()).digest() == rec[key + "_pad_sha256"].tobytes()
+    np.testing.assert_array_equal(info, rec[key + "_info"])
+    if os.path.exists(REF_TILE):
+        pad_ref, info_ref = _ref_prepare()(img, win, msk)
+        np.testing.assert_array_equal(pad, pad_ref)
+        np.testing.assert_array_equal(info, info_ref)
 
 
 def test_prepare_patching_known_answer():

@@ -4,12 +4,13 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 T=${1:-bench}; R=${2:-r05}; O=gpurun_out/${R}_${T}.log; : > $O
+D=${O%/*}           # the output folder
 bench() {   # bench <name> [env / args ...]: one bench.py run -> gpurun_out/<R>_<name>.json + its summary in the log
   local name=$1; shift
   SECONDS=0
-  env "${ENVV[@]}" timeout 900 python bench.py "$@" > gpurun_out/${R}_${name}.json 2> gpurun_out/${R}_${name}.err
+  env "${ENVV[@]}" timeout 900 python bench.py --full "$@" > $D/${R}_${name}.json 2> $D/${R}_${name}.err
   echo "== bench $name (${ENVV[*]} $*) rc=$? wall=${SECONDS}s" >> $O
-  python tools/bench_summary.py gpurun_out/${R}_${name}.json >> $O 2>&1 || tail -5 gpurun_out/${R}_${name}.err >> $O
+  python tools/bench_summary.py $D/${R}_${name}.json >> $O 2>&1 || tail -5 $D/${R}_${name}.err >> $O
 }
 ENVV=()
 case $T in
