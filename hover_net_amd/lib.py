@@ -21,7 +21,7 @@ VARIANTS = {
 }
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("hvn_conv.hip", "hvn_conv_chain.hip", "hvn_conv_chain_x3.hip", "hvn_conv_chain_x3r.hip", "hvn_conv_bf16.hip", "hvn_conv_bf16g.hip", "hvn_conv_chain_bf16.hip", "hvn_conv_x3.hip", "hvn_conv_x3g.hip", "hvn_net_ops.hip", "hvn_postproc.hip", "hvn_api.hip", "hvn_train.hip", "hvn_wgrad_x3.hip", "hvn_targets.hip", "hvn_wsi_merge.hip",
-           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp")
+           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_metrics.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                "-fvisibility=hidden", "-Wno-unused-value", "-pthread")
 
@@ -73,6 +73,8 @@ EXPORTS = (
     "hvn_run_train_plan", "hvn_run_train_plan_ws", "hvn_train_workspace_bytes", "hvn_train_last_error", "hvn_loss_partials_count", "hvn_loss_forward", "hvn_loss_backward", "hvn_adam_step",
     "hvn_extract_patches", "hvn_gen_targets", "hvn_gen_targets_workspace_bytes", "hvn_augment_shape", "hvn_augment_input",
     "hvn_wsi_merge_normal", "hvn_wsi_merge_fixing",
+    "hvn_pair_table_workspace_bytes", "hvn_pair_table", "hvn_label_range", "hvn_remap_label_workspace_bytes", "hvn_remap_label",
+    "hvn_label_areas", "hvn_label_permute",
 )
 
 
@@ -250,6 +252,17 @@ def lib():
         L.hvn_wsi_merge_fixing.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.hvn_pair_table_workspace_bytes.restype = ctypes.c_size_t
+        L.hvn_pair_table_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.hvn_pair_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.hvn_label_range.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.hvn_remap_label_workspace_bytes.restype = ctypes.c_size_t
+        L.hvn_remap_label_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32]
+        L.hvn_remap_label.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.hvn_label_areas.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        L.hvn_label_permute.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
         L.hvn_train_last_error.restype = ctypes.c_char_p
         L.hvn_run_train_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.hvn_run_train_plan_ws.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]

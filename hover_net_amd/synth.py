@@ -6,6 +6,8 @@
   `h`/`v` the per-instance horizontal/vertical distance maps in [-1, 1] (semantics of
   /root/reference/models/hovernet/targets.py:63-93), plus noise.  These give the
   post-processing a realistic instance load independent of any weights.
+* `synth_inst_pair` -- a ground-truth / prediction pair of int32 instance maps (disks; the prediction shifted, with merged,
+  split, missed and spurious instances) for the metrics (hover_net_amd/metrics.py).
 """
 import numpy as np
 
@@ -149,3 +151,53 @@ def synth_train_batch(n, mode="original", nr_types=None, seed=0):
     if nr_types is not None:
         batch["tp_map"] = np.clip(pm[..., 0].round().astype(np.int64), 0, nr_types - 1) * (inst > 0)
     return batch
+
+
+def synth_inst_pair(h, w, n_inst, seed=0, r_lo=3, r_hi=9, shift=(2, 1), n_merge=None, n_split=None, n_miss=None, n_spurious=None,
+                    id_stride=1, id_base=0):
+    """(true, pred) int32 [h, w]: `n_inst` disks of radius r_lo..r_hi (later ones drawn over earlier ones, ids 1..n_inst);
+    pred = true rolled by `shift`, then n_merge neighbouring pairs merged, n_split instances cut in two along their centre
+    column, n_miss removed and n_spurious new disks added (each defaults to ~3 % of n_inst).  Non-zero ids of both maps become
+    id_base + id_stride * id (non-contiguous ids; the largest must stay within int32)."""
+    rng = np.random.default_rng(seed)
+    d = lambda v: max(1, n_inst // 33) if v is None else v  # noqa: E731
+    true = np.zeros((h, w), np.int64)
+    yy, xx = np.ogrid[:h, :w]
+    cen = []
+    for i in range(1, n_inst + 1):
+        r = int(rng.integers(r_lo, r_hi + 1))
+        cy, cx = int(rng.integers(0, h)), int(rng.integers(0, w))
+        y0, y1, x0, x1 = max(0, cy - r), min(h, cy + r + 1), max(0, cx - r), min(w, cx + r + 1)
+        m = (yy[y0:y1] - cy) ** 2 + (xx[:, x0:x1] - cx) ** 2 <= r * r
+        true[y0:y1, x0:x1][m] = i
+        cen.append((cy, cx))
+    pred = np.roll(true, shift, (0, 1)).copy()
+    nxt = n_inst + 1
+    ids = np.unique(pred)[1:]
+    for _ in range(d(n_merge)):
+        if len(ids) < 2:
+            break
+        a, b = rng.choice(ids, 2, replace=False)
+        pred[pred == b] = a
+    for _ in range(d(n_split) if len(ids) else 0):
+        a = int(rng.choice(ids))
+        ys, xs = np.nonzero(pred == a)
+        if len(xs) > 1:
+            half = xs > int(np.median(xs))
+            pred[ys[half], xs[half]] = nxt
+            nxt += 1
+    for _ in range(d(n_miss) if len(ids) else 0):
+        pred[pred == int(rng.choice(ids))] = 0
+    for _ in range(d(n_spurious)):
+        r = int(rng.integers(r_lo, r_hi + 1))
+        cy, cx = int(rng.integers(0, h)), int(rng.integers(0, w))
+        y0, y1, x0, x1 = max(0, cy - r), min(h, cy + r + 1), max(0, cx - r), min(w, cx + r + 1)
+        m = ((yy[y0:y1] - cy) ** 2 + (xx[:, x0:x1] - cx) ** 2 <= r * r) & (pred[y0:y1, x0:x1] == 0)
+        pred[y0:y1, x0:x1][m] = nxt
+        nxt += 1
+    out = []
+    for a in (true, pred):
+        a = np.where(a > 0, id_base + id_stride * a, 0)
+        assert a.max() <= 2 ** 31 - 1
+        out.append(a.astype(np.int32))
+    return out[0], out[1]

@@ -169,6 +169,27 @@ HVN_API int hvn_instance_table(const int32_t *inst, const float *pred, int n, in
                                int nr_types, hvn_inst_rec *records, int32_t *counts, int max_inst,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* -- instance-segmentation metrics: the exact integer tables behind metrics/stats_utils.py (get_fast_pq, get_fast_aji,
+ * get_fast_aji_plus, get_dice_1, get_fast_dice_2, get_dice_2, remap_label); hover_net_amd/metrics.py does the float arithmetic.
+ * All maps: dev int32 [n][h][w], h * w <= 2^30, n <= 65535.
+ * Pair table: every distinct (t, p, count) over the pixels whose pair (true, pred) is not (0, 0), labels >= 0 and otherwise
+ * arbitrary; triples: dev int32 [n][h * w][3], image i's first counts[i] rows in no canonical order; counts: dev int32 [n]. */
+HVN_API size_t hvn_pair_table_workspace_bytes(int n, int h, int w);
+HVN_API int hvn_pair_table(const int32_t *true_map, const int32_t *pred_map, int n, int h, int w, int32_t *triples, int32_t *counts,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* range: dev int32 [n][2] = (smallest, largest) label of each map. */
+HVN_API int hvn_label_range(const int32_t *map, int n, int h, int w, int32_t *range, void *stream);
+/* remap_label(by_size=False): out = 0 where map <= 0 or > max_id, else 1 + the number of distinct labels of the image in
+ * (0, label); n_ids: dev int32 [n] = distinct labels in [1, max_id] per image.  out may alias map.  Workspace: two bits per
+ * label value in [0, max_id] per image (512 MB per image at max_id = INT32_MAX). */
+HVN_API size_t hvn_remap_label_workspace_bytes(int n, int h, int w, int32_t max_id);
+HVN_API int hvn_remap_label(const int32_t *map, int n, int h, int w, int32_t max_id, int32_t *out, int32_t *n_ids, void *workspace,
+                            size_t workspace_bytes, void *stream);
+/* areas: dev int32 [n][max_label + 1] = pixels of each label in [0, max_label] (others are not counted). */
+HVN_API int hvn_label_areas(const int32_t *map, int n, int h, int w, int32_t max_label, int32_t *areas, void *stream);
+/* map = perm[image][map] in place where 0 <= map <= max_label; perm: dev int32 [n][max_label + 1]. */
+HVN_API int hvn_label_permute(int32_t *map, int n, int h, int w, int32_t max_label, const int32_t *perm, void *stream);
+
 /* -- whole-slide merge: infer/wsi.py:569-599 post_proc_normal_tile_callback, :602-677 post_proc_fixing_tile_callback and :51-60
  * _remove_inst on a DEVICE-resident int32 instance map [H][map_w] (tiles strictly in the reference's order: the id offset is the
  * running maximum id and the fix-up windows overlap).  pred_inst: dev int32 [h][w] local ids of the tile at (y0, x0).
