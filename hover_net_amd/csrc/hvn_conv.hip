@@ -36,10 +36,7 @@
 
 #include <type_traits>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP's float4 struct copies lower to memcpy -> scratch
+#include "hvn_conv_common.h"
 
 #define BK 32
 // LDS row layout of the staged A / B tiles (rows of BK = 32 floats = eight 16-byte chunks):
@@ -52,15 +49,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP'
 #ifndef HVN_SWZ
 #define HVN_SWZ 1
 #endif
-// Experiment builds (lib.VARIANTS, default 0: the default library is byte-identical without them; NOT yet measured -- prepared for the next GPU session):
-//   HVN_EPI_LINEAR=1  branch-free epilogue addressing for row-contiguous output / residual views (offset = base[sample] + m * pixel stride)
-//   HVN_NT=1          non-temporal hints on the epilogue's residual loads and output stores (read once / written once per launch)
-#ifndef HVN_EPI_LINEAR
-#define HVN_EPI_LINEAR 0
-#endif
-#ifndef HVN_NT
-#define HVN_NT 0
-#endif
+// Diagnosis build (lib.VARIANTS["trace"]):
 //   HVN_TRACE_FINE=1  (with HVN_CONV_TRACE) 8 instead of 4 words per workgroup: + the end of each epilogue phase (accumulators in LDS and
 //                     barrier passed, residual loads returned, values finished, stores issued); the phase waits it inserts perturb the timing
 //                     a little -- a diagnosis build (tools/conv_trace.py --fine)
@@ -74,22 +63,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP'
 #define LDS_LD 36  // padded row length in floats
 #endif
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, int ABL = 0, bool GROUPED = false, bool HAS_PRE = true, bool HAS_X2 = false>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool GROUPED = false, bool HAS_PRE = true, bool HAS_X2 = false>
 __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) void hvn_conv_igemm_f32(ConvArgs p)
 {
-    // EXPERIMENT (off by default, HVN_STAGGER=1|2|3): two workgroups share a CU, i.e. two waves share each SIMD's matrix pipe; giving
-    // one of them a raised issue priority (told apart by LDS base or wave slot) or a delayed start was meant to keep one
-    // workgroup's epilogue under the other's k-loop.  Measured: no effect (profiles/r02_experiments.md section 7).
-    if (p.stagger) {
-        // the two workgroups of a CU are told apart by where their LDS allocation starts (HW_REG_LDS_ALLOC[7:0] = LDS_BASE)
-        const unsigned lds_base = __builtin_amdgcn_s_getreg(6 | (0 << 6) | ((8 - 1) << 11));
-        if (p.stagger == 1 && lds_base != 0u) __builtin_amdgcn_s_setprio(3);
-        if (p.stagger == 2) {               // variant: by the wave slot on the SIMD (HW_REG_HW_ID[3:0])
-            const unsigned slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | ((4 - 1) << 11));
-            if (slot & 1u) __builtin_amdgcn_s_setprio(3);
-        }
-        if (p.stagger == 3 && lds_base != 0u) __builtin_amdgcn_s_sleep(127);   // variant: the second workgroup starts ~8k cycles late (no priority)
-    }
     unsigned long long t_start = 0, t_kend = 0;
     if (p.dbg) t_start = __builtin_readcyclecounter();
     if (p.nbatch > 1) {  // batched launch: one of nbatch independent problems per blockIdx.y
@@ -135,7 +111,6 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;                                        // sample of the tile's first row
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;       // keeps every thread offset >= 0
-    constexpr unsigned OOB = 0x80000000u;
     unsigned a_voff[PA];
     int a_iy[PA], a_ix[PA];
 #pragma unroll
@@ -149,18 +124,18 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
         a_iy[j] = ok ? (int)oy * p.stride - p.pad_t : -(1 << 28);
         a_ix[j] = ok ? (int)ox * p.stride - p.pad_l : -(1 << 28);
         a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + scol) * 4)
-                       : OOB;  // rows past the end of the batch load zeros (buffer range check)
+                       : HVN_OOB;  // rows past the end of the batch load zeros (buffer range check)
     }
     const float *xblk = p.x + (long)n_blk * p.xsn - padoff;
     // Buffer descriptors: address = base + soffset (SGPR, moves with the k-step) + voffset (VGPR, loop-invariant),
     // so a load carries NO vector address arithmetic; voffset >= num_records makes the hardware return 0, which is
     // how out-of-image taps (zero padding) and tail rows are produced without a select.
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)xblk, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = hvn_buf(xblk);
+    const __amdgpu_buffer_rsrc_t rsrc_w = hvn_buf(p.w);
     // optional second 1x1 input (fused shortcut): its channels extend the reduction after the first input's
     unsigned a2_voff[PA];
     const float *x2blk = HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x;
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc((void *)x2blk, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = hvn_buf(x2blk);
     if constexpr (HAS_X2) {
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
@@ -170,7 +145,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
             const unsigned n = mm / HoWo;
             const unsigned rem = mm - n * HoWo;
             const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : OOB;
+            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : HVN_OOB;
         }
     }
     const long Ktot = (long)p.KH * p.KW * p.Cin + (HAS_X2 ? p.Cin2 : 0);
@@ -198,9 +173,8 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
 
     // issue the raw loads of one k-step (nothing here waits on memory)
     auto load_global = [&](Stage &st, int kt) {
-        // uniform (SALU).  Channels-last: slab ld_c starts at channel 32 ld_c.  Blocked experiment: block (ld_c >> s) + slab (ld_c & mask) inside it
-        const unsigned cs = p.blk_shift ? (unsigned)p.blk_shift - 5u : 31u;
-        int a_soff = (int)(((long)ld_r * p.xsy + (long)ld_s * p.xsx + (long)((unsigned)ld_c >> cs) * p.xsb + (long)((unsigned)ld_c & ((1u << cs) - 1u)) * BK) * 4);
+        // uniform (SALU).  Channels-last: slab ld_c starts at channel 32 ld_c
+        int a_soff = (int)(((long)ld_r * p.xsy + (long)ld_s * p.xsx + (long)ld_c * BK) * 4);
         const int w_soff = kt * (BK * 4);
         const bool second = HAS_X2 && kt >= KT1;                                             // uniform
         if constexpr (HAS_X2) a_soff = second ? (kt - KT1) * (BK * 4) : a_soff;
@@ -213,7 +187,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
             unsigned vo = a_voff[j];
             if constexpr (PADDED) {
                 const bool ok = (unsigned)(a_iy[j] + ld_r) < (unsigned)p.H && (unsigned)(a_ix[j] + ld_s) < (unsigned)p.W;
-                vo = ok ? vo : OOB;
+                vo = ok ? vo : HVN_OOB;
             }
             if constexpr (HAS_X2) {
                 vo = second ? a2_voff[j] : vo;
@@ -349,24 +323,9 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
         constexpr int PER_Q = TM * TN * 4;                       // MFMAs per k-sub-chunk of 8
         constexpr int Q1 = (NQ >= 4 && PER_Q >= 8) ? 1 : NQ / 2;  // sub-chunks in segment 1
         constexpr int Q2 = (NQ >= 4 && PER_Q >= 8) ? 3 : NQ;      // end of segment 2
-        if constexpr (ABL == 3) {
-            f32x4 fa0 = stg.ra[0], fb0 = stg.rb[0];  // pure MFMA: fragments held in registers
-#pragma unroll
-            for (int rep = 0; rep < 4; ++rep)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0.x, fb0.x, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0.y, fb0.y, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0.z, fb0.z, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0.w, fb0.w, acc[i][j], 0, 0, 0);
-                    }
-            return;
-        }
         // ---- segment 1 ----
         mma(kt, integral_constant<int, 0>{}, integral_constant<int, Q1>{});
-        if constexpr (decltype(do_load)::value && ABL < 1) load_global(ld, kt + 2);
+        if constexpr (decltype(do_load)::value) load_global(ld, kt + 2);
 #pragma unroll
         for (int g = 0; g < Q1 * PER_Q; ++g) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
@@ -376,19 +335,17 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
         __builtin_amdgcn_sched_barrier(0);
         // ---- segment 2 ----
         mma(kt, integral_constant<int, Q1>{}, integral_constant<int, Q2>{});
-        if constexpr (ABL < 2) {
-            store_lds(stg, (kt + 1) & 1);
+        store_lds(stg, (kt + 1) & 1);
 #pragma unroll
-            for (int g = 0; g < (Q2 - Q1) * PER_Q; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
-                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
-            }
+        for (int g = 0; g < (Q2 - Q1) * PER_Q; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- segment 3 ----
         if constexpr (Q2 < NQ) mma(kt, integral_constant<int, Q2>{}, integral_constant<int, NQ>{});
-        if constexpr (ABL < 2) __syncthreads();
+        __syncthreads();
     };
     const std::true_type LOAD{};
     const std::false_type NOLOAD{};
@@ -465,19 +422,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     constexpr int NIT = BM / RPP;         // rows per thread: 16 / 8 / 4
     // this thread's rows are m0 + erow0 + k*RPP: decode the first with divisions, walk the rest (n, oy, ox) incrementally
     // (32 integer divisions per thread and tile were ~10 % of a short-K tile's instruction stream)
-#if HVN_EPI_LINEAR
-    // row-contiguous views: offset(n, oy, ox) = n * sn + (m - n * HoWo) * sx; a 128-row tile touches at most two samples (HoWo >= BM)
-    const bool lin = p.ysy == (long)p.Wo * p.ysx && (!has_res || p.rsy == (long)p.Wo * p.rsx) && HoWo >= (unsigned)BM && !p.ysb && !p.rsb;   // uniform
-    const unsigned lin_bound = (n_blk + 1u) * HoWo;                       // first pixel row of the next sample
-    const long ybase0 = (long)n_blk * p.ysn - (long)n_blk * HoWo * p.ysx + co, ybase1 = ybase0 + p.ysn - (long)HoWo * p.ysx;
-    const long rbase0 = (long)n_blk * p.rsn - (long)n_blk * HoWo * p.rsx + co, rbase1 = rbase0 + p.rsn - (long)HoWo * p.rsx;
-#endif
-#if HVN_EPI_LINEAR
-    unsigned e_n = 0, e_oy = 0, e_ox = 0;
-    if (!lin)
-#else
     unsigned e_n, e_oy, e_ox;
-#endif
     {
         const unsigned m = m0 + erow0;
         e_n = m / HoWo;
@@ -491,31 +436,13 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     // round trips per tile, 30-50 k cycles against a 14-40 k cycle k-loop on the K <= 512 layers (per-workgroup timelines,
     // profiles/r02_experiments.md).
     f32x4 rall[NIT];
-#if HVN_EPI_LINEAR
-    if (has_res && ABL != 4 && lin) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const unsigned m = m0 + erow0 + it * RPP;
-            const long ro = (m < M && cok) ? (m >= lin_bound ? rbase1 : rbase0) + (long)m * p.rsx : 0;
-#if HVN_NT
-            rall[it] = __builtin_nontemporal_load((const f32x4 *)(p.res + ro));
-#else
-            rall[it] = *(const f32x4 *)(p.res + ro);
-#endif
-        }
-    } else
-#endif
-    if (has_res && ABL != 4) {
+    if (has_res) {
         unsigned a_n = e_n, a_oy = e_oy, a_ox = e_ox;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const unsigned m = m0 + erow0 + it * RPP;
-            const long ro = (m < M && cok) ? (long)a_n * p.rsn + (long)a_oy * p.rsy + (long)a_ox * p.rsx + (p.rsb ? (long)(co >> p.blk_shift) * p.rsb + (co & ((1 << p.blk_shift) - 1)) : (long)co) : 0;
-#if HVN_NT
-            rall[it] = __builtin_nontemporal_load((const f32x4 *)(p.res + ro));
-#else
+            const long ro = (m < M && cok) ? (long)a_n * p.rsn + (long)a_oy * p.rsy + (long)a_ox * p.rsx + (long)co : 0;
             rall[it] = *(const f32x4 *)(p.res + ro);
-#endif
             a_ox += RPP;
             while (a_ox >= (unsigned)p.Wo) {
                 a_ox -= (unsigned)p.Wo;
@@ -546,27 +473,15 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     for (int it = 0; it < NIT; ++it) {
         const unsigned m = m0 + erow0 + it * RPP;
         oks[it] = m < M && cok;
-        yoffs[it] = (long)e_n * p.ysn + (long)e_oy * p.ysy + (long)e_ox * p.ysx + (p.ysb ? (long)(co >> p.blk_shift) * p.ysb + (co & ((1 << p.blk_shift) - 1)) : (long)co);
-#if HVN_EPI_LINEAR
-        if (lin) yoffs[it] = (m >= lin_bound ? ybase1 : ybase0) + (long)m * p.ysx;
-#endif
-        if constexpr (ABL == 6) {   // experiment: the tile's 64 KB written as ONE contiguous block (wrong place, right amount)
-            yoffs[it] = ((long)(m_tile * NT + n_tile) * BM + (erow0 + it * RPP)) * BN + ecol;
-            oks[it] = oks[it] && yoffs[it] + 4 <= (long)M * p.Cout;
+        yoffs[it] = (long)e_n * p.ysn + (long)e_oy * p.ysy + (long)e_ox * p.ysx + (long)co;
+        e_ox += RPP;
+        while (e_ox >= (unsigned)p.Wo) {
+            e_ox -= (unsigned)p.Wo;
+            ++e_oy;
         }
-#if HVN_EPI_LINEAR
-        if (!lin)
-#endif
-        {
-            e_ox += RPP;
-            while (e_ox >= (unsigned)p.Wo) {
-                e_ox -= (unsigned)p.Wo;
-                ++e_oy;
-            }
-            while (e_oy >= (unsigned)p.Ho) {
-                e_oy -= (unsigned)p.Ho;
-                ++e_n;
-            }
+        while (e_oy >= (unsigned)p.Ho) {
+            e_oy -= (unsigned)p.Ho;
+            ++e_n;
         }
         const int rr = erow0 + it * RPP;
         f32x4 v = *(const f32x4 *)(ep + rr * EP_LD + ecol);
@@ -590,15 +505,8 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     if (p.dbg) t_f[2] = __builtin_readcyclecounter();
 #endif
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        if constexpr (ABL != 4) {
-#if HVN_NT
-            if (oks[it]) __builtin_nontemporal_store(vout[it], (f32x4 *)(p.y + yoffs[it]));
-#else
-            if (oks[it]) *(f32x4 *)(p.y + yoffs[it]) = vout[it];
-#endif
-        } else if (vout[it].x == 12345.678f && oks[it]) *(f32x4 *)(p.y + yoffs[it]) = vout[it];   // keeps the math alive, stores nothing
-    }
+    for (int it = 0; it < NIT; ++it)
+        if (oks[it]) *(f32x4 *)(p.y + yoffs[it]) = vout[it];
 #if HVN_TRACE_FINE
     if (p.dbg) t_f[3] = __builtin_readcyclecounter();        // stores issued (not yet acknowledged)
 #endif
@@ -619,16 +527,10 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, int ABL = 0, bool GROUPED = false, bool HAS_PRE = true, bool HAS_X2 = false>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool GROUPED = false, bool HAS_PRE = true, bool HAS_X2 = false>
 static int launch_conv(const ConvArgs &a, hipStream_t stream)
 {
     ConvArgs p = a;
-    static int stagger = -1;
-    if (stagger < 0) {
-        const char *e = getenv("HVN_STAGGER");   // experiment switch (profiles/r02_experiments.md section 7): 0 = off (default)
-        stagger = e ? atoi(e) : 0;
-    }
-    p.stagger = stagger;
     static unsigned long long *dbg_buf = nullptr;
     static int dbg_on = -1;
     if (dbg_on < 0) {
@@ -642,7 +544,7 @@ static int launch_conv(const ConvArgs &a, hipStream_t stream)
     constexpr size_t stage_fl = (size_t)2 * (BM + BN) * LDS_LD, ep_fl = (size_t)BM * (BN + 4);   // staging buffers / epilogue tile (floats)
     const size_t lds = (stage_fl > ep_fl ? stage_fl : ep_fl) * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = hvn_conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, PADDED, ABL, GROUPED, HAS_PRE, HAS_X2>;
+    auto kern = hvn_conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, PADDED, GROUPED, HAS_PRE, HAS_X2>;
     if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
     const long groups = (p.m_tiles + 7) / 8;
     const long grid = groups * 8 * p.n_tiles;
@@ -666,63 +568,41 @@ int hvn_launch_dense_grouped(const ConvArgs &a, hipStream_t stream);
 int hvn_launch_conv(const ConvArgs &a, int tile_n, hipStream_t stream)
 {
     if (a.Cin % BK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;  // 32-bit pixel index arithmetic in the kernel
-    // 32-bit per-thread byte offsets relative to the sample of the tile's first row; 2^31 and beyond is the "load zeros" range of the
-    // buffer descriptor.  A tile of bm rows reaches (HoWo + bm - 2) / HoWo samples ahead -- ONE when a sample holds a tile's worth of
-    // pixels, FOUR for a Winograd-domain product with 36 tiles per sample: with the arena's 0.5 GB sample stride that is beyond the
-    // reach, and rows would silently read zeros (round 4: the F(6x6,3x3) product of d3 in 'fast' mode).  Refused here instead.
+    // 32-bit pixel indices and per-thread byte offsets into x / x2 (the epilogue addresses y and res with 64 bits)
     const int bm = tile_n == 320 ? 256 : 128;
-    const long howo = (long)a.Ho * a.Wo;
-    if (howo <= 0) return -1;
-    const long ahead = (howo + bm - 2) / howo;
-    const long span = ahead * a.xsn + (long)(a.H + a.KH) * a.xsy + (long)(a.W + a.KW) * a.xsx;
-    if (span < 0 || span * 4 >= (1L << 31)) return -1;
-    if (a.x2 && (ahead * a.x2sn + (long)a.H * a.x2sy * a.stride2) * 4 >= (1L << 31)) return -1;
+    if (!hvn_conv_reach_ok(a, bm, 4, 256, true, false)) return -1;
     if ((long)(a.Cout + 128) * a.KH * a.KW * a.Cin * 4 >= (1L << 32)) return -1;
-    // "padded" = some tap of some output pixel falls outside the input window
-    const bool padded = a.pad_t > 0 || a.pad_l > 0 || (a.Ho - 1) * a.stride - a.pad_t + a.KH > a.H ||
-                        (a.Wo - 1) * a.stride - a.pad_l + a.KW > a.W;
+    const bool padded = hvn_conv_padded(a);
     if (padded && a.pre_s) return -1;  // zero padding is produced by the load, before a prologue could run
-    static int abl = -1;
-    if (abl < 0) {
-        const char *e = getenv("HVN_CONV_ABLATE");
-        abl = e ? atoi(e) : 0;
-    }
     if (a.x2) {  // fused shortcut: 1x1, no prologue, no padding (validated by the caller)
         if (padded || a.Cin2 % BK) return -1;
-        if (tile_n == 128) return launch_conv<128, 128, 2, 2, false, 0, false, false, true>(a, stream);
-        if (tile_n == 64) return launch_conv<128, 64, 4, 1, false, 0, false, false, true>(a, stream);
+        if (tile_n == 128) return launch_conv<128, 128, 2, 2, false, false, false, true>(a, stream);
+        if (tile_n == 64) return launch_conv<128, 64, 4, 1, false, false, false, true>(a, stream);
         return -1;
     }
     switch (tile_n) {
     case 128:
-        if (abl == 1) return launch_conv<128, 128, 2, 2, true, 1>(a, stream);
-        if (abl == 2) return launch_conv<128, 128, 2, 2, true, 2>(a, stream);
-        if (abl == 3) return launch_conv<128, 128, 2, 2, true, 3>(a, stream);
-        if (abl == 4) return launch_conv<128, 128, 2, 2, true, 4>(a, stream);
-        if (abl == 6) return launch_conv<128, 128, 2, 2, true, 6>(a, stream);
-        if (abl == 5) return launch_conv<128, 128, 2, 2, true, 0>(a, stream);   // the same instantiation without ablation (PADDED + prologue code paths on): the baseline of the ablation series
-        if (!a.pre_s && !getenv("HVN_NO_RAWSTORE"))
-            return padded ? launch_conv<128, 128, 2, 2, true, 0, false, false>(a, stream) : launch_conv<128, 128, 2, 2, false, 0, false, false>(a, stream);
+        if (!a.pre_s)
+            return padded ? launch_conv<128, 128, 2, 2, true, false, false>(a, stream) : launch_conv<128, 128, 2, 2, false, false, false>(a, stream);
         return padded ? launch_conv<128, 128, 2, 2, true>(a, stream) : launch_conv<128, 128, 2, 2, false>(a, stream);
     case 64:
-        if (!a.pre_s && !getenv("HVN_NO_RAWSTORE"))
-            return padded ? launch_conv<128, 64, 4, 1, true, 0, false, false>(a, stream) : launch_conv<128, 64, 4, 1, false, 0, false, false>(a, stream);
+        if (!a.pre_s)
+            return padded ? launch_conv<128, 64, 4, 1, true, false, false>(a, stream) : launch_conv<128, 64, 4, 1, false, false, false>(a, stream);
         return padded ? launch_conv<128, 64, 4, 1, true>(a, stream) : launch_conv<128, 64, 4, 1, false>(a, stream);
     case 320:
         // 256 x 64 tiles for the 64-channel layers (d0's 3x3 convs, u1.conva's Winograd products): a wave owns 64 x 64 like in the
         // 128 x 128 tile, so a k-step carries 64 MFMAs per wave instead of 32 between two barriers (tile_n = 64 | 0x100; chosen per
         // launch shape by Engine.autotune_tiles; same k order per output element, same bits)
-        if (!a.pre_s && !getenv("HVN_NO_RAWSTORE"))
-            return padded ? launch_conv<256, 64, 4, 1, true, 0, false, false>(a, stream) : launch_conv<256, 64, 4, 1, false, 0, false, false>(a, stream);
+        if (!a.pre_s)
+            return padded ? launch_conv<256, 64, 4, 1, true, false, false>(a, stream) : launch_conv<256, 64, 4, 1, false, false, false>(a, stream);
         return padded ? launch_conv<256, 64, 4, 1, true>(a, stream) : launch_conv<256, 64, 4, 1, false>(a, stream);
     case 32:
-        // dense-unit conv2: patch-staged kernel (no per-tap restaging); HVN_NO_DENSE_KERNEL=1 falls back to the generic grouped path
+        // dense-unit conv2: patch-staged kernel (no per-tap restaging)
         if (a.groups == 4 && a.Cin == 128 && a.Cout == 32 && a.stride == 1 && !padded && !a.pre_s && !a.res && !a.post_s && a.nbatch <= 1 &&
-            a.KH == a.KW && (a.KH == 5 || a.KH == 3) && !getenv("HVN_NO_DENSE_KERNEL"))
+            a.KH == a.KW && (a.KH == 5 || a.KH == 3))
             return hvn_launch_dense_grouped(a, stream);
-        if (a.groups == 4 && a.Cin == 128 && a.Cout == 32 && !getenv("HVN_NO_GROUPED"))
-            return padded ? launch_conv<128, 32, 4, 1, true, 0, true>(a, stream) : launch_conv<128, 32, 4, 1, false, 0, true>(a, stream);
+        if (a.groups == 4 && a.Cin == 128 && a.Cout == 32)
+            return padded ? launch_conv<128, 32, 4, 1, true, true>(a, stream) : launch_conv<128, 32, 4, 1, false, true>(a, stream);
         if (a.groups != 1 && !(a.groups == 4 && a.Cin == 128 && a.Cout == 32)) return -1;
         return padded ? launch_conv<128, 32, 4, 1, true>(a, stream) : launch_conv<128, 32, 4, 1, false>(a, stream);
     default: return -1;

@@ -20,25 +20,10 @@
 
 #include <type_traits>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "hvn_conv_common.h"
 
 #define BKH 64      // reduction elements per k-step
 #define LDH 72      // LDS row pitch in bf16 elements (144 B: conflict-free ds_read_b128 / ds_write_b128)
-
-__device__ inline float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ inline float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-__device__ inline uint32_t pack_bf(float a, float b)
-{
-    bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
 
 // WIDE = true (round 4, default): the loop structure of hvn_conv_x3.hip -- a k-step is TWO 64-channel chunks side by side in one LDS
 // buffer (row pitch 272 B = 68 banks = 4 x 17: conflict-free ds_read_b128), barrier, store the staged step, barrier, issue the next
@@ -81,7 +66,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;
-    constexpr unsigned OOB = 0x80000000u;
     unsigned a_voff[PA];
     int a_iy[PA], a_ix[PA];
 #pragma unroll
@@ -94,14 +78,14 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
         a_iy[j] = ok ? (int)oy * p.stride - p.pad_t : -(1 << 28);
         a_ix[j] = ok ? (int)ox * p.stride - p.pad_l : -(1 << 28);
-        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + scol) * 2) : OOB;
+        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + scol) * 2) : HVN_OOB;
     }
     const uint16_t *xblk = px + (long)n_blk * p.xsn - padoff;
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)xblk, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void *)pw, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = hvn_buf(xblk);
+    const __amdgpu_buffer_rsrc_t rsrc_w = hvn_buf(pw);
     unsigned a2_voff[PA];
     const uint16_t *x2blk = HAS_X2 ? (const uint16_t *)p.x2 + (long)n_blk * p.x2sn : px;
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc((void *)x2blk, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = hvn_buf(x2blk);
     if constexpr (HAS_X2) {
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
             const unsigned n = mm / HoWo;
             const unsigned rem = mm - n * HoWo;
             const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 2) : OOB;
+            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 2) : HVN_OOB;
         }
     }
     const int kchunks = (p.Cin + BKH - 1) / BKH;
@@ -145,18 +129,18 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
             unsigned vo = a_voff[j];
             if constexpr (PADDED) {
                 const bool ok = (unsigned)(a_iy[j] + ld_r) < (unsigned)p.H && (unsigned)(a_ix[j] + ld_s) < (unsigned)p.W;
-                vo = ok ? vo : OOB;
+                vo = ok ? vo : HVN_OOB;
             }
-            vo = zero_half ? OOB : vo;
+            vo = zero_half ? HVN_OOB : vo;
             if constexpr (HAS_X2) {
                 vo = second ? a2_voff[j] : vo;
-                vo = past ? OOB : vo;
+                vo = past ? HVN_OOB : vo;
                 s.ra[j] = __builtin_amdgcn_raw_buffer_load_b128(second ? rsrc_a2 : rsrc_a, vo, a_soff, 0);
             } else
                 s.ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, vo, a_soff, 0);
         }
 #pragma unroll
-        for (int j = 0; j < PB; ++j) s.rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, past ? OOB : w_voff[j], w_soff, 0);
+        for (int j = 0; j < PB; ++j) s.rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, past ? HVN_OOB : w_voff[j], w_soff, 0);
         if (past) return;
         if (++ld_s == p.KW) {
             ld_s = 0;
@@ -188,9 +172,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
                     const float b_[8] = {pb0.x, pb0.y, pb0.z, pb0.w, pb1.x, pb1.y, pb1.z, pb1.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float lo = fmaxf(fmaf(bf_lo(v[e]), s_[2 * e], b_[2 * e]), 0.f);
-                        const float hi = fmaxf(fmaf(bf_hi(v[e]), s_[2 * e + 1], b_[2 * e + 1]), 0.f);
-                        v[e] = pack_bf(lo, hi);
+                        const float lo = fmaxf(fmaf(hvn_bf16_lo(v[e]), s_[2 * e], b_[2 * e]), 0.f);
+                        const float hi = fmaxf(fmaf(hvn_bf16_hi(v[e]), s_[2 * e + 1], b_[2 * e + 1]), 0.f);
+                        v[e] = hvn_bf16_pack(lo, hi);
                     }
                 }
             }
@@ -301,7 +285,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
         // rows m0 + erow0 + it * RPP: the first located with divisions, the rest walked incrementally; addresses = 32-bit byte offsets from the
         // sample of the tile's first row through buffer descriptors (hvn_conv_x3g.hip: the 64-bit products per load / store cost several times
         // the arithmetic they served); out-of-range offset = zeros loaded, store dropped
-        constexpr unsigned EOOB = 0x80000000u;
         unsigned oy, ox, y_off, r_off;
         const unsigned e_nblk = m0 / HoWo;
         {
@@ -315,9 +298,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
         }
         const unsigned y_step = (unsigned)(RPP * p.ysx * 2), y_row = (unsigned)((p.ysy - (long)p.Wo * p.ysx) * 2), y_smp = (unsigned)((p.ysn - (long)p.Ho * p.ysy) * 2);
         const unsigned r_step = (unsigned)(RPP * p.rsx * 2), r_row = (unsigned)((p.rsy - (long)p.Wo * p.rsx) * 2), r_smp = (unsigned)((p.rsn - (long)p.Ho * p.rsy) * 2);
-        const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(py + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((py + (long)e_nblk * p.ysn));
         const __amdgpu_buffer_rsrc_t rsrc_r =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? pres + (long)e_nblk * p.rsn : py + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+            hvn_buf((has_res ? pres + (long)e_nblk * p.rsn : py + (long)e_nblk * p.ysn));
         // all residual loads of the tile first, then the stores back to back: vmcnt retires loads and stores in order, so a
         // load issued after a store cannot be waited for without draining that store (see hvn_conv.hip)
         constexpr int NIT = (BM + RPP - 1) / RPP;
@@ -328,8 +311,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
             const int rr = erow0 + it * RPP;
             const bool ok = rr < BM && m0 + rr < M && cok;
             rall[it] = (u32x4){0u, 0u, 0u, 0u};
-            if (has_res) rall[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : EOOB, 0, 0);
-            yoffs[it] = ok ? y_off : EOOB;
+            if (has_res) rall[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : HVN_OOB, 0, 0);
+            yoffs[it] = ok ? y_off : HVN_OOB;
             ox += RPP;
             y_off += y_step;
             r_off += r_step;
@@ -364,10 +347,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
                         v.w = fmaxf(v.w + bias[h].w, relu_lo);
                     }
                     if (HR && has_res) {
-                        v.x += bf_lo(r4[2 * h]);
-                        v.y += bf_hi(r4[2 * h]);
-                        v.z += bf_lo(r4[2 * h + 1]);
-                        v.w += bf_hi(r4[2 * h + 1]);
+                        v.x += hvn_bf16_lo(r4[2 * h]);
+                        v.y += hvn_bf16_hi(r4[2 * h]);
+                        v.z += hvn_bf16_lo(r4[2 * h + 1]);
+                        v.w += hvn_bf16_hi(r4[2 * h + 1]);
                     }
                     if constexpr (HP) {
                         v.x = fmaxf(fmaf(v.x, qs[h].x, qb[h].x), post_lo);
@@ -375,8 +358,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
                         v.z = fmaxf(fmaf(v.z, qs[h].z, qb[h].z), post_lo);
                         v.w = fmaxf(fmaf(v.w, qs[h].w, qb[h].w), post_lo);
                     }
-                    o[2 * h] = pack_bf(v.x, v.y);
-                    o[2 * h + 1] = pack_bf(v.z, v.w);
+                    o[2 * h] = hvn_bf16_pack(v.x, v.y);
+                    o[2 * h + 1] = hvn_bf16_pack(v.z, v.w);
                 }
                 vout[it] = o;
             }
@@ -416,19 +399,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2, bool WIDE>
 static int launch_bf16w(const ConvArgs &a, hipStream_t stream)
 {
-    ConvArgs p = a;
-    p.m_tiles = (p.M + BM - 1) / BM;
-    p.n_tiles = (p.Cout + BN - 1) / BN;
     constexpr size_t stage_b = WIDE ? (size_t)(BM + BN) * LDW * 2 : (size_t)2 * (BM + BN) * LDH * 2, ep_b = (size_t)BM * (BN + 4) * 4;
     const size_t lds = stage_b > ep_b ? stage_b : ep_b;
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = hvn_conv_igemm_bf16<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, WIDE>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
-    const long groups = (p.m_tiles + 7) / 8;
-    const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hvn_conv_launch(hvn_conv_igemm_bf16<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, WIDE>, a, BM, BN, 256, lds, (int)lds, attr_done, stream);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2>
@@ -449,19 +423,10 @@ int hvn_launch_conv_bf16(const ConvArgs &a, int tile_n, hipStream_t stream)
 {
     if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0 || a.nbatch > 1) return -1;
     if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return -1;   // 16-byte epilogue accesses
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
-    const long howo = (long)a.Ho * a.Wo;
-    if (howo <= 0) return -1;
-    const long ahead = (howo + 126) / howo;      // samples a 128-row tile reaches beyond its first row's (hvn_launch_conv)
-    const long span = ahead * a.xsn + (long)(a.H + a.KH) * a.xsy + (long)(a.W + a.KW) * a.xsx;
-    if (span < 0 || span * 2 >= (1L << 31)) return -1;
-    // the epilogue's 32-bit offsets into y / res, from the sample of the tile's first row
-    if ((ahead * a.ysn + (long)(a.Ho + 1) * a.ysy + (long)a.Wo * a.ysx) * 2 >= (1L << 31)) return -1;
-    if (a.res && (ahead * a.rsn + (long)(a.Ho + 1) * a.rsy + (long)a.Wo * a.rsx) * 2 >= (1L << 31)) return -1;
+    if (!hvn_conv_reach_ok(a, 128, 2, 256, false, true)) return -1;      // (this launcher never checked the reach of x2)
     const long kt = (long)a.KH * a.KW * ((a.Cin + BKH - 1) / BKH) + (a.x2 ? a.Cin2 / BKH : 0);
     if ((long)(a.Cout + 128) * kt * BKH * 2 >= (1L << 31)) return -1;
-    const bool padded = a.pad_t > 0 || a.pad_l > 0 || (a.Ho - 1) * a.stride - a.pad_t + a.KH > a.H ||
-                        (a.Wo - 1) * a.stride - a.pad_l + a.KW > a.W;
+    const bool padded = hvn_conv_padded(a);
     if (padded && a.pre_s) return -1;
     if (a.x2) {
         if (padded || a.Cin2 % BKH || a.Cin % BKH || a.pre_s) return -1;

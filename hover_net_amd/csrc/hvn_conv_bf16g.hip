@@ -9,39 +9,12 @@
 // Every output element sums its products in hvn_conv_igemm_bf16's order (k ascending in groups of 16): BIT-IDENTICAL to it
 // (tests/test_gpu_bf16.py), so the engine picks per launch shape by time.  Launches with a prologue (pre-activation BN on the input) or
 // fewer than 128 output channels stay on hvn_conv_bf16.hip.  Reference geometry: /root/reference/models/hovernet/net_desc.py:76-99.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "hvn_conv_common.h"
 
 #define HK 64               // reduction elements (channels) per k-step
 #define HBN 128             // output channels per workgroup
 #define H_BSTAGE (HBN * 128)      // bytes of one weight stage: [128 rows][64 bf16]
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-
-// one LDS-DMA instruction (hvn_conv_x3g.hip:dma16; the builtin exists in the device pass only)
-__device__ __forceinline__ void hdma16(__amdgpu_buffer_rsrc_t rsrc, lds_ptr_t dst, unsigned voff, int soff)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, voff, soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ float hbf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float hbf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-__device__ __forceinline__ uint32_t hpack_bf(float a, float b)
-{
-    bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
 
 template <int BM, bool PADDED, bool HAS_X2>
 __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
@@ -83,7 +56,6 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;
-    constexpr unsigned OOB = 0x80000000u;
     unsigned a_voff[GA], a2_voff[GA];
     int a_iy[GA], a_ix[GA];
     bool a_upper[GA];                  // this lane's piece is the upper 32 channels of its 64-channel chunk
@@ -100,16 +72,16 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
         a_iy[jj] = ok ? (int)oy * p.stride - p.pad_t : -(1 << 28);
         a_ix[jj] = ok ? (int)ox * p.stride - p.pad_l : -(1 << 28);
-        a_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + piece * 8) * 2) : OOB;
-        a2_voff[jj] = OOB;
+        a_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + piece * 8) * 2) : HVN_OOB;
+        a2_voff[jj] = HVN_OOB;
         if constexpr (HAS_X2)
-            a2_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + piece * 8) * 2) : OOB;
+            a2_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + piece * 8) * 2) : HVN_OOB;
     }
     const uint16_t *xblk = px + (long)n_blk * p.xsn - padoff;
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)xblk, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void *)pw, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = hvn_buf(xblk);
+    const __amdgpu_buffer_rsrc_t rsrc_w = hvn_buf(pw);
     const uint16_t *x2blk = HAS_X2 ? (const uint16_t *)p.x2 + (long)n_blk * p.x2sn : px;
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc((void *)x2blk, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = hvn_buf(x2blk);
     const int kchunks = (p.Cin + HK - 1) / HK;
     const bool tail32 = (p.Cin % HK) != 0;                     // the last chunk of a tap holds 32 channels: its upper half is zeros
     const int KT1 = p.KH * p.KW * kchunks;
@@ -135,17 +107,17 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
             unsigned vo = a_voff[jj];
             if constexpr (PADDED) {
                 const bool ok = (unsigned)(a_iy[jj] + ld_r) < (unsigned)p.H && (unsigned)(a_ix[jj] + ld_s) < (unsigned)p.W;
-                vo = ok ? vo : OOB;
+                vo = ok ? vo : HVN_OOB;
             }
-            vo = (zero_upper && a_upper[jj]) ? OOB : vo;
+            vo = (zero_upper && a_upper[jj]) ? HVN_OOB : vo;
             lds_ptr_t dst = (lds_ptr_t)(hs + stage * A_STAGE + (wave * GA + jj) * 1024);
             if constexpr (HAS_X2) {
                 if (second)
-                    hdma16(rsrc_a2, dst, a2_voff[jj], a_soff);
+                    hvn_dma16(rsrc_a2, dst, a2_voff[jj], a_soff);
                 else
-                    hdma16(rsrc_a, dst, vo, a_soff);
+                    hvn_dma16(rsrc_a, dst, vo, a_soff);
             } else
-                hdma16(rsrc_a, dst, vo, a_soff);
+                hvn_dma16(rsrc_a, dst, vo, a_soff);
         }
         if (++ld_s == p.KW) {
             ld_s = 0;
@@ -161,7 +133,7 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
 #pragma unroll
         for (int jj = 0; jj < GB; ++jj) {
             lds_ptr_t dst = (lds_ptr_t)(hs + B_OFF + stage * H_BSTAGE + (wave * GB + jj) * 1024);
-            hdma16(rsrc_w, dst, w_voff[jj], w_soff);
+            hvn_dma16(rsrc_w, dst, w_voff[jj], w_soff);
         }
     };
 
@@ -270,7 +242,6 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
     const uint16_t *pres = (const uint16_t *)p.res;
     // addresses: 32-bit byte offsets from the sample of the tile's first row, stepped row to row, through buffer descriptors (hvn_conv_x3g.hip:
     // the 64-bit products per load / store cost several times the arithmetic they served); out-of-range offset = zeros loaded, store dropped
-    constexpr unsigned EOOB = 0x80000000u;
     unsigned oy, ox, y_off, r_off;
     const unsigned e_nblk = m0 / HoWo;
     {
@@ -284,9 +255,9 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
     }
     const unsigned y_step = (unsigned)(RPP * p.ysx * 2), y_row = (unsigned)((p.ysy - (long)p.Wo * p.ysx) * 2), y_smp = (unsigned)((p.ysn - (long)p.Ho * p.ysy) * 2);
     const unsigned r_step = (unsigned)(RPP * p.rsx * 2), r_row = (unsigned)((p.rsy - (long)p.Wo * p.rsx) * 2), r_smp = (unsigned)((p.rsn - (long)p.Ho * p.rsy) * 2);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(py + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((py + (long)e_nblk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? pres + (long)e_nblk * p.rsn : py + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? pres + (long)e_nblk * p.rsn : py + (long)e_nblk * p.ysn));
     // all residual loads of the tile first, every value finished in registers, then the stores back to back (one vmcnt for loads and stores)
     u32x4 rall[NIT];
     unsigned yoffs[NIT];
@@ -295,8 +266,8 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
         const int rr = erow0 + it * RPP;
         const bool ok = m0 + rr < M && cok;
         rall[it] = (u32x4){0u, 0u, 0u, 0u};
-        if (has_res) rall[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : EOOB, 0, 0);
-        yoffs[it] = ok ? y_off : EOOB;
+        if (has_res) rall[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : HVN_OOB, 0, 0);
+        yoffs[it] = ok ? y_off : HVN_OOB;
         ox += RPP;
         y_off += y_step;
         r_off += r_step;
@@ -333,10 +304,10 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
                     v.w = fmaxf(v.w + bias[h].w, relu_lo);
                 }
                 if (HR && has_res) {
-                    v.x += hbf_lo(r4[2 * h]);
-                    v.y += hbf_hi(r4[2 * h]);
-                    v.z += hbf_lo(r4[2 * h + 1]);
-                    v.w += hbf_hi(r4[2 * h + 1]);
+                    v.x += hvn_bf16_lo(r4[2 * h]);
+                    v.y += hvn_bf16_hi(r4[2 * h]);
+                    v.z += hvn_bf16_lo(r4[2 * h + 1]);
+                    v.w += hvn_bf16_hi(r4[2 * h + 1]);
                 }
                 if constexpr (HP) {
                     v.x = fmaxf(fmaf(v.x, qs[h].x, qb[h].x), post_lo);
@@ -344,8 +315,8 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
                     v.z = fmaxf(fmaf(v.z, qs[h].z, qb[h].z), post_lo);
                     v.w = fmaxf(fmaf(v.w, qs[h].w, qb[h].w), post_lo);
                 }
-                o[2 * h] = hpack_bf(v.x, v.y);
-                o[2 * h + 1] = hpack_bf(v.z, v.w);
+                o[2 * h] = hvn_bf16_pack(v.x, v.y);
+                o[2 * h + 1] = hvn_bf16_pack(v.z, v.w);
             }
             vout[it] = o;
         }
@@ -382,20 +353,11 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_bf16g(ConvArgs p)
 template <int BM, bool PADDED, bool HAS_X2>
 static int launch_bf16g(const ConvArgs &a, hipStream_t stream)
 {
-    ConvArgs p = a;
-    p.m_tiles = (p.M + BM - 1) / BM;
-    p.n_tiles = (p.Cout + HBN - 1) / HBN;
     constexpr size_t stage_b = (size_t)3 * BM * 128 + (size_t)(BM == 256 ? 3 : 2) * H_BSTAGE, ep_b = (size_t)BM * (HBN + 4) * 4;
     constexpr size_t lds = stage_b > ep_b ? stage_b : ep_b;
     static_assert(lds <= 160 * 1024 && (BM == 256 || lds <= 80 * 1024), "one workgroup per CU at 256 pixels, two at 128");
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = hvn_conv_igemm_bf16g<BM, PADDED, HAS_X2>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
-    const long groups = (p.m_tiles + 7) / 8;
-    const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BM * 2), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hvn_conv_launch(hvn_conv_igemm_bf16g<BM, PADDED, HAS_X2>, a, BM, HBN, BM * 2, lds, (int)lds, attr_done, stream);
 }
 
 // As hvn_launch_conv_bf16 (same operands, same packing, same bits): bm = 256 | 128 pixels x 128 channels per workgroup; no prologue,
@@ -405,20 +367,10 @@ int hvn_launch_conv_bf16g(const ConvArgs &a, int bm, hipStream_t stream)
     if ((bm != 256 && bm != 128) || a.Cout < 128 || a.pre_s || a.nbatch > 1) return -1;
     if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0) return -1;
     if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 512) return -1;
-    const long howo = (long)a.Ho * a.Wo;
-    if (howo <= 0) return -1;
-    const long ahead = (howo + bm - 2) / howo;       // samples a bm-row tile reaches beyond its first row's (hvn_launch_conv)
-    const long span = ahead * a.xsn + (long)(a.H + a.KH) * a.xsy + (long)(a.W + a.KW) * a.xsx;
-    if (span < 0 || span * 2 >= (1L << 31)) return -1;
-    // the epilogue's 32-bit offsets into y / res, from the sample of the tile's first row
-    if ((ahead * a.ysn + (long)(a.Ho + 1) * a.ysy + (long)a.Wo * a.ysx) * 2 >= (1L << 31)) return -1;
-    if (a.res && (ahead * a.rsn + (long)(a.Ho + 1) * a.rsy + (long)a.Wo * a.rsx) * 2 >= (1L << 31)) return -1;
-    if (a.x2 && (ahead * a.x2sn + (long)a.H * a.x2sy * a.stride2) * 2 >= (1L << 31)) return -1;
+    if (!hvn_conv_reach_ok(a, bm, 2, 512, true, true)) return -1;
     const long kt = (long)a.KH * a.KW * ((a.Cin + HK - 1) / HK) + (a.x2 ? a.Cin2 / HK : 0);
     if ((long)(a.Cout + 128) * kt * HK * 2 >= (1L << 31)) return -1;
-    const bool padded = a.pad_t > 0 || a.pad_l > 0 || (a.Ho - 1) * a.stride - a.pad_t + a.KH > a.H ||
-                        (a.Wo - 1) * a.stride - a.pad_l + a.KW > a.W;
+    const bool padded = hvn_conv_padded(a);
     if (a.x2) {
         if (padded || a.Cin2 % HK || a.Cin % HK) return -1;
         return bm == 256 ? launch_bf16g<256, false, true>(a, stream) : launch_bf16g<128, false, true>(a, stream);

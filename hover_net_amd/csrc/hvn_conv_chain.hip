@@ -29,24 +29,11 @@
 
 #include <vector>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "hvn_conv_common.h"
 
 #define CH_BM 128
 #define CH_BN 64
 #define CH_EP 68   // epilogue / GEMM2-A tile row pitch (floats)
-
-static __device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-static __device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-}
 
 // BM = pixels per workgroup: 128 (two workgroups per CU) or 64 (W1' staged one k-step at a time: 40 / 48 KB of LDS, <= 168 VGPRs, three
 // workgroups per CU -- for the seams that are bound by exposed load latency rather than by bytes; chosen per launch by the engine's
@@ -62,7 +49,6 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
     constexpr int WM2 = BM / WAVES_M2, WN2 = N2 / WAVES_N2;
     constexpr int TM2 = WM2 / 32, TN2 = WN2 / 32;
     constexpr bool B2ONE = BM == 64;                                       // W1' chunk: one k-step of 32 in LDS at a time
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(W1M * W1N == 4 && TN1 >= 1 && TM2 >= 1 && TN2 >= 1, "256 threads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *As = smem;                              // [2][BM][32]
@@ -91,14 +77,14 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + scol) * 4) : OOB;
-        a2_voff[j] = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : OOB;
+        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + scol) * 4) : HVN_OOB;
+        a2_voff[j] = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (long)n_blk * p.xsn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = hvn_buf((p.x + (long)n_blk * p.xsn));
     const __amdgpu_buffer_rsrc_t rsrc_x2 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w1, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w2, 0, 0x7fffffff, 0x00020000);
+        hvn_buf((HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x));
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = hvn_buf(p.w1);
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = hvn_buf(p.w2);
     const int KT1 = p.K1 / 32;
     const int KT = KT1 + (HAS_X2 ? p.K1b / 32 : 0);
     const int Ktot = KT * 32;
@@ -123,11 +109,11 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : OOB;
+        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((p.y + (long)n_blk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? p.res + (long)n_blk * p.rsn : p.x), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? p.res + (long)n_blk * p.rsn : p.x));
     const bool has_post = p.post_s != nullptr, has_pre = p.pre_s != nullptr;
     const float post_lo = has_post ? 0.f : -__builtin_inff();
     const float pre_lo = has_pre ? 0.f : -__builtin_inff();
@@ -142,13 +128,13 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
             if constexpr (HAS_X2)
-                st.ra[j] = buf_load(second ? rsrc_x2 : rsrc_x, second ? a2_voff[j] : a_voff[j], a_soff);
+                st.ra[j] = hvn_buf_load16(second ? rsrc_x2 : rsrc_x, second ? a2_voff[j] : a_voff[j], a_soff);
             else
-                st.ra[j] = buf_load(rsrc_x, a_voff[j], a_soff);
+                st.ra[j] = hvn_buf_load16(rsrc_x, a_voff[j], a_soff);
         }
         const int w_soff = (c * CH_BN * Ktot + kt * 32) * 4;
 #pragma unroll
-        for (int j = 0; j < PB; ++j) st.rb[j] = buf_load(rsrc_w1, w_voff[j], w_soff);
+        for (int j = 0; j < PB; ++j) st.rb[j] = hvn_buf_load16(rsrc_w1, w_voff[j], w_soff);
     };
     auto store1 = [&](int buf) {
         float *a = As + buf * BM * 32;
@@ -231,7 +217,7 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int j = 0; j < PB2; ++j) rb2[ks][j] = buf_load(rsrc_w2, w2_voff[j], ((2 * c + ks) * 32) * 4);
+            for (int j = 0; j < PB2; ++j) rb2[ks][j] = hvn_buf_load16(rsrc_w2, w2_voff[j], ((2 * c + ks) * 32) * 4);
         __syncthreads();
         CH_STAMP(2);
 #pragma unroll
@@ -257,7 +243,7 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
         f32x4 rres[NIT];
 #pragma unroll
         for (int it = 0; it < NIT; ++it)
-            rres[it] = has_res ? buf_load(rsrc_r, y_voff[it], c * (CH_BN * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            rres[it] = has_res ? hvn_buf_load16(rsrc_r, y_voff[it], c * (CH_BN * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
         if (c + 1 < NC) load1(c + 1, 0);
         mma1((KT - 1) & 1);
         CH_STAMP(3);
@@ -306,7 +292,7 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
             for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(vout[it]));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) buf_store(vout[it], rsrc_y, y_voff[it], c * (CH_BN * 4));
+            for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y, y_voff[it], c * (CH_BN * 4));
         }
         CH_STAMP(5);
         __syncthreads();
@@ -334,9 +320,9 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : OOB;
+        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y2 + (long)n_blk * p.y2sn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = hvn_buf((p.y2 + (long)n_blk * p.y2sn));
     const float relu_lo = p.relu2 ? 0.f : -__builtin_inff();
 #pragma unroll
     for (int h = 0; h < N2 / 64; ++h) {
@@ -367,7 +353,7 @@ __global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void hvn_conv_chain_f32(cons
             vout[it] = v;
         }
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) buf_store(vout[it], rsrc_y2, y2_voff[it], h * 256);
+        for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y2, y2_voff[it], h * 256);
         if (h + 1 < N2 / 64) __syncthreads();
     }
     if (p.dbg && tid == 0) {

@@ -20,26 +20,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "hvn_conv_common.h"
 
 #define CB_BM 64
 #define CB_CN 64                      // conv3 output channels per chunk
 #define CB_EP 68                      // fp32 tile row pitch (floats)
 #define CB_T 72                       // bf16 tile / W1' chunk row pitch (elements: 144 B)
-
-static __device__ __forceinline__ float cb_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-static __device__ __forceinline__ float cb_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-static __device__ __forceinline__ uint32_t cb_pack(float a, float b)
-{
-    bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
 
 // FL: which optional operands exist, known at compile time for the four seam kinds HoVer-Net has (bit 0 residual, bit 1 the next unit's
 // pre-activation, bit 2 block-closing BN-ReLU) -- the epilogue is then straight-line code; -1: decided at run time (any other chain).
@@ -51,7 +37,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
     constexpr int PA = BM * (KA / 8) / 256;            // 16-byte pieces per thread of the input tile / a W1 chunk: 2 | 4
     constexpr int PW2 = N2 * 8 / 256;                  // ... of a W1' chunk: 2 | 4
     constexpr int TN2 = N2 / 64;                       // 32-column MFMA tiles per wave in GEMM2 (waves 2 x 2: 32 rows x N2 / 2 columns)
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(KA == 64 || KA == 128, "K1 + K1b");
     static_assert(N2 == 64 || N2 == 128, "cout2");
     extern __shared__ __attribute__((aligned(16))) unsigned char cbs[];
@@ -79,9 +64,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
     const bool has_post = FL < 0 ? p.post_s != nullptr : (FL & 4) != 0;
 
     // ---- the input tile: piece t = tid + 256 j of [64 rows][KA / 8 pieces]; the first K1 / 8 pieces of a row come from x, the rest from x2 ----
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void *)(px + (long)n_blk * p.xsn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = hvn_buf((px + (long)n_blk * p.xsn));
     const __amdgpu_buffer_rsrc_t rsrc_x2 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(HAS_X2 ? px2 + (long)n_blk * p.x2sn : px), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((HAS_X2 ? px2 + (long)n_blk * p.x2sn : px));
     {
         u32x4 ra[PA];
 #pragma unroll
@@ -100,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
                 vo = (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + (pc * 8 - p.K1)) * 2);
             else
                 vo = (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + pc * 8) * 2);
-            vo = ok ? vo : OOB;
+            vo = ok ? vo : HVN_OOB;
             if constexpr (HAS_X2)
                 ra[j] = second ? __builtin_amdgcn_raw_buffer_load_b128(rsrc_x2, vo, 0, 0) : __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, 0, 0);
             else
@@ -115,8 +100,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
     }
 
     // ---- per-chunk operands, a chunk ahead in registers --------------------------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)pw1, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)pw2, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = hvn_buf(pw1);
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = hvn_buf(pw2);
     unsigned w1_voff[PA], w2_voff[PW2];
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
@@ -163,13 +148,13 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 2) : OOB;
-        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 2) : OOB;
+        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 2) : HVN_OOB;
+        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 2) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(py + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((py + (long)n_blk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? pres + (long)n_blk * p.rsn : px), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void *)(py2 + (long)n_blk * p.y2sn), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? pres + (long)n_blk * p.rsn : px));
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = hvn_buf((py2 + (long)n_blk * p.y2sn));
     // (the first conv of a chain has no ReLU / bias of its own: validated by the caller)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -251,10 +236,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
                     // finite or infinite value that is not -0, and an MFMA accumulator that started at +0 is never -0 (x + y is -0 only if
                     // both are), nor is a sum with one operand that is not -0.  (Not preserved: a NaN, which max(., -inf) would turn into -inf.)
                     if (has_res) {
-                        v.x += cb_lo(r4[2 * h]);
-                        v.y += cb_hi(r4[2 * h]);
-                        v.z += cb_lo(r4[2 * h + 1]);
-                        v.w += cb_hi(r4[2 * h + 1]);
+                        v.x += hvn_bf16_lo(r4[2 * h]);
+                        v.y += hvn_bf16_hi(r4[2 * h]);
+                        v.z += hvn_bf16_lo(r4[2 * h + 1]);
+                        v.w += hvn_bf16_hi(r4[2 * h + 1]);
                     }
                     if (has_post) {
                         v.x = fmaxf(fmaf(v.x, qs[h].x, qb[h].x), 0.f);
@@ -262,15 +247,15 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
                         v.z = fmaxf(fmaf(v.z, qs[h].z, qb[h].z), 0.f);
                         v.w = fmaxf(fmaf(v.w, qs[h].w, qb[h].w), 0.f);
                     }
-                    o[2 * h] = cb_pack(v.x, v.y);
-                    o[2 * h + 1] = cb_pack(v.z, v.w);
+                    o[2 * h] = hvn_bf16_pack(v.x, v.y);
+                    o[2 * h + 1] = hvn_bf16_pack(v.z, v.w);
                     if (has_pre) {      // the unchained conv1 stages relu(bf16(y) * s + b), rounded to bf16 (hvn_conv_igemm_bf16: store_lds)
                         const float s_[4] = {ps[h].x, ps[h].y, ps[h].z, ps[h].w}, b_[4] = {pb[h].x, pb[h].y, pb[h].z, pb[h].w};
 #pragma unroll
                         for (int e = 0; e < 2; ++e) {
-                            const float lo = fmaxf(fmaf(cb_lo(o[2 * h + e]), s_[2 * e], b_[2 * e]), 0.f);
-                            const float hi = fmaxf(fmaf(cb_hi(o[2 * h + e]), s_[2 * e + 1], b_[2 * e + 1]), 0.f);
-                            a4[2 * h + e] = cb_pack(lo, hi);
+                            const float lo = fmaxf(fmaf(hvn_bf16_lo(o[2 * h + e]), s_[2 * e], b_[2 * e]), 0.f);
+                            const float hi = fmaxf(fmaf(hvn_bf16_hi(o[2 * h + e]), s_[2 * e + 1], b_[2 * e + 1]), 0.f);
+                            a4[2 * h + e] = hvn_bf16_pack(lo, hi);
                         }
                     } else {
                         a4[2 * h] = o[2 * h];
@@ -339,8 +324,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_bf16(const ChainArgs p)
                 v.z = fmaxf(v.z + bias[h].z, relu_lo);
                 v.w = fmaxf(v.w + bias[h].w, relu_lo);
                 // (hvn_conv_igemm_bf16 goes on with fma(v, 1, 0) and max(., -inf): identities here, see epilogue 1)
-                out[it][2 * h] = cb_pack(v.x, v.y);
-                out[it][2 * h + 1] = cb_pack(v.z, v.w);
+                out[it][2 * h] = hvn_bf16_pack(v.x, v.y);
+                out[it][2 * h + 1] = hvn_bf16_pack(v.z, v.w);
             }
         }
 #pragma unroll

@@ -22,42 +22,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "hvn_conv_common.h"
 
 #define CX_BM 128
 #define CX_BN 64
 #define CX_EP 68                      // epilogue / GEMM2-A tile row pitch (floats)
 #define CX_ASTAGE (CX_BM * 128)       // bytes: [128 rows][32 floats]
 #define CX_BSTAGE (3 * CX_BN * 64)    // bytes: [3 planes][64 rows][64 B]
-
-static __device__ __forceinline__ f32x4 cx_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-static __device__ __forceinline__ void cx_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-}
-
-// hvn_conv_x3.hip:split3 over the 8 k-values a lane feeds one MFMA with
-static __device__ __forceinline__ void cx_split(const f32x4 a, const f32x4 b, bf16x8 &h, bf16x8 &m, bf16x8 &l)
-{
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 hh = (__bf16)x[e];
-        const float r = x[e] - (float)hh;
-        const __bf16 mm = (__bf16)r;
-        h[e] = hh;
-        m[e] = mm;
-        l[e] = (__bf16)(r - (float)mm);
-    }
-}
 
 template <int N2, bool HAS_X2, int NTERMS>
 __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
@@ -71,7 +42,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
     constexpr int WM2 = BM / WAVES_M2, WN2 = N2 / WAVES_N2;
     constexpr int TM2 = WM2 / 32, TN2 = WN2 / 32;     // 1 x 2 | 2 x 2
     constexpr int B2PLANE = N2 * 64;                  // bytes of one plane of a W1' k-step
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(NTERMS == 9 || NTERMS == 6, "nine exact partial products, or the six that carry > 2^-24 of the product");
     extern __shared__ __attribute__((aligned(16))) unsigned char cs[];
     unsigned char *As = cs;                                   // [2][128][128 B]
@@ -100,14 +70,14 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + scol) * 4) : OOB;
-        a2_voff[j] = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : OOB;
+        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + scol) * 4) : HVN_OOB;
+        a2_voff[j] = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (long)n_blk * p.xsn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = hvn_buf((p.x + (long)n_blk * p.xsn));
     const __amdgpu_buffer_rsrc_t rsrc_x2 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w1, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w2, 0, 0x7fffffff, 0x00020000);
+        hvn_buf((HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x));
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = hvn_buf(p.w1);
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = hvn_buf(p.w2);
     const int KT1 = p.K1 / 32;
     const int KT = KT1 + (HAS_X2 ? p.K1b / 32 : 0);
     const int NC = p.C / CX_BN;
@@ -143,11 +113,11 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : OOB;
+        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((p.y + (long)n_blk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? p.res + (long)n_blk * p.rsn : p.x), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? p.res + (long)n_blk * p.rsn : p.x));
     const bool has_post = p.post_s != nullptr, has_pre = p.pre_s != nullptr;
     const float post_lo = has_post ? 0.f : -__builtin_inff();
     const float pre_lo = has_pre ? 0.f : -__builtin_inff();
@@ -163,9 +133,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
             if constexpr (HAS_X2)
-                st.ra[j] = cx_load(second ? rsrc_x2 : rsrc_x, second ? a2_voff[j] : a_voff[j], a_soff);
+                st.ra[j] = hvn_buf_load16(second ? rsrc_x2 : rsrc_x, second ? a2_voff[j] : a_voff[j], a_soff);
             else
-                st.ra[j] = cx_load(rsrc_x, a_voff[j], a_soff);
+                st.ra[j] = hvn_buf_load16(rsrc_x, a_voff[j], a_soff);
         }
         const int w_soff = (c * CX_BN * KT + kt) * 192;
 #pragma unroll
@@ -213,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
                     fb[j][pl] = __builtin_bit_cast(bf16x8, *(const u32x4 *)(b + pl * (CX_BN * 64) + j * 32 * 64 + (((2 * q + lh) ^ bkey) << 4)));
-            cx_split(v0, v1, fa[0], fa[1], fa[2]);
+            hvn_split3x8(v0, v1, fa[0], fa[1], fa[2]);
 #pragma unroll
             for (int s = 4; s >= 0; --s) {
                 if (NTERMS == 6 && s > 2) continue;
@@ -233,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
             for (int i = 0; i < TM2; ++i) {
                 const f32x4 v0 = *(const f32x4 *)(a + i * 32 * CX_EP + q * 16);
                 const f32x4 v1 = *(const f32x4 *)(a + i * 32 * CX_EP + q * 16 + 4);
-                cx_split(v0, v1, fa[i][0], fa[i][1], fa[i][2]);
+                hvn_split3x8(v0, v1, fa[i][0], fa[i][1], fa[i][2]);
             }
 #pragma unroll
             for (int j = 0; j < TN2; ++j)
@@ -288,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
         f32x4 rres[NIT];
 #pragma unroll
         for (int it = 0; it < NIT; ++it)
-            rres[it] = has_res ? cx_load(rsrc_r, y_voff[it], c * (CX_BN * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            rres[it] = has_res ? hvn_buf_load16(rsrc_r, y_voff[it], c * (CX_BN * 4)) : (f32x4){0.f, 0.f, 0.f, 0.f};
         if (c + 1 < NC) load1(c + 1, 0);
         mma1((KT - 1) & 1);
         __syncthreads();               // every wave is done reading the staging buffers: the tile may overwrite them
@@ -339,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
                 for (int j = 0; j < PB2; ++j) rb2[1][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w2, w2_voff[j], (2 * c + 1) * 192, 0);
             }
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) cx_store(vout[it], rsrc_y, y_voff[it], c * (CX_BN * 4));
+            for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y, y_voff[it], c * (CX_BN * 4));
         }
         __syncthreads();
         mma2(0);
@@ -363,9 +333,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : OOB;
+        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y2 + (long)n_blk * p.y2sn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = hvn_buf((p.y2 + (long)n_blk * p.y2sn));
     const float relu_lo = p.relu2 ? 0.f : -__builtin_inff();
 #pragma unroll
     for (int h = 0; h < N2 / 64; ++h) {
@@ -396,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3(const ChainArgs p)
             vout[it] = v;
         }
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) cx_store(vout[it], rsrc_y2, y2_voff[it], h * 256);
+        for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y2, y2_voff[it], h * 256);
         if (h + 1 < N2 / 64) __syncthreads();
     }
 }

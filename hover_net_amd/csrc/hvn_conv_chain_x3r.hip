@@ -24,47 +24,10 @@
 
 #include <type_traits>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "hvn_conv_common.h"
 
 #define CR_BM 128
 #define CR_CB 32                      // conv3 output channels per chunk
-
-typedef __attribute__((address_space(3))) void *cr_lds_ptr_t;
-
-// one LDS-DMA instruction (hvn_conv_x3g.hip:dma16; the builtin exists in the device pass only)
-static __device__ __forceinline__ void cr_dma16(__amdgpu_buffer_rsrc_t rsrc, cr_lds_ptr_t dst, unsigned voff, int soff)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, voff, soff, 0, 0);
-#endif
-}
-static __device__ __forceinline__ f32x4 cr_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-static __device__ __forceinline__ void cr_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-}
-// hvn_conv_x3.hip:split3 over the 8 k-values a lane feeds one MFMA with
-static __device__ __forceinline__ void cr_split(const f32x4 a, const f32x4 b, bf16x8 &h, bf16x8 &m, bf16x8 &l)
-{
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 hh = (__bf16)x[e];
-        const float r = x[e] - (float)hh;
-        const __bf16 mm = (__bf16)r;
-        h[e] = hh;
-        m[e] = mm;
-        l[e] = (__bf16)(r - (float)mm);
-    }
-}
 
 // wait until at most VM of this wave's vector-memory operations are outstanding (they complete in issue order) and its LDS operations
 // have returned, then the workgroup barrier
@@ -99,7 +62,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
     constexpr int TM2 = WM2 / 32, TN2 = WN2 / 32;     // 1 x 2 | 2 x 2
     constexpr int NIT = BM / 32;                      // epilogue passes: 32 rows x 8 pieces of 16 B per pass
     constexpr bool RES = !HAS_X2;                     // a fused shortcut takes the residual's place (validated by the launcher)
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(NTERMS == 9 || NTERMS == 6, "nine exact partial products, or the six that carry > 2^-24 of the product");
     static_assert(NIT == 4, "the counted waits below assume 4 y stores and 4 residual loads per thread and chunk");
     extern __shared__ __attribute__((aligned(16))) unsigned char cs[];
@@ -117,12 +79,12 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
     const int KT2 = p.C / 32;                         // k-steps of the second GEMM (row length of W1')
     const bool has_res = p.res != nullptr;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (long)n_blk * p.xsn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = hvn_buf((p.x + (long)n_blk * p.xsn));
     const __amdgpu_buffer_rsrc_t rsrc_x2 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w1, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)p.w2, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x));
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = hvn_buf(p.w1);
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = hvn_buf(p.w2);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((p.y + (long)n_blk * p.ysn));
     // Optional operands are loaded UNCONDITIONALLY through descriptors of zero records when absent (every load out of range: zeros, no
     // memory traffic): the number of vector-memory operations per chunk is then the same on every path, which the counted waits
     // below -- mine and the compiler's -- depend on.
@@ -159,10 +121,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
         const int s1 = __builtin_amdgcn_readfirstlane(c * (CB * KT * 192));
         const int s2 = __builtin_amdgcn_readfirstlane(c * 192);
 #pragma unroll
-        for (int jj = 0; jj < D1; ++jj) cr_dma16(rsrc_w1, (cr_lds_ptr_t)(cs + W1_OFF + (wave * D1 + jj) * 1024), w1_voff[jj], s1);
+        for (int jj = 0; jj < D1; ++jj) hvn_dma16(rsrc_w1, (lds_ptr_t)(cs + W1_OFF + (wave * D1 + jj) * 1024), w1_voff[jj], s1);
 #pragma unroll
         for (int jj = 0; jj < D2; ++jj)
-            cr_dma16(rsrc_w2, (cr_lds_ptr_t)(cs + W2_OFF + (c & 1) * W2_BYTES + (wave * D2 + jj) * 1024), w2_voff[jj], s2);
+            hvn_dma16(rsrc_w2, (lds_ptr_t)(cs + W2_OFF + (c & 1) * W2_BYTES + (wave * D2 + jj) * 1024), w2_voff[jj], s2);
         // nothing that is issued later in program order may be moved ahead of the DMAs: the counted waits below count what is YOUNGER
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -180,14 +142,14 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        const unsigned ax = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + lh * 8) * 4) : OOB;
-        const unsigned ax2 = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + lh * 8) * 4) : OOB;
+        const unsigned ax = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)oy * p.xsy + (long)ox * p.xsx + lh * 8) * 4) : HVN_OOB;
+        const unsigned ax2 = (ok && HAS_X2) ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + lh * 8) * 4) : HVN_OOB;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const bool second = HAS_X2 && s >= 4;
             const int soff = (second ? s - 4 : s) * 64;
-            raw[s][0] = cr_load(second ? rsrc_x2 : rsrc_x, second ? ax2 : ax, soff);
-            raw[s][1] = cr_load(second ? rsrc_x2 : rsrc_x, (second ? ax2 : ax) + 16, soff);
+            raw[s][0] = hvn_buf_load16(second ? rsrc_x2 : rsrc_x, second ? ax2 : ax, soff);
+            raw[s][1] = hvn_buf_load16(second ? rsrc_x2 : rsrc_x, (second ? ax2 : ax) + 16, soff);
         }
     }
 
@@ -205,17 +167,17 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : OOB;
+        y_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + ecol) * 4) : HVN_OOB;
     }
     const float post_lo = has_post ? 0.f : -__builtin_inff();
     const float pre_lo = has_pre ? 0.f : -__builtin_inff();
 
     f32x4 rres[NIT];
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) rres[it] = RES ? cr_load(rsrc_r, y_voff[it], 0) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < NIT; ++it) rres[it] = RES ? hvn_buf_load16(rsrc_r, y_voff[it], 0) : (f32x4){0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_sched_barrier(0);         // (the first residual chunk is requested before the wait for the input rows)
 #pragma unroll
-    for (int s = 0; s < NS; ++s) cr_split(raw[s][0], raw[s][1], fa[s][0], fa[s][1], fa[s][2]);
+    for (int s = 0; s < NS; ++s) hvn_split3x8(raw[s][0], raw[s][1], fa[s][0], fa[s][1], fa[s][2]);
 
     f32x16 acc2[TM2][TN2];
 #pragma unroll
@@ -249,8 +211,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
         // vector-memory operations complete in issue order, so waiting for a load issued after the DMAs would wait for the DMAs
         const f32x4 ones = {1.f, 1.f, 1.f, 1.f};
         const int csoff = __builtin_amdgcn_readfirstlane(c * (CB * 4));
-        f32x4 qs = cr_load(rsrc_qs, ecol * 4, csoff), qb = cr_load(rsrc_qb, ecol * 4, csoff);
-        f32x4 ps = cr_load(rsrc_ps, ecol * 4, csoff), pb = cr_load(rsrc_pb, ecol * 4, csoff);
+        f32x4 qs = hvn_buf_load16(rsrc_qs, ecol * 4, csoff), qb = hvn_buf_load16(rsrc_qb, ecol * 4, csoff);
+        f32x4 ps = hvn_buf_load16(rsrc_ps, ecol * 4, csoff), pb = hvn_buf_load16(rsrc_pb, ecol * 4, csoff);
         __builtin_amdgcn_sched_barrier(0);     // (issued here; their first use is behind the next barrier -- hipcc otherwise waits for them, and with
                                                //  them for the residual loads ahead of them, in the middle of GEMM 1)
         // ---- GEMM 1: this wave's 32 pixels x the chunk's 32 channels; A from registers, W1 planes from LDS --------------------------
@@ -300,10 +262,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
                 *(f32x4 *)e = a;
             }
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) cr_store(vout[it], rsrc_y, y_voff[it], csoff);
+            for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y, y_voff[it], csoff);
             if constexpr (!LAST && RES) {
 #pragma unroll
-                for (int it = 0; it < NIT; ++it) rres[it] = cr_load(rsrc_r, y_voff[it], csoff + CB * 4);
+                for (int it = 0; it < NIT; ++it) rres[it] = hvn_buf_load16(rsrc_r, y_voff[it], csoff + CB * 4);
             }
         }
         CR_BARRIER_LDS();              // the activated tile is visible
@@ -318,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
                 for (int i = 0; i < TM2; ++i) {
                     const f32x4 v0 = *(const f32x4 *)(a + i * 32 * CB + (((4 * q + 2 * lh) ^ akey) << 2));
                     const f32x4 v1 = *(const f32x4 *)(a + i * 32 * CB + (((4 * q + 2 * lh + 1) ^ akey) << 2));
-                    cr_split(v0, v1, fa2[i][0], fa2[i][1], fa2[i][2]);
+                    hvn_split3x8(v0, v1, fa2[i][0], fa2[i][1], fa2[i][2]);
                 }
 #pragma unroll
                 for (int j = 0; j < TN2; ++j)
@@ -357,9 +319,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
         const unsigned n = mm / HoWo;
         const unsigned rem = mm - n * HoWo;
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : OOB;
+        y2_voff[it] = ok ? (unsigned)(((long)(n - n_blk) * p.y2sn + (long)oy * p.y2sy + (long)ox * p.y2sx + ecol) * 4) : HVN_OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y2 + (long)n_blk * p.y2sn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = hvn_buf((p.y2 + (long)n_blk * p.y2sn));
     const float relu_lo = p.relu2 ? 0.f : -__builtin_inff();
 #pragma unroll
     for (int h = 0; h < N2 / 32; ++h) {
@@ -389,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_chain_x3r(const ChainArgs p)
             vout[it] = v;
         }
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) cr_store(vout[it], rsrc_y2, y2_voff[it], h * 128);
+        for (int it = 0; it < NIT; ++it) hvn_buf_store16(vout[it], rsrc_y2, y2_voff[it], h * 128);
         if (h + 1 < N2 / 32) CR_BARRIER_LDS();
     }
 }

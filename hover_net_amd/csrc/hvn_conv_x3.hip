@@ -22,28 +22,11 @@
 
 #include <type_traits>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "hvn_conv_common.h"
 
 #define XK 32        // reduction elements per k-step
 #define XPITCH 104   // LDS row pitch in bf16 elements (3 planes x 32 + 8)
 
-// x = h + m + l exactly (RNE conversions; x - h and x - h - m are exact in fp32) for 2^-110 <= |x| < 3.38e38 and for 0: below, the low
-// planes underflow bf16's denormal grid (absolute error < 2^-133); within 0.3 % of FLT_MAX h rounds to infinity -- a value no fp32
-// accumulation of this network survives either (tests/test_x3_arithmetic.py pins both limits)
-__device__ __forceinline__ void split3(float x, __bf16 &h, __bf16 &m, __bf16 &l)
-{
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
 __device__ __forceinline__ uint32_t pack2(__bf16 a, __bf16 b)
 {
     bf16x2 v = {a, b};
@@ -94,7 +77,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;
-    constexpr unsigned OOB = 0x80000000u;
     unsigned a_voff[PA];
     int a_iy[PA], a_ix[PA];
 #pragma unroll
@@ -107,14 +89,14 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
         a_iy[j] = ok ? (int)oy * p.stride - p.pad_t : -(1 << 28);
         a_ix[j] = ok ? (int)ox * p.stride - p.pad_l : -(1 << 28);
-        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + scol) * 4) : OOB;
+        a_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + scol) * 4) : HVN_OOB;
     }
     const float *xblk = p.x + (long)n_blk * p.xsn - padoff;
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)xblk, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void *)pw, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = hvn_buf(xblk);
+    const __amdgpu_buffer_rsrc_t rsrc_w = hvn_buf(pw);
     unsigned a2_voff[PA];
     const float *x2blk = HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x;
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc((void *)x2blk, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = hvn_buf(x2blk);
     if constexpr (HAS_X2) {
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
             const unsigned n = mm / HoWo;
             const unsigned rem = mm - n * HoWo;
             const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
-            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : OOB;
+            a2_voff[j] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + scol) * 4) : HVN_OOB;
         }
     }
     const int kchunks = p.Cin / XK;
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
             unsigned vo = a_voff[j];
             if constexpr (PADDED) {
                 const bool ok = (unsigned)(a_iy[j] + ld_r) < (unsigned)p.H && (unsigned)(a_ix[j] + ld_s) < (unsigned)p.W;
-                vo = ok ? vo : OOB;
+                vo = ok ? vo : HVN_OOB;
             }
             if constexpr (HAS_X2) {
                 vo = second ? a2_voff[j] : vo;
@@ -192,10 +174,10 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
                 }
             }
             __bf16 h[4], m[4], l[4];
-            split3(v.x, h[0], m[0], l[0]);
-            split3(v.y, h[1], m[1], l[1]);
-            split3(v.z, h[2], m[2], l[2]);
-            split3(v.w, h[3], m[3], l[3]);
+            hvn_split3(v.x, h[0], m[0], l[0]);
+            hvn_split3(v.y, h[1], m[1], l[1]);
+            hvn_split3(v.z, h[2], m[2], l[2]);
+            hvn_split3(v.w, h[3], m[3], l[3]);
             uint16_t *dst = As + (srow + 32 * j) * XPITCH + scol;
             *(u32x2 *)(dst) = (u32x2){pack2(h[0], h[1]), pack2(h[2], h[3])};
             *(u32x2 *)(dst + 32) = (u32x2){pack2(m[0], m[1]), pack2(m[2], m[3])};
@@ -287,7 +269,6 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
     const float post_lo = has_post ? 0.f : -__builtin_inff();
     // addresses: 32-bit byte offsets from the sample of the tile's first row, stepped row to row, through buffer descriptors (hvn_conv_x3g.hip:
     // the 64-bit products per load / store were ~600 VALU per thread and tile); out-of-range offset = zeros loaded, store dropped
-    constexpr unsigned EOOB = 0x80000000u;
     unsigned e_oy, e_ox, y_off, r_off;
     const unsigned e_nblk = m0 / HoWo;
     {
@@ -301,9 +282,9 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
     }
     const unsigned y_step = (unsigned)(RPP * p.ysx * 4), y_row = (unsigned)((p.ysy - (long)p.Wo * p.ysx) * 4), y_smp = (unsigned)((p.ysn - (long)p.Ho * p.ysy) * 4);
     const unsigned r_step = (unsigned)(RPP * p.rsx * 4), r_row = (unsigned)((p.rsy - (long)p.Wo * p.rsx) * 4), r_smp = (unsigned)((p.rsn - (long)p.Ho * p.rsy) * 4);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((p.y + (long)e_nblk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? p.res + (long)e_nblk * p.rsn : p.y + (long)e_nblk * p.ysn), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? p.res + (long)e_nblk * p.rsn : p.y + (long)e_nblk * p.ysn));
     // all residual loads of the tile, then every value finished in registers, then the stores back to back (one vmcnt for loads
     // and stores on gfx9: hvn_conv.hip has the measurements)
     f32x4 rall[NIT], vout[NIT];
@@ -313,8 +294,8 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_x3(ConvArgs p)
         const unsigned m = m0 + erow0 + it * RPP;
         const bool ok = m < M && cok;
         rall[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (has_res) rall[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : EOOB, 0, 0));
-        yoffs[it] = ok ? y_off : EOOB;
+        if (has_res) rall[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : HVN_OOB, 0, 0));
+        yoffs[it] = ok ? y_off : HVN_OOB;
         e_ox += RPP;
         y_off += y_step;
         r_off += r_step;
@@ -394,10 +375,10 @@ __global__ __launch_bounds__(256) void hvn_split_x3(const float *src, uint16_t *
     if (g >= granules) return;
     const f32x4 v = *(const f32x4 *)(src + g * 32 + q * 4);
     __bf16 h[4], m[4], l[4];
-    split3(v.x, h[0], m[0], l[0]);
-    split3(v.y, h[1], m[1], l[1]);
-    split3(v.z, h[2], m[2], l[2]);
-    split3(v.w, h[3], m[3], l[3]);
+    hvn_split3(v.x, h[0], m[0], l[0]);
+    hvn_split3(v.y, h[1], m[1], l[1]);
+    hvn_split3(v.z, h[2], m[2], l[2]);
+    hvn_split3(v.w, h[3], m[3], l[3]);
     uint16_t *d = dst + g * 96 + q * 4;
     *(u32x2 *)(d) = (u32x2){pack2(h[0], h[1]), pack2(h[2], h[3])};
     *(u32x2 *)(d + 32) = (u32x2){pack2(m[0], m[1]), pack2(m[2], m[3])};
@@ -416,19 +397,10 @@ int hvn_launch_split_x3(const float *src, uint16_t *dst, long granules, hipStrea
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2, int NTERMS>
 static int launch_x3(const ConvArgs &a, hipStream_t stream)
 {
-    ConvArgs p = a;
-    p.m_tiles = (p.M + BM - 1) / BM;
-    p.n_tiles = (p.Cout + BN - 1) / BN;
     constexpr size_t stage_b = (size_t)(BM + BN) * XPITCH * 2, ep_b = (size_t)BM * (BN + 4) * 4;
     const size_t lds = stage_b > ep_b ? stage_b : ep_b;
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = hvn_conv_igemm_x3<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, NTERMS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
-    const long groups = (p.m_tiles + 7) / 8;
-    const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, p.nbatch > 1 ? p.nbatch : 1), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hvn_conv_launch(hvn_conv_igemm_x3<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, NTERMS>, a, BM, BN, 256, lds, (int)lds, attr_done, stream);
 }
 
 template <int NTERMS>
@@ -455,21 +427,10 @@ static int dispatch_x3(const ConvArgs &a, int tile_n, bool padded, hipStream_t s
 int hvn_launch_conv_x3(const ConvArgs &a, int tile_n, int terms, hipStream_t stream)
 {
     if (a.Cin % XK != 0 || a.Cin <= 0 || a.Cout % 4 != 0 || a.groups > 1) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
-    // a 128-row tile reaches (HoWo + 126) / HoWo samples ahead of its first row's sample (hvn_launch_conv): 32-bit offsets below 2^31
-    const long howo = (long)a.Ho * a.Wo;
-    if (howo <= 0) return -1;
-    const long ahead = (howo + 126) / howo;
-    const long span = ahead * a.xsn + (long)(a.H + a.KH) * a.xsy + (long)(a.W + a.KW) * a.xsx;
-    if (span < 0 || span * 4 >= (1L << 31)) return -1;
-    if (a.x2 && (ahead * a.x2sn + (long)a.H * a.x2sy * a.stride2) * 4 >= (1L << 31)) return -1;
-    // the epilogue's 32-bit offsets into y / res, from the sample of the tile's first row
-    if ((ahead * a.ysn + (long)(a.Ho + 1) * a.ysy + (long)a.Wo * a.ysx) * 4 >= (1L << 31)) return -1;
-    if (a.res && (ahead * a.rsn + (long)(a.Ho + 1) * a.rsy + (long)a.Wo * a.rsx) * 4 >= (1L << 31)) return -1;
+    if (!hvn_conv_reach_ok(a, 128, 4, 256, true, true)) return -1;
     const long kt = (long)a.KH * a.KW * (a.Cin / XK) + (a.x2 ? a.Cin2 / XK : 0);
     if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return -1;
-    const bool padded = a.pad_t > 0 || a.pad_l > 0 || (a.Ho - 1) * a.stride - a.pad_t + a.KH > a.H ||
-                        (a.Wo - 1) * a.stride - a.pad_l + a.KW > a.W;
+    const bool padded = hvn_conv_padded(a);
     if (padded && a.pre_s) return -1;
     if (a.x2 && (padded || a.Cin2 % XK || a.pre_s)) return -1;
     return terms == 6 ? dispatch_x3<6>(a, tile_n, padded, stream) : dispatch_x3<9>(a, tile_n, padded, stream);

@@ -26,44 +26,11 @@
 
 #include <type_traits>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "hvn_conv_common.h"
 
 #define GK 32               // reduction elements per k-step
 #define GBN 128             // output channels per workgroup
 #define G_BSTAGE (3 * GBN * 64)   // bytes of one B stage: [plane 3][row 128][64 B]
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-
-// One LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global offsets (voff + the wave-uniform soff; beyond num_records: zeros)
-// to the 1 KiB at the wave-uniform LDS address `dst`, lane-linear.  (The builtin exists in the device pass only; hipcc's host pass
-// silently drops a kernel whose body names it, and with it the kernel's launch stub.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, lds_ptr_t dst, unsigned voff, int soff)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, voff, soff, 0, 0);
-#endif
-}
-
-// hvn_conv_x3.hip:split3 for 8 lanes' worth of k: x = h + m + l exactly (RNE conversions; both differences exact in fp32)
-__device__ __forceinline__ void split3x8(const f32x4 a, const f32x4 b, bf16x8 &h, bf16x8 &m, bf16x8 &l)
-{
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 hh = (__bf16)x[e];
-        const float r = x[e] - (float)hh;
-        const __bf16 mm = (__bf16)r;
-        h[e] = hh;
-        m[e] = mm;
-        l[e] = (__bf16)(r - (float)mm);
-    }
-}
 
 template <int BM, bool PADDED, bool HAS_PRE, bool HAS_X2, int NTERMS>
 __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
@@ -125,7 +92,6 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;
-    constexpr unsigned OOB = 0x80000000u;
     unsigned a_voff[GA], a2_voff[GA];
     int a_iy[GA], a_ix[GA];
 #pragma unroll
@@ -140,16 +106,16 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
         const unsigned oy = rem / (unsigned)p.Wo, ox = rem - oy * (unsigned)p.Wo;
         a_iy[jj] = ok ? (int)oy * p.stride - p.pad_t : -(1 << 28);
         a_ix[jj] = ok ? (int)ox * p.stride - p.pad_l : -(1 << 28);
-        a_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + piece * 4) * 4) : OOB;
-        a2_voff[jj] = OOB;
+        a_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.xsn + (long)(oy * p.stride) * p.xsy + (long)(ox * p.stride) * p.xsx + piece * 4) * 4) : HVN_OOB;
+        a2_voff[jj] = HVN_OOB;
         if constexpr (HAS_X2)
-            a2_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + piece * 4) * 4) : OOB;
+            a2_voff[jj] = ok ? (unsigned)(((long)(n - n_blk) * p.x2sn + (long)(oy * p.stride2) * p.x2sy + (long)(ox * p.stride2) * p.x2sx + piece * 4) * 4) : HVN_OOB;
     }
     const float *xblk = p.x + (long)n_blk * p.xsn - padoff;
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)xblk, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void *)pw, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = hvn_buf(xblk);
+    const __amdgpu_buffer_rsrc_t rsrc_w = hvn_buf(pw);
     const float *x2blk = HAS_X2 ? p.x2 + (long)n_blk * p.x2sn : p.x;
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc((void *)x2blk, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = hvn_buf(x2blk);
     const int kchunks = p.Cin / GK;
     const int KT1 = p.KH * p.KW * kchunks;
     const int KT = KT1 + (HAS_X2 ? p.Cin2 / GK : 0);
@@ -178,8 +144,8 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
     // its barrier, where everything outstanding is waited for anyway -- the compiler then knows them complete and adds no wait of its own
     // behind the DMAs it cannot count on (they are conditional)
     f32x4 pvs[2][2], pvb[2][2];
-    const __amdgpu_buffer_rsrc_t rsrc_ps = __builtin_amdgcn_make_buffer_rsrc((void *)(PRE_GLB ? p.pre_s : p.x), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_pb = __builtin_amdgcn_make_buffer_rsrc((void *)(PRE_GLB ? p.pre_b : p.x), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_ps = hvn_buf(PRE_GLB ? p.pre_s : p.x);
+    const __amdgpu_buffer_rsrc_t rsrc_pb = hvn_buf(PRE_GLB ? p.pre_b : p.x);
     auto load_pre = [&](int slab) {
         if constexpr (PRE_GLB) {
             const int so = __builtin_amdgcn_readfirstlane(slab * (GK * 4));
@@ -225,16 +191,16 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
             unsigned vo = a_voff[jj];
             if constexpr (PADDED) {
                 const bool ok = (unsigned)(a_iy[jj] + ld_r) < (unsigned)p.H && (unsigned)(a_ix[jj] + ld_s) < (unsigned)p.W;
-                vo = ok ? vo : OOB;
+                vo = ok ? vo : HVN_OOB;
             }
             lds_ptr_t dst = (lds_ptr_t)(gs + stage * A_STAGE + (wave * GA + jj) * 1024);
             if constexpr (HAS_X2) {
                 if (second)
-                    dma16(rsrc_a2, dst, a2_voff[jj], a_soff);
+                    hvn_dma16(rsrc_a2, dst, a2_voff[jj], a_soff);
                 else
-                    dma16(rsrc_a, dst, vo, a_soff);
+                    hvn_dma16(rsrc_a, dst, vo, a_soff);
             } else
-                dma16(rsrc_a, dst, vo, a_soff);
+                hvn_dma16(rsrc_a, dst, vo, a_soff);
         }
         if (++ld_s == p.KW) {
             ld_s = 0;
@@ -250,7 +216,7 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
 #pragma unroll
         for (int jj = 0; jj < GB; ++jj) {
             lds_ptr_t dst = (lds_ptr_t)(gs + B_OFF + stage * G_BSTAGE + (wave * GB + jj) * 1024);
-            dma16(rsrc_w, dst, w_voff[jj], w_soff);
+            hvn_dma16(rsrc_w, dst, w_voff[jj], w_soff);
         }
     };
 
@@ -308,7 +274,7 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
             }
         }
 #pragma unroll
-        for (int i = 0; i < TI; ++i) split3x8(v0[i], v1[i], f.a[i][0], f.a[i][1], f.a[i][2]);
+        for (int i = 0; i < TI; ++i) hvn_split3x8(v0[i], v1[i], f.a[i][0], f.a[i][1], f.a[i][2]);
     };
     // smallest partial products first; (plane of a, plane of b) with 0 = high, 2 = low -- hvn_conv_igemm_x3's order, per accumulator.
     // The 4 NTERMS MFMAs of a slice are numbered in that order; mma(f, lo, hi) issues numbers lo .. hi - 1.
@@ -442,9 +408,9 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
     }
     const unsigned y_step = (unsigned)(RPP * p.ysx * 4), y_row = (unsigned)((p.ysy - (long)p.Wo * p.ysx) * 4), y_smp = (unsigned)((p.ysn - (long)p.Ho * p.ysy) * 4);
     const unsigned r_step = (unsigned)(RPP * p.rsx * 4), r_row = (unsigned)((p.rsy - (long)p.Wo * p.rsx) * 4), r_smp = (unsigned)((p.rsn - (long)p.Ho * p.rsy) * 4);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = hvn_buf((p.y + (long)n_blk * p.ysn));
     const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(has_res ? p.res + (long)n_blk * p.rsn : p.y + (long)n_blk * p.ysn), 0, 0x7fffffff, 0x00020000);
+        hvn_buf((has_res ? p.res + (long)n_blk * p.rsn : p.y + (long)n_blk * p.ysn));
     // two halves of NIT / 2 rows each (register pressure): all residual loads, every value finished, then the stores back to back.
     // Round 6: the epilogue exists in the 8 forms {bias + ReLU | neither} x {residual | none} x {block BN-ReLU | none} and a launch takes the one
     // that holds only ITS operations.  hvn_conv_igemm_x3 always computes max(acc + bias, lo) + res, max(fma(., qs, qb), lo') with bias = res = qb
@@ -463,8 +429,8 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
                 const unsigned m = m0 + erow0 + (half * HN + it) * RPP;
                 const bool ok = m < M && cok;
                 rall[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (HR && has_res) rall[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : OOB, 0, 0));
-                yoffs[it] = ok ? y_off : OOB;
+                if (HR && has_res) rall[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, ok ? r_off : HVN_OOB, 0, 0));
+                yoffs[it] = ok ? y_off : HVN_OOB;
                 // next row of this thread: RPP pixels on; the wraps add what a row / a sample is longer than its pixels
                 e_ox += RPP;
                 y_off += y_step;
@@ -532,21 +498,12 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
 template <int BM, bool PADDED, bool HAS_PRE, bool HAS_X2, int NTERMS>
 static int launch_x3g(const ConvArgs &a, hipStream_t stream)
 {
-    ConvArgs p = a;
-    p.m_tiles = (p.M + BM - 1) / BM;
-    p.n_tiles = (p.Cout + GBN - 1) / GBN;
     constexpr int NA = BM == 256 ? 3 : 2;
     const size_t stage_b = (size_t)NA * BM * 128 + 2 * G_BSTAGE + (HAS_PRE && BM == 256 ? (size_t)2 * a.Cin * 4 : 0), ep_b = (size_t)BM * (GBN + 4) * 4;
     const size_t lds = stage_b > ep_b ? stage_b : ep_b;
     if (lds > 160 * 1024) return -1;
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = hvn_conv_igemm_x3g<BM, PADDED, HAS_PRE, HAS_X2, NTERMS>;
-    if (hvn_max_lds_once((const void *)kern, 160 * 1024, attr_done)) return -2;
-    const long groups = (p.m_tiles + 7) / 8;
-    const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, p.nbatch > 1 ? p.nbatch : 1), dim3(BM * 2), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hvn_conv_launch(hvn_conv_igemm_x3g<BM, PADDED, HAS_PRE, HAS_X2, NTERMS>, a, BM, GBN, BM * 2, lds, 160 * 1024, attr_done, stream);
 }
 
 template <int BM, int NTERMS>
@@ -571,21 +528,10 @@ int hvn_launch_conv_x3g(const ConvArgs &a, int bm, int terms, hipStream_t stream
 {
     if (!hvn_conv_x3g_supported(a, bm)) return -1;
     if (a.Cin % GK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 512) return -1;
-    // a bm-row tile reaches (HoWo + bm - 2) / HoWo samples ahead of its first row's sample: 32-bit offsets below 2^31 (hvn_launch_conv)
-    const long howo = (long)a.Ho * a.Wo;
-    if (howo <= 0) return -1;
-    const long ahead = (howo + bm - 2) / howo;
-    const long span = ahead * a.xsn + (long)(a.H + a.KH) * a.xsy + (long)(a.W + a.KW) * a.xsx;
-    if (span < 0 || span * 4 >= (1L << 31)) return -1;
-    if (a.x2 && (ahead * a.x2sn + (long)a.H * a.x2sy * a.stride2) * 4 >= (1L << 31)) return -1;
-    // the epilogue's 32-bit offsets into y / res, from the sample of the tile's first row
-    if ((ahead * a.ysn + (long)(a.Ho + 1) * a.ysy + (long)a.Wo * a.ysx) * 4 >= (1L << 31)) return -1;
-    if (a.res && (ahead * a.rsn + (long)(a.Ho + 1) * a.rsy + (long)a.Wo * a.rsx) * 4 >= (1L << 31)) return -1;
+    if (!hvn_conv_reach_ok(a, bm, 4, 512, true, true)) return -1;
     const long kt = (long)a.KH * a.KW * (a.Cin / GK) + (a.x2 ? a.Cin2 / GK : 0);
     if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return -1;
-    const bool padded = a.pad_t > 0 || a.pad_l > 0 || (a.Ho - 1) * a.stride - a.pad_t + a.KH > a.H ||
-                        (a.Wo - 1) * a.stride - a.pad_l + a.KW > a.W;
+    const bool padded = hvn_conv_padded(a);
     if (padded && a.pre_s) return -1;
     if (a.x2 && (padded || a.Cin2 % GK || a.pre_s)) return -1;
     if (a.pre_s && (((uintptr_t)a.pre_s | (uintptr_t)a.pre_b) & 15)) return -1;

@@ -11,18 +11,9 @@
 #include <stdlib.h>
 #include <stdint.h>
 
-#include "hvn_kernels.h"
+#include "hvn_conv_common.h"
 
 // ---------------------------------------------------------------------------------------
-typedef __bf16 hvn_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ inline float hvn_bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ inline float hvn_bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-__device__ inline uint32_t hvn_pack_bf(float a, float b)
-{
-    hvn_bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
-
 #define C0_T 16              // output tile edge
 #define C0_P (C0_T + 6)      // patch edge
 template <typename T>
@@ -63,8 +54,8 @@ __global__ __launch_bounds__(256) void hvn_conv0(const Conv0Args p)
             uint16_t *y = (uint16_t *)p.y + yoff;
 #pragma unroll
             for (int c = 0; c < 64; c += 4) {
-                hvn_bf16x2 h0 = {(__bf16)fmaxf(acc[c], lo), (__bf16)fmaxf(acc[c + 1], lo)};
-                hvn_bf16x2 h1 = {(__bf16)fmaxf(acc[c + 2], lo), (__bf16)fmaxf(acc[c + 3], lo)};
+                bf16x2 h0 = {(__bf16)fmaxf(acc[c], lo), (__bf16)fmaxf(acc[c + 1], lo)};
+                bf16x2 h1 = {(__bf16)fmaxf(acc[c + 2], lo), (__bf16)fmaxf(acc[c + 3], lo)};
                 *(uint2 *)(y + c) = make_uint2(__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, h1));
             }
         } else {
@@ -84,7 +75,6 @@ __global__ __launch_bounds__(256) void hvn_conv0(const Conv0Args p)
 template <typename T>
 __global__ __launch_bounds__(256) void hvn_conv0_mfma(const Conv0Args p)
 {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     __shared__ float patch[C0_P + 1][C0_PITCH];   // + one zero row: k = 147 (the padding of the odd K) reads row py + 7
     __shared__ float wl[148][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -203,10 +193,10 @@ __global__ __launch_bounds__(256) void hvn_upadd_bf16(const UpAddArgs p, long to
         const uint4 a = *(const uint4 *)(lo + (long)n * p.lsn + (long)(y >> 1) * p.lsy + (long)(x >> 1) * p.lsx + c8 * 8);
         const uint4 b = *(const uint4 *)(skip + (long)n * p.ssn + (long)y * p.ssy + (long)x * p.ssx + c8 * 8);
         uint4 o;
-        o.x = hvn_pack_bf(hvn_bf_lo(a.x) + hvn_bf_lo(b.x), hvn_bf_hi(a.x) + hvn_bf_hi(b.x));
-        o.y = hvn_pack_bf(hvn_bf_lo(a.y) + hvn_bf_lo(b.y), hvn_bf_hi(a.y) + hvn_bf_hi(b.y));
-        o.z = hvn_pack_bf(hvn_bf_lo(a.z) + hvn_bf_lo(b.z), hvn_bf_hi(a.z) + hvn_bf_hi(b.z));
-        o.w = hvn_pack_bf(hvn_bf_lo(a.w) + hvn_bf_lo(b.w), hvn_bf_hi(a.w) + hvn_bf_hi(b.w));
+        o.x = hvn_bf16_pack(hvn_bf16_lo(a.x) + hvn_bf16_lo(b.x), hvn_bf16_hi(a.x) + hvn_bf16_hi(b.x));
+        o.y = hvn_bf16_pack(hvn_bf16_lo(a.y) + hvn_bf16_lo(b.y), hvn_bf16_hi(a.y) + hvn_bf16_hi(b.y));
+        o.z = hvn_bf16_pack(hvn_bf16_lo(a.z) + hvn_bf16_lo(b.z), hvn_bf16_hi(a.z) + hvn_bf16_hi(b.z));
+        o.w = hvn_bf16_pack(hvn_bf16_lo(a.w) + hvn_bf16_lo(b.w), hvn_bf16_hi(a.w) + hvn_bf16_hi(b.w));
         *(uint4 *)(yo + (long)n * p.ysn + (long)y * p.ysy + (long)x * p.ysx + c8 * 8) = o;
     }
 }
@@ -245,8 +235,8 @@ __global__ __launch_bounds__(256) void hvn_head(const HeadArgs p, long total)
 #pragma unroll
         for (int c = 0; c < 64; c += 8) {
             const uint4 q = *(const uint4 *)(src + c);
-            v[c] = hvn_bf_lo(q.x); v[c + 1] = hvn_bf_hi(q.x); v[c + 2] = hvn_bf_lo(q.y); v[c + 3] = hvn_bf_hi(q.y);
-            v[c + 4] = hvn_bf_lo(q.z); v[c + 5] = hvn_bf_hi(q.z); v[c + 6] = hvn_bf_lo(q.w); v[c + 7] = hvn_bf_hi(q.w);
+            v[c] = hvn_bf16_lo(q.x); v[c + 1] = hvn_bf16_hi(q.x); v[c + 2] = hvn_bf16_lo(q.y); v[c + 3] = hvn_bf16_hi(q.y);
+            v[c + 4] = hvn_bf16_lo(q.z); v[c + 5] = hvn_bf16_hi(q.z); v[c + 6] = hvn_bf16_lo(q.w); v[c + 7] = hvn_bf16_hi(q.w);
         }
     } else {
         const float *src = p.x + xoff;

@@ -17,10 +17,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "hvn_kernels.h"
+#include "hvn_conv_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 static inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -2; }
@@ -1046,13 +1044,12 @@ __global__ __launch_bounds__(256) void hvn_conv0_wgrad(const Conv0WgradArgs p, i
 #define W0M_PITCH (W0_P * 3 + 2)
 __global__ __launch_bounds__(256) void hvn_conv0_wgrad_mfma(const Conv0WgradArgs p, int tiles_x, int tiles_y, long tiles_total)
 {
-    typedef float f32x16v __attribute__((ext_vector_type(16)));
     extern __shared__ __attribute__((aligned(16))) float w0m_lds[];
     float *patch = w0m_lds;                              // [W0_P][W0M_PITCH]
     float *dzs = w0m_lds + W0_P * W0M_PITCH;             // [128][64]; later the [64][160] reduction buffer
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
-    f32x16v acc[2][5];
+    f32x16 acc[2][5];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -15,12 +15,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "hvn_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "hvn_conv_common.h"
 
 #define WX_PLANE (128 * 64)          // bytes of one plane of one operand: [128 rows][32 pixels x 2 B]
 #define WX_OPER (3 * WX_PLANE)

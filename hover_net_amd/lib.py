@@ -10,9 +10,6 @@ LIB_PATH = os.path.join(_HERE, "libhvn_hip.so")
 # kernel A/B runs on one box without rebuilding there.  Not used by the product path (unset = libhvn_hip.so).
 VARIANTS = {
     "pad": ("-DHVN_SWZ=0",),                        # padded LDS rows (round-1 layout) instead of the XOR swizzle
-    "lin": ("-DHVN_EPI_LINEAR=1",),                 # prepared, NOT yet measured: branch-free epilogue addressing for row-contiguous views
-    "nt": ("-DHVN_NT=1",),                          # prepared, NOT yet measured: non-temporal hints on the epilogue's residual loads / stores
-    "lin_nt": ("-DHVN_EPI_LINEAR=1", "-DHVN_NT=1"),
     "noxcd": ("-DHVN_WINO_XCD=0", "-DHVN_CONV_XCD_CONTIG=0"),   # A/B: round-robin tile order in the Winograd input transform and the multi-tap convolutions
     "fullepi": ("-DHVN_X3G_FULL_EPI=1",),           # A/B (round 6): hvn_conv_igemm_x3g with the one full epilogue of rounds 1-5 instead of the 8 operand-set forms
     "wn1": ("-DHVN_X3G_WN=1",),                      # A/B (round 6, neutral): hvn_conv_igemm_x3g with 32 x 128 wave tiles (every wave splits its A fragment once)
@@ -89,7 +86,7 @@ def source_id():
     import hashlib
 
     h = hashlib.sha256()
-    for f in sorted(SOURCES) + ["hvn_kernels.h"]:
+    for f in sorted(SOURCES) + ["hvn_conv_common.h", "hvn_kernels.h"]:
         h.update(f.encode())
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read())
@@ -124,7 +121,7 @@ def _hipcc_version():
 
 
 def _compile(out, extra, verbose):
-    """One object per source, compiled in parallel and cached by the hash of what it is built from (the source, both headers, the
+    """One object per source, compiled in parallel and cached by the hash of what it is built from (the source, the headers, the
     flags) under csrc/.obj/, then linked: editing one kernel file recompiles that file only (~30 s instead of ~150 s for all).
     The .so still carries the id of ALL sources (`hvn_build_id`, stamped into hvn_api.hip's object)."""
     import hashlib
@@ -133,7 +130,7 @@ def _compile(out, extra, verbose):
     sid = source_id() + ("" if not extra else "+" + "".join(extra))
     objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
-    hdr = open(os.path.join(CSRC, "hvn_kernels.h"), "rb").read() + open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read()
+    hdr = open(os.path.join(CSRC, "hvn_kernels.h"), "rb").read() + open(os.path.join(CSRC, "hvn_conv_common.h"), "rb").read() + open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read()
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra)
     jobs, objs = [], []
     for src in SOURCES:

@@ -1,8 +1,6 @@
 #!/usr/bin/env python
 """Times ONE conv launch shape through the real library (MiniPlan + Engine, like tests/gpu_util.py) -- the tool behind the
-per-layer ablations of profiles/r02_experiments.md.  HVN_CONV_ABLATE selects the ablated instantiation of the 128x128 kernel:
-5 = baseline (same instantiation, nothing removed), 1 = no global loads in the k-loop, 2 = no LDS staging either, 3 = MFMAs only,
-4 = full k-loop but an epilogue without global traffic.
+per-layer tables of profiles/r02_experiments.md.
 usage: python tools/conv_bench.py N H CIN COUT K [res] [pre] [x2=CIN2]"""
 import os
 import sys
@@ -47,5 +45,4 @@ e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
 fl = 2.0 * n * h * h * cout * cin * k * k
-print("abl=%s N=%d %dx%d %d->%d k%d %s tile_n=%d: %.3f ms  %.1f TFLOP/s" % (os.environ.get("HVN_CONV_ABLATE", "-"), n, h, h, cin, cout, k, " ".join(flags),
-                                                                         eng.ops[0].tile_n, ms, fl / ms / 1e9))
+print("N=%d %dx%d %d->%d k%d %s tile_n=%d: %.3f ms  %.1f TFLOP/s" % (n, h, h, cin, cout, k, " ".join(flags), eng.ops[0].tile_n, ms, fl / ms / 1e9))
