@@ -14,6 +14,8 @@ import torch
 
 from . import lib as L
 from . import plan as PL
+from . import tune as T
+from .tune import X3G_128, X3G_256, X3R  # noqa: F401  (the form codes, importable from here as before)
 
 
 def _view_struct(v, base_ptr, sn, itemsize=4):
@@ -27,36 +29,7 @@ def _view_struct(v, base_ptr, sn, itemsize=4):
     return s
 
 
-WG_SLOTS = 512            # resident 128x128 conv workgroups: 2 per CU (VGPRs) x 256 CUs
-WG_SLOTS_NARROW = 768     # resident 128x64 workgroups: 3 per CU (48 KB of LDS each with the swizzled layout, <= 168 VGPRs)
-NARROW_TILE_COST = 0.45   # time of a round of 128x64 tiles relative to a round of 128x128 tiles (3 x 1/2 vs 2 x 1 tiles of MFMA work per CU)
-
-
-def pick_tile_n(op, batch):
-    """Column tile (128 or 64) of a CONV launch by its wave quantisation -- the MODEL behind `HVN_TILE_SELECT=model` and the
-    starting point of the measured selection (`Engine.autotune_tiles`, the default): a launch of W workgroups runs in
-    ceil(W / slots) rounds, so 1092 workgroups of 128x128 tiles (2.13 rounds -> 3) lose 29 % to the last round.  The packed
-    weights are the same for both widths (cout is padded to 128) and so is every output bit (same k order per element).  Only
-    plain launches with cout >= 128 are re-tiled; HVN_TILE_SELECT=0 keeps the static choice of plan._tile_n.
-    Experiment knobs: HVN_FORCE_TILE_N=64|128, HVN_WG_SLOTS_64, HVN_NARROW_COST."""
-    import math
-    import os
-
-    if op.tile_n != 128 or os.environ.get("HVN_TILE_SELECT", "auto") == "0":
-        return op.tile_n
-    force = os.environ.get("HVN_FORCE_TILE_N")
-    if force:
-        return int(force)
-    slots64 = int(os.environ.get("HVN_WG_SLOTS_64", WG_SLOTS_NARROW))
-    cost64 = float(os.environ.get("HVN_NARROW_COST", NARROW_TILE_COST))
-    m_tiles = math.ceil(batch * op.y.h * op.y.w / 128.0)
-    nb = int(op.extra.get("nbatch", 1))
-    wide = math.ceil(m_tiles * math.ceil(op.cout / 128.0) * nb / WG_SLOTS)
-    narrow = math.ceil(m_tiles * math.ceil(op.cout / 64.0) * nb / slots64) * cost64
-    return 64 if narrow < wide else 128
-
-
-_STREAM_POOL, _STREAM_CHOICE = {}, {}   # device -> [streams]; (device, sub-batches, lanes, dtype) -> (pool offset, {offset: ms})
+_STREAM_POOL = {}       # device -> [streams]
 
 
 def lane_stream_pool(device, count):
@@ -65,32 +38,6 @@ def lane_stream_pool(device, count):
     while len(have) < count:
         have.append(torch.cuda.Stream(device))
     return have
-
-
-_TILE_CACHE = {}        # device -> {launch shape key: (choice, ms of the default, ms of the choice, {candidate: ms})}
-X3G_256, X3G_128 = 128 + 0x300, 128 + 0x200     # hvn_op.tile_n of the LDS-DMA forms of the bf16x3 convolution (include/hvn.h)
-X3R = 128 + 0x400                               # hvn_op.tile_n of the bf16x3 CHAIN with a register-resident input tile (include/hvn.h)
-
-
-def x3g_forms_for(op):
-    """The LDS-DMA workgroup shapes (csrc/hvn_conv_x3g.hip) a bf16x3 CONV launch may run on besides hvn_conv_x3.hip's, as tile_n codes:
-    they need >= 128 output channels and -- the 256-row form with a prologue -- its two per-channel vectors next to the operand rings
-    in the CU's 160 KB of LDS.  Same packing, same bits (tests/test_gpu_x3.py): which one runs is a timing decision (`Engine.autotune_tiles`).  HVN_X3G=0
-    keeps hvn_conv_x3.hip everywhere; HVN_X3G=896 | 640 offers one form only."""
-    import os
-
-    want = os.environ.get("HVN_X3G", "1")
-    if want == "0" or op.cout < 128 or int(op.extra.get("groups", 1)) != 1:
-        return ()
-    cin = op.x.c
-    forms = []
-    for code, bm, na in ((X3G_256, 256, 3), (X3G_128, 128, 2)):
-        if want not in ("1", str(code)):
-            continue
-        if op.pre is not None and bm == 256 and na * bm * 128 + 2 * 3 * 128 * 64 + 2 * cin * 4 > 160 * 1024:
-            continue                                   # (the 128-row form reads the prologue's vectors from global memory)
-        forms.append(code)
-    return tuple(forms)
 
 
 def to_bf16_bits(a):
@@ -185,26 +132,18 @@ class Engine:
         self.ops = (L.hvn_op * len(plan.ops))()
         self._bind()
         self._sub_ops = {}
-        # measured launch-shape choices (column tile / kernel form), keyed by everything the timing depends on: shared by every engine of
-        # the process on this device -- the forms give the same bits, so WHICH engine timed a shape first is invisible in the results
-        self.tile_choice = _TILE_CACHE.setdefault(str(self.device), {})
-        tile_file = os.environ.get("HVN_TILE_FILE")          # a list of per-op column tiles written by another engine of the same plan
+        tile_file = T.knob("HVN_TILE_FILE")                  # a list of per-op tile_n codes written by another engine of the same plan
         if tile_file and dtype == "fp32":                   # (bench.py hands its measured choices to the PMC child runs)
             import json
             tiles = json.load(open(tile_file))
             if len(tiles) != len(self.ops):
                 raise ValueError("HVN_TILE_FILE holds %d entries for a plan of %d ops" % (len(tiles), len(self.ops)))
-            for o, op, tn in zip(self.ops, plan.ops, tiles):
-                if op.kind == PL.OP_CONV and ((op.tile_n == 128 and (tn in (64, 128) or (op.extra.get("x3") and tn in x3g_forms_for(op)))) or
-                                              (op.tile_n == 64 and tn in (64, 320) and not op.extra.get("x3"))):
+            for o, tn in zip(self.ops, tiles):
+                if tn in T.candidates(o):
                     o.tile_n = tn
-                if op.kind == PL.OP_CHAIN and (tn in (64, 128) or (tn == X3R and op.extra.get("x3"))):
-                    o.tile_n = tn
-        elif dtype == "fp32" and os.environ.get("HVN_TILE_SELECT", "auto") == "auto" and not os.environ.get("HVN_FORCE_TILE_N"):
+        elif T.tile_select() == "auto" and not (dtype == "fp32" and T.knob("HVN_FORCE_TILE_N")):
             self.autotune_tiles()
-        elif dtype == "bf16" and os.environ.get("HVN_TILE_SELECT", "auto") == "auto" and os.environ.get("HVN_BF16G", "1") != "0":
-            self.autotune_bf16_forms()
-        if os.environ.get("HVN_TILE_SELECT", "auto") == "auto" and os.environ.get("HVN_STREAM_SELECT", "1") != "0":
+        if T.tile_select() == "auto" and T.knob("HVN_STREAM_SELECT") != "0":
             self.autotune_streams()
 
     # ---------------------------------------------------------------------------------
@@ -286,7 +225,7 @@ class Engine:
             o.kind, o.kh, o.kw, o.stride = op.kind, op.kh, op.kw, op.stride
             o.pad_t, o.pad_l, o.relu, o.cout, o.tile_n, o.x_dtype = op.pad_t, op.pad_l, op.relu, op.cout, op.tile_n, 0
             if op.kind == PL.OP_CONV and self.dtype == "fp32":
-                o.tile_n = pick_tile_n(op, self.max_batch)
+                o.tile_n = T.pick_tile_n(op, self.max_batch)
             o.groups = int(op.extra.get("groups", 1))
             o._rsv = int(op.extra.get("stride2", 1))
             o.nbatch = int(op.extra.get("nbatch", 1))
@@ -335,14 +274,14 @@ class Engine:
             o.post_scale, o.post_shift = self._pptr(i, "post_s"), self._pptr(i, "post_b")
 
     # ---------------------------------------------------------------------------------
-    def autotune_streams(self, reps=3):
+    def autotune_streams(self):
         """Which streams of the process-wide pool this engine's launch schedule runs on (round 6).  HIP multiplexes a process's streams
         onto a few hardware queues in creation order, and two lanes of one step that share a queue run one after the other: with k idle
         streams created before the engine's own, the cfg-2 network step measured 41.5 / 42.4 / 41.7 / 43.4 / 41.5 ms for k = 0 .. 4 against
         42.4 on one stream (`profiles/r06_stream_map_probe.txt`) -- the schedule's gain depended on what the process had done before (in
         bench.py: a fit).  So the streams come from one pool per process and device (`lane_stream_pool`), and the engine times its whole
-        schedule on the pool's four rotations once per (device, schedule) and process; outputs do not depend on the answer
-        (tests/test_gpu_chain.py: every schedule gives the same bits)."""
+        schedule on the pool's four rotations once per (device, schedule) and process and takes the fastest (margin 1: no form is
+        preferred); outputs do not depend on the answer (tests/test_gpu_chain.py: every schedule gives the same bits)."""
         split = self.n_split if (self.n_split > 1 and self.max_batch >= 2 * self.n_split) else 1
         need = (split - 1) + split * self.n_lane_streams
         if need == 0 or self.plan.ops[0].kind != PL.OP_CONV0 or not getattr(self.plan, "geo", None):
@@ -350,186 +289,41 @@ class Engine:
         g = int(self.plan.geo.get("inp", 0))
         if g <= 0:
             return
-        key = (str(self.device), split, self.n_lane_streams, self.dtype)
-        if key not in _STREAM_CHOICE:
-            import os
-            reps = max(1, int(os.environ.get("HVN_TUNE_REPS", reps)))
-            imgs = torch.zeros((self.max_batch, g, g, 3), dtype=torch.uint8, device=self.device)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ms = {}
-            for off in range(4):
-                self._stream_off, self._streams = off, None
-                best = float("inf")
-                for r in range(reps + 1):
-                    e0.record()
-                    self.run(imgs)
-                    self.run(imgs)
-                    e1.record()
-                    e1.synchronize()
-                    if r:
-                        best = min(best, e0.elapsed_time(e1) / 2)
-                ms[off] = best
-            _STREAM_CHOICE[key] = (min(ms, key=ms.get), ms)
-        self._stream_off, self._streams = _STREAM_CHOICE[key][0], None
+        imgs = torch.zeros((self.max_batch, g, g, 3), dtype=torch.uint8, device=self.device)
 
-    def autotune_tiles(self, reps=3, margin=0.985):
-        """Measured column-tile selection (the default; `HVN_TILE_SELECT=model` keeps `pick_tile_n`'s rounds model): every
-        re-tileable CONV launch is timed once per distinct shape with 128x128 and with 128x64 tiles at this engine's batch
-        (min of `reps` HIP-event timings after a warm-up launch, on whatever the arena holds -- MFMA time does not depend
-        on the values) and gets the narrow tile when that is faster by more than 1.5 %.  Both widths produce the same bits
-        (identical k order per output element), so the choice is invisible in the results.  ~1 s per engine."""
-        import os
+        def measure(off):
+            self._stream_off, self._streams = off, None
+            return T.time_launch(lambda: self.run(imgs), runs=2)
 
+        key = (str(self.device), "streams", split, self.n_lane_streams, self.dtype)
+        self._stream_off, self._streams = T.choose(T.CACHE, key, (0, 1, 2, 3), measure, margin=1.0)[0], None
+
+    def autotune_tiles(self):
+        """Measured launch-form selection (the default; `HVN_TILE_SELECT=model` keeps `tune.pick_tile_n`'s rounds model): every CONV /
+        CHAIN launch that has more than one form (`tune.candidates`) is timed once per distinct shape on each of them at the batch it is
+        launched with, on whatever the arena holds -- MFMA time does not depend on the values -- and bound to `tune.pick`'s answer.
+        All forms of a launch produce the same bits, so the choice is invisible in the results.  ~1 s per engine."""
         lib = L.lib()
-        reps = max(1, int(os.environ.get("HVN_TUNE_REPS", reps)))       # (tests/conftest.py: 1 -- every candidate gives the same bits)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         osz = ctypes.sizeof(L.hvn_op)
         base = ctypes.addressof(self.ops)
-
         # the encoder launches of a split engine run on sub-batches: their shapes are timed at the sub-batch size
         lanes = getattr(self.plan, "lanes", None)
         enc_end = lanes[0][2] if (lanes and lanes[0][0] == "main" and len(lanes) > 1) else 0
         split = self.n_split if (self.n_split > 1 and self.max_batch >= 2 * self.n_split) else 1
-        sub_n = -(-self.max_batch // split)
-        if os.environ.get("HVN_TUNE_SUB", "1") == "0":      # A/B knob: time every launch at the full batch (round 3's selection)
-            sub_n = self.max_batch
-
-        def time_op(i):
-            best = float("inf")
+        sub_n = -(-self.max_batch // split) if T.knob("HVN_TUNE_SUB") != "0" else self.max_batch
+        for i, o in enumerate(self.ops):
+            cands = T.candidates(o)
+            if not cands:
+                continue
             nb = sub_n if (i < enc_end or self.split_decoder) else self.max_batch
-            for r in range(reps + 1):
-                e0.record()
-                L.check(lib.hvn_run_op(base + i * osz, nb, ctypes.c_void_p(stream)), "hvn_run_op (autotune)")
-                e1.record()
-                e1.synchronize()
-                if r:
-                    best = min(best, e0.elapsed_time(e1))
-            return best
+            family = "infer-bf16" if o.act_dtype == 1 else "infer-conv" if o.kind == PL.OP_CONV else "infer-chain-x3" if o.act_dtype else "infer-chain"
 
-        for i, op in enumerate(self.plan.ops):
-            if op.kind == PL.OP_CHAIN and op.extra.get("x3"):
-                # bf16x3 chain: csrc/hvn_conv_chain_x3.hip (tile_n 128) or, where it exists (conv3 with 64 input channels), the form with the
-                # input tile resident in registers and every other operand a chunk ahead in flight (csrc/hvn_conv_chain_x3r.hip, tile_n
-                # X3R) -- same bits (tests/test_gpu_chain.py), picked by time.  HVN_CHAIN_X3R=0 | force: never | wherever it exists.
-                mode = os.environ.get("HVN_CHAIN_X3R", "1")
-                x2 = op.extra.get("x2")
-                if mode == "0" or op.x.c != 64 or (x2 is not None and (x2.c != 64 or op.res is not None or op.extra["cout2"] != 64)):
-                    continue
-                key = ("chain_x3", sub_n if (i < enc_end or self.split_decoder) else self.max_batch, op.x.c, x2.c if x2 is not None else 0, op.cout, op.extra["cout2"],
-                       op.y.h, op.y.w, op.res is not None, op.post is not None, op.pre is not None, int(op.extra.get("x3", 0)), mode)
-                if key not in self.tile_choice:
-                    o = self.ops[i]
-                    t = {}
-                    for tn in ((X3R,) if mode == "force" else (128, X3R)):
-                        o.tile_n = tn
-                        t[tn] = time_op(i)
-                    best = X3R if (mode == "force" or t[X3R] < margin * t[128]) else 128
-                    self.tile_choice[key] = (best, t.get(128, float("nan")), t[X3R], dict(t))
-                self.ops[i].tile_n = self.tile_choice[key][0]
-                continue
-            if op.kind == PL.OP_CHAIN:                     # chained 1x1 convs: 128 or 64 pixels per workgroup (same bits)
-                if os.environ.get("HVN_CHAIN_BM"):         # A/B runs: force one
-                    self.ops[i].tile_n = int(os.environ["HVN_CHAIN_BM"])
-                    continue
-                x2 = op.extra.get("x2")
-                key = ("chain", sub_n if (i < enc_end or self.split_decoder) else self.max_batch, op.x.c, x2.c if x2 is not None else 0, op.cout, op.extra["cout2"], op.y.h, op.y.w, op.res is not None,
-                       op.post is not None, op.pre is not None)
-                if key not in self.tile_choice:
-                    o = self.ops[i]
-                    t = {}
-                    for tn in (128, 64):
-                        o.tile_n = tn
-                        t[tn] = time_op(i)
-                    self.tile_choice[key] = (64 if t[64] < margin * t[128] else 128, t[128], t[64])
-                self.ops[i].tile_n = self.tile_choice[key][0]
-                continue
-            if op.kind != PL.OP_CONV or op.tile_n not in (128, 64) or int(op.extra.get("groups", 1)) != 1:
-                continue
-            x2 = op.extra.get("x2")
-            key = (sub_n if (i < enc_end or self.split_decoder) else self.max_batch, op.kh, op.kw, op.stride, op.x.c, op.cout, op.y.h, op.y.w, op.x.h, op.x.w, op.res is not None, op.pre is not None,
-                   op.post is not None, int(op.extra.get("nbatch", 1)), x2.c if x2 is not None else 0)
-            # 128-channel-wide plans: 128 x 128 or 128 x 64 tiles; 64-wide ones: 128 x 64 or 256 x 64 (tile_n 320 = 64 | 0x100)
-            if op.tile_n == 64 and (x2 is not None or op.extra.get("x3")):
-                continue                                   # the fused-shortcut and bf16x3 instantiations exist for 128 x 128 and 128 x 64 tiles only
-            key = key + (int(op.extra.get("x3", 0)),)
-            cands = (128, 64) if op.tile_n == 128 else (64, 320)
-            if op.tile_n == 128 and op.extra.get("x3") and x3g_forms_for(op):
-                # + the LDS-DMA forms of the bf16x3 kernel (csrc/hvn_conv_x3g.hip): 256 | 128 pixels x 128 channels, same bits
-                forced = os.environ.get("HVN_X3G_FORCE")       # tests / A-B runs: that form wherever it exists, no timing
-                if forced and int(forced) in x3g_forms_for(op):
-                    self.ops[i].tile_n = int(forced)
-                    try:
-                        time_op(i)
-                        continue
-                    except L.HvnError:
-                        self.ops[i].tile_n = 128
-                cands = cands + x3g_forms_for(op)
-            key = key + (cands,)                           # (the cache is shared between engines: another candidate set is another question)
-            if key not in self.tile_choice:
-                o = self.ops[i]
-                t = {}
-                for tn in cands:
-                    o.tile_n = tn
-                    try:
-                        t[tn] = time_op(i)
-                    except L.HvnError:
-                        if tn in (128, 64, 320):
-                            raise
-                        t[tn] = float("inf")       # an LDS-DMA form the launcher refuses for this geometry (32-bit reach of a 256-row tile)
-                best = min(cands[1:], key=lambda tn: t[tn])
-                self.tile_choice[key] = (best if t[best] < margin * t[cands[0]] else cands[0], t[cands[0]], t[best], dict(t))
-            self.ops[i].tile_n = self.tile_choice[key][0]
-        torch.cuda.synchronize(self.device)
+            def measure(tn):
+                o.tile_n = tn
+                return T.time_launch(lambda: L.check(lib.hvn_run_op(base + i * osz, nb, stream), "hvn_run_op (autotune)"))
 
-    def autotune_bf16_forms(self, reps=3, margin=0.985):
-        """bf16 engine (BASELINE cfg 3): every CONV launch with >= 128 output channels and no prologue is timed once per distinct
-        shape on csrc/hvn_conv_bf16.hip (tile_n 128) and on the two LDS-DMA forms of csrc/hvn_conv_bf16g.hip (256 | 128 pixels x 128
-        channels) and keeps the fastest -- same packing and same bits for all three (tests/test_gpu_bf16.py).  HVN_BF16G=0 keeps
-        hvn_conv_bf16.hip everywhere, HVN_BF16G_FORCE=896 | 640 takes that form wherever it exists (tests, A/B runs)."""
-        import os
-
-        lib = L.lib()
-        reps = max(1, int(os.environ.get("HVN_TUNE_REPS", reps)))
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        osz = ctypes.sizeof(L.hvn_op)
-        base = ctypes.addressof(self.ops)
-        forced = os.environ.get("HVN_BF16G_FORCE")
-
-        def time_op(i):
-            best = float("inf")
-            for r in range(reps + 1):
-                e0.record()
-                L.check(lib.hvn_run_op(base + i * osz, self.max_batch, ctypes.c_void_p(stream)), "hvn_run_op (autotune)")
-                e1.record()
-                e1.synchronize()
-                if r:
-                    best = min(best, e0.elapsed_time(e1))
-            return best
-
-        for i, op in enumerate(self.plan.ops):
-            if op.kind != PL.OP_CONV or self.ops[i].tile_n != 128 or op.pre is not None or op.cout < 128 or int(op.extra.get("nbatch", 1)) > 1:
-                continue
-            x2 = op.extra.get("x2")
-            key = ("bf16", self.max_batch, op.kh, op.kw, op.stride, op.x.c, op.cout, op.y.h, op.y.w, op.x.h, op.x.w, op.res is not None,
-                   op.post is not None, x2.c if x2 is not None else 0, int(op.extra.get("groups", 1)))
-            key = key + (forced,)
-            if key not in self.tile_choice:
-                t = {}
-                for tn in ((int(forced),) if forced else (128, X3G_256, X3G_128)):
-                    self.ops[i].tile_n = tn
-                    try:
-                        t[tn] = time_op(i)
-                    except L.HvnError:
-                        if tn == 128:
-                            raise
-                        t[tn] = float("inf")           # a form the launcher refuses for this geometry
-                best = min(t, key=t.get)
-                if t[best] == float("inf") or (not forced and best != 128 and t[best] >= margin * t[128]):
-                    best = 128
-                self.tile_choice[key] = (best, t.get(128, float("nan")), t[best], dict(t))
-            self.ops[i].tile_n = self.tile_choice[key][0]
+            o.tile_n = T.pick(T.CACHE, T.launch_key(self.device, family, o, nb), cands, measure, forced=T.forced_form(o))
         torch.cuda.synchronize(self.device)
 
     # ---------------------------------------------------------------------------------

@@ -20,16 +20,13 @@ import torch
 from . import arch
 from . import lib as L
 from . import train_plan as TP
+from . import tune as T
 from . import winograd as WG
 from .plan import OP_CONV, OP_CONV0, OP_HEAD, OP_UPADD, OP_WINO_IN, OP_WINO_OUT, _tile_n
 
 T_NET, T_PACK_W, T_BN_FWD, T_BN_BWD, T_WGRAD, T_CONV0_WGRAD, T_UPADD_BWD, T_HEAD_BWD, T_WINO_DY, T_WINO_DW = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 T_SPLIT_X3, T_PACK_MULTI = 11, 12
 MOMENTUM = 0.1
-
-
-_TILE_CHOICE = {}       # (batch, launch shape) -> (choice, ms of the static choice, ms of the alternative): see TrainEngine.autotune_tiles
-WGRAD_TARGETS = (1536, 1024, 768, 512, 384)     # workgroups a weight-gradient launch may aim at; the first is the untuned default
 
 
 def static_wgrad_target(kh, kw):
@@ -41,11 +38,6 @@ def static_wgrad_target(kh, kw):
     launches of a step: 15.2 / 14.3 / 26.3 ms with this rule against 15.3 / 15.4 / 26.6 at 1536 everywhere and 14.5 / 13.7 / 24.6 with
     every launch at its own best."""
     return 1024 if kh * kw > 1 else 768
-
-
-def _tune_reps(default):
-    """Timings per candidate of the engines' timing passes (HVN_TUNE_REPS; tests/conftest.py sets 1: every candidate is bit-identical)."""
-    return max(1, int(os.environ.get("HVN_TUNE_REPS", default)))
 
 
 _STREAMS = {}
@@ -594,112 +586,66 @@ class TrainEngine:
             ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(t), ctypes.sizeof(L.hvn_top))
         return arr
 
-    def autotune_tiles(self, reps=3, margin=0.985):
-        """Measured column-tile selection for the step's CONV launches (forward convs, data gradients, the Winograd-domain products),
+    def autotune_tiles(self):
+        """Measured launch-form selection for the step's CONV launches (forward convs, data gradients, the Winograd-domain products),
         like `engine.Engine.autotune_tiles` for the inference plan: the static choice of `plan._tile_n` fits batch 32 of the
         inference path, while a phase-1 step carries 4 samples per GPU (opt.py:75-76) and most of its launches are one or two rounds
-        of workgroups, where the narrower tile's finer quantisation wins.  Candidates: 128 x 128 | 128 x 64 for cout >= 128,
-        128 x 64 | 256 x 64 for cout = 64 -- same packed weights, same k order per output element, hence the same bits.  Timed
-        on whatever the arenas hold (min of `reps` HIP-event timings after a warm-up launch); one choice per launch shape and
-        batch, shared by every engine of the process.  The weight-gradient launches get the same treatment for the split of
-        their pixel sum (fewer, longer workgroups pay fewer atomics: best for the encoder's few-tile launches at batch 4; the
+        of workgroups, where the narrower tile's finer quantisation wins.  Candidates: `tune.candidates` -- same packed weights, same
+        k order per output element, hence the same bits.  Timed on whatever the arenas hold; one choice per launch shape and
+        batch, shared by every engine of the process (`tune.choose`).  The weight-gradient launches get the same treatment for the
+        split of their pixel sum (fewer, longer workgroups pay fewer atomics: best for the encoder's few-tile launches at batch 4; the
         decoder's 400-tile 5x5 launches want the opposite).  HVN_TILE_SELECT=0 | model keeps the static choices."""
-        if os.environ.get("HVN_TILE_SELECT", "auto") in ("0", "model"):
+        if T.tile_select() != "auto":
             return
         lib = L.lib()
         stream = self._stream()
-        reps = _tune_reps(reps)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-        def time_op(o):
-            best = float("inf")
-            for r in range(reps + 1):
-                e0.record()
-                L.check(lib.hvn_run_op(ctypes.addressof(o), self.n, stream), "hvn_run_op (autotune)")
-                e1.record()
-                e1.synchronize()
-                if r:
-                    best = min(best, e0.elapsed_time(e1))
-            return best
-
         for o in self._keep:
-            if not isinstance(o, L.hvn_op) or o.kind != OP_CONV or o.groups > 1 or o.tile_n not in (128, 64):
+            cands = T.candidates(o) if isinstance(o, L.hvn_op) else ()
+            if not cands:
                 continue
-            if o.tile_n == 64 and (o.x2.base or o.act_dtype in (2, 3)):
-                continue                                   # the fused-shortcut / bf16x3 instantiations exist for 128 x 128 and 128 x 64 tiles only (as in Engine.autotune_tiles)
-            key = (self.n, o.kh, o.kw, o.stride, o.pad_t, o.x.c, o.cout, o.y.h, o.y.w, o.x.h, o.x.w, bool(o.res.base), int(o.nbatch),
-                   bool(o.pre_scale), int(o.x2.c) if o.x2.base else 0, int(o.act_dtype))
-            cands = (128, 64) if o.tile_n == 128 else (64, 320)
-            if (o.tile_n == 128 and o.act_dtype in (2, 3) and o.cout >= 128 and not o.pre_scale and os.environ.get("HVN_X3G", "1") != "0"):
-                cands = cands + (896, 640)                 # + the LDS-DMA forms of the bf16x3 convolution (csrc/hvn_conv_x3g.hip): same packing, same bits
-            key = key + (cands, str(self.device))          # (round-5 advisor: another candidate set / device is another question)
-            if key not in _TILE_CHOICE:
-                t = {}
-                for tn in cands:
-                    o.tile_n = tn
-                    try:
-                        t[tn] = time_op(o)
-                    except L.HvnError:
-                        if tn in (128, 64, 320):
-                            raise
-                        t[tn] = float("inf")               # a form the launcher refuses for this geometry
-                best = min(cands[1:], key=lambda tn: t[tn])
-                _TILE_CHOICE[key] = (best if t[best] < margin * t[cands[0]] else cands[0], t[cands[0]], t[best])
-            o.tile_n = _TILE_CHOICE[key][0]
+
+            def measure(tn):
+                o.tile_n = tn
+                return T.time_launch(lambda: L.check(lib.hvn_run_op(ctypes.addressof(o), self.n, stream), "hvn_run_op (autotune)"))
+
+            o.tile_n = T.choose(T.CACHE, T.launch_key(self.device, "train-conv", o, self.n), cands, measure)[0]
         # weight gradients: the split of the pixel sum (hvn_top.mode = workgroups aimed at; csrc/hvn_train.hip: launch_wgrad)
         tsz = ctypes.sizeof(L.hvn_top)
         base = ctypes.addressof(self.bwd_ops)
 
-        def time_top(i):
-            best = float("inf")
-            for r in range(reps + 1):
-                e0.record()
-                rc = lib.hvn_run_train_plan(base + i * tsz, 1, self.n, stream)
-                if rc:
-                    raise L.HvnError("hvn_run_train_plan (autotune) failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
-                e1.record()
-                e1.synchronize()
-                if r:
-                    best = min(best, e0.elapsed_time(e1))
-            return best
+        def run_top(i):
+            rc = lib.hvn_run_train_plan(base + i * tsz, 1, self.n, stream)
+            if rc:
+                raise L.HvnError("hvn_run_train_plan (autotune) failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
 
         for i in range(len(self.bwd_ops)):
             t = self.bwd_ops[i]
             if t.kind != T_WGRAD or self.deterministic:      # a timed split = a summation order that depends on the box and the run
                 continue
-            key = ("wgrad", self.n, t.kh, t.kw, t.stride, t.pad_t, t.x.c, t.dy.c, t.dy.h, t.dy.w, t.x.h, t.x.w, t.groups, int(t.nbatch), int(t._pad))
-            if key not in _TILE_CHOICE:
-                ms = {}
-                for want in WGRAD_TARGETS:
-                    t.mode = want
-                    ms[want] = time_top(i)
-                best = min(ms, key=ms.get)
-                _TILE_CHOICE[key] = (best if ms[best] < margin * ms[WGRAD_TARGETS[0]] else WGRAD_TARGETS[0], ms[WGRAD_TARGETS[0]], ms[best])
-            t.mode = _TILE_CHOICE[key][0]
+
+            def measure(want):
+                t.mode = want
+                return T.time_launch(lambda: run_top(i))
+
+            key = (str(self.device), "train-wgrad", self.n, t.kh, t.kw, t.stride, t.pad_t, t.x.c, t.dy.c, t.dy.h, t.dy.w, t.x.h, t.x.w, t.groups, int(t.nbatch), int(t._pad))
+            t.mode = T.choose(T.CACHE, key, T.WGRAD_TARGETS, measure)[0]
         torch.cuda.synchronize(self.device)
         self.gmem.zero_()       # the data-gradient and weight-gradient launches accumulate
         self._share_launch_shapes()
 
-    def _choose_wgrad_stream(self, reps=2):
-        """HVN_TRAIN_WGRAD_STREAM=auto: the whole backward list timed with the weight gradients floating and in list order (on whatever
-        the arenas hold, like `autotune_tiles`; the forward list is not run: it would move the running statistics), the faster one kept.
+    def _choose_wgrad_stream(self):
+        """HVN_TRAIN_WGRAD_STREAM=auto: the whole backward list timed in list order and with the weight gradients floating (on whatever
+        the arenas hold, like `autotune_tiles`; the forward list is not run: it would move the running statistics); floating is kept when
+        it wins by `tune.MARGIN` (a tie keeps the list order: fewer events, fewer host calls).  Asked per engine, not cached.
         Every rank may answer for itself: the answer changes no bit."""
-        if self._wgrad_mode != "auto" or not self._floats or os.environ.get("HVN_TILE_SELECT", "auto") == "0":
+        if self._wgrad_mode != "auto" or not self._floats or T.tile_select() == "0":
             return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ms = {}
-        for on in (True, False):
+
+        def measure(on):
             self.wgrad_stream = on
-            best = float("inf")
-            for r in range(_tune_reps(reps) + 1):
-                e0.record()
-                self._run_range(self.bwd_ops, self._bwd_runs, 0, len(self.bwd_ops), "backward (timing)")
-                e1.record()
-                e1.synchronize()
-                if r:
-                    best = min(best, e0.elapsed_time(e1))
-            ms[on] = best
-        self.wgrad_stream = ms[True] < 0.985 * ms[False]          # a tie keeps the list order (fewer events, fewer host calls)
+            return T.time_launch(lambda: self._run_range(self.bwd_ops, self._bwd_runs, 0, len(self.bwd_ops), "backward (timing)"), reps=2)
+
+        self.wgrad_stream, _, _, ms = T.choose({}, (), (False, True), measure)
         self.wgrad_stream_ms = (ms[True], ms[False])
         torch.cuda.synchronize(self.device)
         self.gmem.zero_()
@@ -714,7 +660,7 @@ class TrainEngine:
         all-reduce) and keeps that rank's own timings.  HVN_TILE_SHARE=0 keeps the per-rank choices everywhere."""
         import torch.distributed as dist
 
-        if (not self._share_shapes or os.environ.get("HVN_TILE_SHARE", "1") == "0" or
+        if (not self._share_shapes or T.knob("HVN_TILE_SHARE") == "0" or
                 not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)):
             return
         convs = [o for o in self._keep if isinstance(o, L.hvn_op) and o.kind == OP_CONV]

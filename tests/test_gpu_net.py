@@ -49,6 +49,30 @@ def test_infer_step_matches_reference_golden(name):
         assert (got[..., 0] != pmap[..., 0]).mean() < 2e-3  # argmax flips only on near-tied logits
 
 
+def test_a_second_engine_of_the_same_plan_times_nothing(monkeypatch):
+    """Launch forms are chosen once per process and launch shape (hover_net_amd.tune.CACHE): a second engine built for the same plan
+    and batch issues no timing launch -- counted at the tuner's one timer -- and binds the same forms."""
+    from hover_net_amd import tune
+
+    mode, nt, sd, tiles, crop, logits, pmap = load_case("orig5")
+    timed = []
+    timer = tune.time_launch
+    monkeypatch.setattr(tune, "time_launch", lambda *a, **kw: (timed.append(1), timer(*a, **kw))[1])
+
+    def build():
+        net = _model(mode, nt, sd)
+        net.max_batch = len(tiles)
+        eng = net.engine(len(tiles))
+        assert any(tune.candidates(o) for o in eng.ops)
+        return [int(o.tile_n) for o in eng.ops], eng._stream_off
+
+    first = build()
+    assert tune.entries("infer-conv") and tune.entries("streams")
+    del timed[:]
+    assert build() == first
+    assert timed == []
+
+
 def test_batch_matches_oracle_and_is_batch_invariant():
     from hover_net_amd.synth import synth_state_dict, synth_tiles
     from oracle import net_torch

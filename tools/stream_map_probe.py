@@ -47,8 +47,8 @@ def main():
             best = min(best, (time.perf_counter() - t0) / 10)
         out.append(best * 1e3)
         del net
-    from hover_net_amd import engine as E
-    pick = {k_[1:3]: (v[0], {o: round(m, 2) for o, m in v[1].items()}) for k_, v in E._STREAM_CHOICE.items()}
+    from hover_net_amd import tune
+    pick = {k_[2:4]: (v[0], {o: round(m, 2) for o, m in v[3].items()}) for k_, v in tune.entries("streams")}
     if len(sys.argv) > 2:
         print("idle streams created first: %d   " % k + "   ".join("schedule %s %.2f ms" % (a, t) for a, t in zip(sys.argv[2:], out)) + "   pool offsets: %s" % pick, flush=True)
         return

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hover_net_amd import net_desc  # noqa: E402
 from hover_net_amd.optim import FusedAdam  # noqa: E402
 from hover_net_amd.synth import synth_state_dict, synth_train_batch  # noqa: E402
-from hover_net_amd import train_engine  # noqa: E402
+from hover_net_amd import tune  # noqa: E402
 from hover_net_amd.train_engine import TrainEngine  # noqa: E402
 
 
@@ -166,6 +166,7 @@ def main():
         af, ab, ef, eb = conv_flops(eng, bs)
         ms = (tf + tb + to) / k
         slab_mb = eng.gslab.numel() * 4 / 1e6
+        conv, wgrad = ([v for key, v in tune.entries(family) if key[2] == bs] for family in ("train-conv", "train-wgrad"))
         print(json.dumps({"phase": phase, "freeze": freeze, "batch": bs, "ms_per_step": ms, "forward_ms": tf / k, "loss_backward_ms": tb / k,
                           "optimizer_ms": to / k, "steps_per_s": 1000.0 / ms, "tiles_per_s": bs * 1000.0 / ms,
                           "executed_gflop_forward": ef / 1e9, "executed_gflop_backward": eb / 1e9,
@@ -178,16 +179,13 @@ def main():
                           "wgrad_stream_timed_ms_on_off": [round(v, 3) for v in getattr(eng, "wgrad_stream_ms", ())],
                           "allreduce": "not measurable on one GPU: N > 1 all-reduces the gradient slab (%.0f MB fp32) in two buckets + 64 doubles of "
                                        "loss partial sums per step; no RCCL run exists for it (one-GPU box)" % slab_mb,
-                          "conv_tiles": {"launch_shapes_timed": sum(1 for k in train_engine._TILE_CHOICE if k[0] == bs),
-                                         "re_tiled": sum(1 for k, v in train_engine._TILE_CHOICE.items() if k[0] == bs and v[0] in (64, 320) and v[1] > v[2]),
-                                         "static_ms": sum(v[1] for k, v in train_engine._TILE_CHOICE.items() if k[0] == bs),
-                                         "chosen_ms": sum(min(v[1], v[2]) if v[0] in (64, 320) and v[2] < v[1] else v[1]
-                                                          for k, v in train_engine._TILE_CHOICE.items() if k[0] == bs),
-                                         "wgrad_targets": {str(w): sum(1 for k, v in train_engine._TILE_CHOICE.items() if k[0] == "wgrad" and k[1] == bs and v[0] == w)
-                                                           for w in train_engine.WGRAD_TARGETS},
-                                         "wgrad_static_ms": sum(v[1] for k, v in train_engine._TILE_CHOICE.items() if k[0] == "wgrad" and k[1] == bs),
-                                         "wgrad_chosen_ms": sum(v[2] if v[0] != train_engine.WGRAD_TARGETS[0] else v[1]
-                                                                for k, v in train_engine._TILE_CHOICE.items() if k[0] == "wgrad" and k[1] == bs),
+                          "conv_tiles": {"launch_shapes_timed": len(conv),
+                                         "re_tiled": sum(1 for v in conv if v[0] in (64, tune.T256X64) and v[1] > v[2]),
+                                         "static_ms": sum(v[1] for v in conv),
+                                         "chosen_ms": sum(min(v[1], v[2]) if v[0] in (64, tune.T256X64) and v[2] < v[1] else v[1] for v in conv),
+                                         "wgrad_targets": {str(w): sum(1 for v in wgrad if v[0] == w) for w in tune.WGRAD_TARGETS},
+                                         "wgrad_static_ms": sum(v[1] for v in wgrad),
+                                         "wgrad_chosen_ms": sum(v[2] if v[0] != tune.WGRAD_TARGETS[0] else v[1] for v in wgrad),
                                          "note": "TrainEngine.autotune_tiles: one timing per distinct launch shape (sums are over shapes, not launches); HVN_TILE_SELECT=0 keeps the static choices"},
                           "loss": eng.loss_terms()["overall_loss"], "arena_gb": eng.arena.numel() * 4 / 1e9, "grad_gb": eng.gmem.numel() * 4 / 1e9}))
         del eng, net, opt
