@@ -226,6 +226,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_wgrad_f32(const WgradArgs p)
     // per-thread staging coordinates: row (n, oy, ox) advanced incrementally by 32 per k-step
     const int a_c4 = tid % (BM / 4), a_r = tid / (BM / 4);
     const int b_c4 = tid % (BN / 4), b_r = tid / (BN / 4);
+    const bool a_ok = m0 + a_c4 * 4 < p.Cout;        // Cout may end inside the last output tile: nothing of dy lies behind it
     int an[PA], ay[PA], ax[PA], bn_[PB], by[PB], bx[PB];
     unsigned arow[PA], brow[PB];
     const unsigned HoWo = (unsigned)p.Ho * p.Wo;
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void hvn_conv_wgrad_f32(const WgradArgs p)
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
             f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (arow[j] < r_end) v = *(const f32x4 *)(pdy + (long)an[j] * p.dsn + (long)ay[j] * p.dsy + (long)ax[j] * p.dsx + m0 + a_c4 * 4);
+            if (arow[j] < r_end && a_ok) v = *(const f32x4 *)(pdy + (long)an[j] * p.dsn + (long)ay[j] * p.dsy + (long)ax[j] * p.dsx + m0 + a_c4 * 4);
             ra[j] = v;
             arow[j] += 32;
             advance(an[j], ay[j], ax[j]);

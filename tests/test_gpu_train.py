@@ -1,7 +1,10 @@
 """-m gpu: the HIP training kernels (through the C ABI: hvn_run_train_plan / hvn_loss_* / hvn_adam_step) against
 the torch references of tests/train_interp.py, and the whole training step against the training oracle.
 
-Floating-point bar: per-kernel 1e-4..1e-3 relative on the tensor's scale (fp32 sums in a different order); the
+Floating-point bar: per-kernel 1e-4..1e-3 relative on the tensor's scale (fp32 sums in a different order), for BOTH forms of the
+cross-workgroup reductions: the atomic one (hvn_run_train_plan, hvn_loss.partials = NULL) and the deterministic one the engine uses by
+default (hvn_run_train_plan_ws with a workspace, hvn_loss.partials: stored per-split / per-workgroup copies added in a fixed order), whose
+copies, order of summation and workspace size are checked kernel by kernel as well, in front of the whole-step tests; the
 whole step is held to the fp32 noise floor measured against a float64 run of the oracle (the synthetic problem
 amplifies rounding through ReLU flips and batch statistics: torch's own fp32 run is a few per cent off the float64
 gradient on the worst tensors)."""
@@ -422,6 +425,477 @@ def test_adam_matches_torch():
         torch.cuda.synchronize()
         assert float((w[:n].cpu() - p.data).abs().max()) < 1e-6      # a couple of ulp: sqrt(v) * (1/sqrt(bc2)) vs sqrt(v) / sqrt(bc2)
     assert float(w[n:].abs().max()) == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------
+# The deterministic reductions (hvn_run_train_plan_ws with a workspace, hvn_loss.partials): every split / workgroup STORES its partial
+# result into its own copy and a second kernel adds the copies in a fixed order.  Kernel by kernel, at the bar of the atomic test of the
+# same kernel (the deterministic form is one more fp32 summation order), plus what only this form has: every copy element has a writer
+# (the workspace starts as NaN), the copies sit where the header says, the order of the sum is the documented one (recomputed on the
+# CPU with IEEE float adds: exact), nothing depends on what the workspace held, nothing is written behind hvn_train_workspace_bytes.
+_WS_GUARD = 4096
+_WS_SENTINEL = -7.25e11
+
+
+def run_tops_ws(tops, batch, poison):
+    """hvn_run_train_plan_ws over `tops` with EXACTLY hvn_train_workspace_bytes of workspace, pre-filled with `poison` ("nan" | "garbage":
+    random finite values) and followed by a guard that must come back bit-unchanged.  -> (workspace tensor, bytes).  After a single-op
+    list the workspace still holds that op's copies."""
+    L = _L()
+    lib = L.lib()
+    arr = (L.hvn_top * len(tops))()
+    for i, t in enumerate(tops):
+        ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(t), ctypes.sizeof(L.hvn_top))
+    need = int(lib.hvn_train_workspace_bytes(arr, len(tops), batch))
+    assert need % 4 == 0
+    nf = need // 4
+    ws = torch.empty(nf + _WS_GUARD, device="cuda")
+    if poison == "nan":
+        ws[:nf] = float("nan")
+    else:
+        assert poison == "garbage"
+        ws[:nf] = torch.randn(nf, device="cuda", generator=torch.Generator(device="cuda").manual_seed(77)) * 1e6
+    guard = torch.full((_WS_GUARD,), _WS_SENTINEL, device="cuda")
+    ws[nf:] = guard
+    rc = lib.hvn_run_train_plan_ws(arr, len(tops), batch, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), ctypes.c_void_p(ws.data_ptr()), need)
+    assert rc == 0, lib.hvn_train_last_error().decode()
+    torch.cuda.synchronize()
+    assert torch.equal(ws[nf:].view(torch.int32), guard.view(torch.int32)), "a write behind hvn_train_workspace_bytes"
+    return ws, need
+
+
+def reduce_parts_cpu(d0, copies):
+    """hvn_reduce_parts as the header states it, in IEEE float32 on the CPU: chain j adds copies j, j + 4, ... ascending from 0.f,
+    total = (c0 + c1) + (c2 + c3), result = d0 + total."""
+    assert d0.dtype == torch.float32 and copies.dtype == torch.float32
+    ch = []
+    for j in range(4):
+        s = torch.zeros_like(d0)
+        for k in range(j, copies.shape[0], 4):
+            s = s + copies[k]
+        ch.append(s)
+    return d0 + ((ch[0] + ch[1]) + (ch[2] + ch[3]))
+
+
+def check_reduction(tops, batch, dsts, expect_need, what, reset=None, also=()):
+    """The five checks on the single reducing op `tops` (a one-element list).  dsts: dicts with `dst` (flat cuda tensor holding random
+    non-zero values), `want` (float64, dst's layout), `tol`, `copies` (callable: the workspace's floats on the CPU -> [copies, elems]),
+    `name`.  reset(): restores whatever else the op accumulates into; also: further cuda tensors to read back after the first run.
+    -> (destinations after the first run, workspace floats, `also` after the first run)."""
+    d0 = [d["dst"].clone() for d in dsts]
+    assert all(float(z.abs().min()) > 0 for z in d0)
+
+    def run(poison):
+        if reset:
+            reset()
+        return run_tops_ws(tops, batch, poison)
+
+    # 1. the deterministic path really ran: the workspace is the copies, nothing else
+    ws, need = run("nan")
+    assert need == expect_need, (what, need, expect_need)
+    wsc = ws[:need // 4].cpu()
+    first = [d["dst"].cpu().clone() for d in dsts]
+    also_first = [a.cpu().clone() for a in also]
+    if need:
+        assert not bool(torch.isnan(wsc).any()), "%s: %d copy elements have no writer" % (what, int(torch.isnan(wsc).sum()))
+    for d, z, f in zip(dsts, d0, first):
+        name = "%s %s" % (what, d["name"])
+        # 2. value, added to what the destination held
+        assert bool(torch.isfinite(f).all()), "%s: not finite -- a copy element without a writer reached the gradient" % name
+        close(f.double() - z.cpu().double(), d["want"], d["tol"], name)
+        if need:
+            cp = d["copies"](wsc)
+            assert cp.shape[1:] == f.shape
+            # 3. the copies on their own
+            close(cp.double().sum(0), d["want"], d["tol"], name + " (sum of the copies)")
+            # 4. the order of the sum, exactly
+            assert torch.equal(reduce_parts_cpu(z.cpu(), cp), f), name + ": not d0 + ((c0 + c1) + (c2 + c3)) over chains j, j + 4, ..."
+    run("nan")
+    for d, z in zip(dsts, d0):
+        close(d["dst"].cpu().double() - z.cpu().double(), 2 * d["want"], d["tol"], "%s %s accumulate" % (what, d["name"]))
+    # 5. the same bits again, whatever the workspace held
+    for d, z in zip(dsts, d0):
+        d["dst"].copy_(z)
+    _, need2 = run("garbage")
+    assert need2 == need
+    for d, f in zip(dsts, first):
+        assert torch.equal(d["dst"].cpu(), f), "%s %s: depends on what the workspace held" % (what, d["name"])
+    return first, wsc, also_first
+
+
+def wgrad_split(R, tiles, nbatch, want):
+    """csrc/hvn_train.hip:hvn_wgrad_split -> (splits, rows per split)."""
+    want = want if want > 0 else 1536
+    ksplit = -(-want // (tiles * nbatch))
+    ksplit = max(1, min(ksplit, -(-R // 256)))
+    rps = -(-(-(-R // ksplit)) // 32) * 32
+    return -(-R // rps), rps
+
+
+def wgrad_tiles(cin, cout, taps, x3):
+    """The tile rule of hvn_launch_wgrad / hvn_launch_wgrad_x3 -> workgroups per split."""
+    bm = 128 if cout >= 128 else 64 if cout >= 64 else 32
+    bn = 128 if cin % 128 == 0 else 64 if cin % 64 == 0 else 32
+    if x3:
+        bm = bn = 128
+    return -(-cout // bm) * (cin // bn) * taps
+
+
+_WGRAD_REF = {}
+
+
+def wgrad_problem(n, H, W, cin, cout, k, stride, pad, groups, step, seed):
+    """As test_wgrad_matches_torch builds it (x a channel / spatial window of a bigger buffer, dy a possibly dilated view), rectangular;
+    the destination holds random non-zero values.  -> (op, tensors to keep alive, dw, float64 reference in dw's layout, rows n * ho * wo).
+    The reference of the last problem is kept (the cases of one shape run one after the other), no more."""
+    from hover_net_amd import lib as L
+    g = torch.Generator().manual_seed(seed)
+    ho = (H + pad[0] + pad[1] - k) // stride + 1
+    wo = (W + pad[0] + pad[1] - k) // stride + 1
+    xb = torch.randn(n, H + 3, W + 2, cin + 32, generator=g)
+    dyb = torch.randn(n, ho * step, wo * step, cout, generator=g)
+    cin_g = cin // groups
+    d0 = torch.randn(cout * k * k * cin_g, generator=g)
+    d0 = torch.where(d0 == 0, torch.ones_like(d0), d0)
+    key = (n, H, W, cin, cout, k, stride, pad, groups, step, seed)
+    if key not in _WGRAD_REF:
+        x = xb[:, 2:2 + H, 1:1 + W, 32:].double().permute(0, 3, 1, 2)
+        dy = dyb[:, ::step, ::step].double().permute(0, 3, 1, 2).contiguous()
+        xp = F.pad(x, (pad[0], pad[1], pad[0], pad[1]))
+        want = torch.nn.grad.conv2d_weight(xp, (cout, cin_g, k, k), dy, stride=stride, groups=groups)
+        _WGRAD_REF.clear()
+        _WGRAD_REF[key] = want.permute(0, 2, 3, 1).reshape(-1).contiguous()
+    xc, dyc, dw = xb.cuda(), dyb.cuda(), d0.cuda()
+    t = L.hvn_top()
+    t.kind, t.kh, t.kw, t.stride, t.pad_t, t.pad_l, t.groups = 5, k, k, stride, pad[0], pad[0], groups
+    t.x = view_of(xc, 2, 1, H, W, 32, cin)
+    t.dy = view_of(dyc, 0, 0, ho, wo, 0, cout, step=step)
+    t.p[0] = dw.data_ptr()
+    return t, (xc, dyc), dw, _WGRAD_REF[key], n * ho * wo
+
+
+def _no_split_overrides(monkeypatch):
+    for k in ("HVN_WGRAD_WGS", "HVN_WGRAD_MIN_ROWS"):
+        monkeypatch.delenv(k, raising=False)
+
+
+WG_WS_CASES = [  # n, H, W, cin, cout, k, stride, pad(lo,hi), groups, dy step: one per kernel instantiation + the edges
+    (2, 20, 20, 64, 64, 3, 1, (1, 1), 1, 1),        # 64 x 64
+    (2, 24, 24, 128, 256, 1, 1, (0, 0), 1, 1),      # 128 x 128, five splits: chain 0 has two copies
+    (3, 18, 18, 128, 32, 5, 1, (0, 0), 4, 1),       # 32 x 128, block-diagonal, ragged last split
+    (2, 24, 24, 128, 128, 3, 2, (0, 1), 1, 2),      # strided, dilated dy
+    (1, 30, 30, 288, 128, 1, 1, (0, 0), 1, 1),      # 128 x 32
+    (2, 16, 16, 256, 64, 5, 1, (2, 2), 1, 1),       # 64 x 128
+    (5, 22, 22, 64, 256, 1, 2, (0, 0), 1, 2),       # 128 x 64
+    (3, 13, 11, 64, 96, 3, 1, (1, 1), 1, 1),        # cout ends inside the second tile; rectangular; 429 rows: no multiple of 32
+    (5, 9, 7, 96, 160, 1, 1, (0, 0), 1, 1),         # cout ends inside a tile
+    (1, 16, 16, 128, 128, 1, 1, (0, 0), 1, 1),      # 256 rows: a single split, no workspace
+]
+
+
+def check_wgrad_ws(case, want_wgs, x3, tol, monkeypatch):
+    n, H, W, cin, cout, k, stride, pad, groups, step = case
+    _no_split_overrides(monkeypatch)
+    t, keep, dw, want, R = wgrad_problem(n, H, W, cin, cout, k, stride, pad, groups, step, seed=11)
+    t.mode, t._pad = want_wgs, x3
+    elems = dw.numel()
+    splits, rps = wgrad_split(R, wgrad_tiles(cin, cout, k * k, x3), 1, want_wgs)
+    assert (splits == 1) == (R <= 256), (splits, rps)              # what each case is there for
+    need = splits * elems * 4 if splits > 1 else 0
+    d0 = dw.clone()
+    (first,), _, _ = check_reduction([t], n, [dict(dst=dw, want=want, tol=tol, name="dw", copies=lambda ws: ws.view(splits, elems))], need,
+                                     "wgrad %s: %d splits of %d rows (last %d)" % ("bf16x3/%d" % x3 if x3 else "fp32", splits, rps, R - (splits - 1) * rps))
+    if x3:
+        # the tile rule, the workspace and the tolerance are those of the fp32 form at these shapes: what tells the two apart is the bits (other
+        # products, or the same ones in another order, over >= 10^5 elements)
+        dw.copy_(d0)
+        t._pad = 0
+        run_tops_ws([t], n, "nan")
+        assert not torch.equal(dw.cpu(), first), "_pad = %d gave the bits of the fp32 pipe: hvn_conv_wgrad_x3 did not run" % x3
+
+
+@pytest.mark.parametrize("want_wgs", [0, 384])
+@pytest.mark.parametrize("case", WG_WS_CASES, ids=lambda c: "-".join(str(v) for v in c[:6]))
+def test_wgrad_stored_splits_and_their_fixed_order_sum(case, want_wgs, monkeypatch):
+    """HVN_T_WGRAD through hvn_run_train_plan_ws: WgradArgs.part / part_stride, hvn_reduce_parts.  (`mode` = the engine's split target.)"""
+    check_wgrad_ws(case, want_wgs, 0, 2e-4, monkeypatch)
+
+
+@pytest.mark.parametrize("terms", [6, 9])
+@pytest.mark.parametrize("n,H,W,cin,cout,k,stride,pad,step", WGX3_CASES + [(6,) + WGX3_CASES[4][1:]], ids=lambda v: str(v).replace(" ", ""))
+def test_wgrad_on_the_bf16_pipe_stored_splits(n, H, W, cin, cout, k, stride, pad, step, terms, monkeypatch):
+    """The same through csrc/hvn_wgrad_x3.hip (`_pad` = 6 | 9); (2,9,7,384,512) is a single split as it stands and two at n = 6."""
+    check_wgrad_ws((n, H, W, cin, cout, k, stride, pad, 1, step), 0, terms, 2e-4 if terms == 9 else 3e-4, monkeypatch)
+
+
+@pytest.mark.parametrize("n,H,cin,cout,pad", [(3, 66, 128, 128, 0), (4, 38, 256, 64, 2), (2, 34, 128, 32, 0)])
+def test_winograd_domain_weight_gradient_stored_splits(n, H, cin, cout, pad, monkeypatch):
+    """The 64 batched WGRAD problems of the Winograd-domain weight gradient (nbatch = 64): copy s holds problem b at
+    s * 64 * cout * cin + b * cout * cin, and holds the rows [s * rows_per_split, ...) of (image, tile) only."""
+    from hover_net_amd import lib as L
+    from hover_net_amd import winograd as WG
+    _no_split_overrides(monkeypatch)
+    g = torch.Generator().manual_seed(8)
+    ho = H + 2 * pad - 4
+    ty = -(-ho // 4)
+    t1 = ty * ty
+    x = torch.randn(n, H, H, cin, generator=g).relu()
+    dy = torch.randn(n, ho, ho, cout, generator=g) * 0.1
+    dU0 = torch.randn(64 * cout * cin, generator=g) + 3.0
+    dW0 = torch.randn(cout * 25 * cin, generator=g) + 3.0
+    xc, dyc = x.cuda(), dy.cuda()
+    at, gm, bt = WG.MATS[4]
+    mats = torch.tensor(list(bt.reshape(-1)) + list(at.reshape(-1)) + list(gm.reshape(-1)), dtype=torch.float32).cuda()
+    V = torch.zeros(n * 64 * t1 * cin, device="cuda")
+    DM = torch.zeros(n * 64 * t1 * cout, device="cuda")
+    dU = torch.zeros(64 * cout * cin, device="cuda")
+    dW = dW0.cuda()
+
+    def tview(t, h, c):
+        v = L.hvn_view()
+        v.base, v.sn, v.sy, v.sx, v.h, v.w, v.c, v.sc = t.data_ptr(), 64 * t1 * c, t1 * c, c, h, t1, c, 1
+        return v
+    o = L.hvn_op()
+    o.kind, o.kh, o.kw, o.pad_t, o.pad_l = 6, ty, ty, pad, pad
+    o.x, o.y, o.w = view_of(xc), tview(V, 64, cin), mats.data_ptr()
+    t0 = L.hvn_top()
+    t0.kind, t0.net = 1, ctypes.pointer(o)
+    t1_ = L.hvn_top()
+    t1_.kind, t1_.kh, t1_.kw = 9, ty, ty
+    t1_.x, t1_.y = view_of(dyc), tview(DM, 64, cout)
+    t1_.p[0] = mats.data_ptr() + 4 * 64
+    t2 = L.hvn_top()
+    t2.kind, t2.kh, t2.kw, t2.stride, t2.groups, t2.nbatch = 5, 1, 1, 1, 1, 64
+    t2.x, t2.dy = tview(V, 1, cin), tview(DM, 1, cout)
+    t2.p[0] = dU.data_ptr()
+    t2.batch_stride[0], t2.batch_stride[1], t2.batch_stride[2] = t1 * cin, t1 * cout, cout * cin
+    t3 = L.hvn_top()
+    t3.kind, t3.cout, t3.cin_g = 10, cout, cin
+    t3.p[0], t3.p[1], t3.p[2] = dU.data_ptr(), dW.data_ptr(), mats.data_ptr() + 4 * 96
+    R = n * t1
+    splits, rps = wgrad_split(R, wgrad_tiles(cin, cout, 1, 0), 64, 0)
+    assert (splits == 1) == (R <= 256)
+    need = splits * 64 * cout * cin * 4 if splits > 1 else 0
+    # the whole chain, twice, into a non-zero dW (the engine clears dU in front of it)
+    xp = F.pad(x.double().permute(0, 3, 1, 2), (pad, pad, pad, pad))
+    want = torch.nn.grad.conv2d_weight(xp, (cout, cin, 5, 5), dy.double().permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).reshape(-1)
+    for rep, poison in ((1, "nan"), (2, "garbage")):
+        dU.zero_()
+        _, got_need = run_tops_ws([t0, t1_, t2, t3], n, poison)
+        assert got_need == need
+        got = dW.cpu()
+        assert bool(torch.isfinite(got).all())
+        close(got.double() - dW0.double(), rep * want, 1e-4, "winograd-domain wgrad, run %d" % rep)
+    # the dU launch alone (V and dM are in place): the workspace is its own
+    Vc = V.cpu().view(n, 64, t1, cin).permute(1, 0, 2, 3).reshape(64, R, cin).double()
+    Dc = DM.cpu().view(n, 64, t1, cout).permute(1, 0, 2, 3).reshape(64, R, cout).double()
+    want_u = torch.bmm(Dc.transpose(1, 2), Vc)                    # [64][cout][cin]
+    dU.copy_(dU0.cuda())
+    _, wsc, _ = check_reduction([t2], n, [dict(dst=dU, want=want_u.reshape(-1), tol=1e-4, name="dU", copies=lambda ws: ws.view(splits, 64 * cout * cin))],
+                             need, "winograd dU: %d splits of %d rows of %d" % (splits, rps, R))
+    for s in range(splits if need else 0):
+        part = torch.bmm(Dc[:, s * rps:(s + 1) * rps].transpose(1, 2), Vc[:, s * rps:(s + 1) * rps])
+        close(wsc.view(splits, 64, cout, cin)[s], part, 1e-4, "winograd dU, copy %d" % s)
+
+
+def head_problem(n, H, W, C, seed=4):
+    from hover_net_amd import lib as L
+    g = torch.Generator().manual_seed(seed)
+    a = torch.randn(n, H, W, 64, generator=g)
+    da0 = torch.randn(n, H, W, 64, generator=g)
+    dl = torch.randn(n, C, H, W, generator=g)
+    W_ = torch.randn(C, 64, generator=g)
+    dW0, db0 = torch.randn(C * 64, generator=g) + 3.0, torch.randn(C, generator=g) + 3.0
+    dev = dict(a=a.cuda(), da=da0.cuda(), dl=dl.cuda(), W=W_.cuda(), dW=dW0.cuda(), db=db0.cuda())
+    t = L.hvn_top()
+    t.kind, t.cout, t.x, t.dx = 8, C, view_of(dev["a"]), view_of(dev["da"])
+    t.p[0], t.p[1], t.p[2], t.p[3] = dev["dl"].data_ptr(), dev["W"].data_ptr(), dev["dW"].data_ptr(), dev["db"].data_ptr()
+    return t, dev, (a, da0, dl, W_, dW0, db0)
+
+
+@pytest.mark.parametrize("n,H,W,C", [(3, 37, 53, 1), (3, 37, 53, 5), (3, 37, 53, 16), (2, 270, 270, 5)])
+def test_head_backward_stored_workgroup_sums(n, H, W, C):
+    """HVN_T_HEAD_BWD through the workspace: one row of C * 64 + C floats per workgroup (bias tail at C * 64), two reduce launches.
+    5883 pixels = 23 workgroups, the last ragged; 145800 pixels = more groups than the 512 workgroups."""
+    t, dev, (a, da0, dl, W_, dW0, db0) = head_problem(n, H, W, C)
+    run_tops([t], n)                                              # the atomic form: dx has no cross-workgroup sum
+    dx_atomic = dev["da"].cpu().clone()
+    close(dx_atomic - da0, torch.einsum("nchw,ck->nhwk", dl.double(), W_.double()), 1e-4, "head da")
+    dev["dW"].copy_(dW0.cuda())
+    dev["db"].copy_(db0.cuda())
+    wgs = min(-(-n * H * W // 256), 512)
+    nv = C * 64 + C
+    dsts = [dict(dst=dev["dW"], want=torch.einsum("nchw,nhwk->ck", dl.double(), a.double()).reshape(-1), tol=1e-4, name="dW",
+                 copies=lambda ws: ws.view(wgs, nv)[:, :C * 64].contiguous()),
+            dict(dst=dev["db"], want=dl.double().sum((0, 2, 3)), tol=1e-4, name="db", copies=lambda ws: ws.view(wgs, nv)[:, C * 64:].contiguous())]
+    _, _, (dx_det,) = check_reduction([t], n, dsts, wgs * nv * 4, "head backward, %d workgroups" % wgs, reset=lambda: dev["da"].copy_(da0.cuda()),
+                                      also=[dev["da"]])
+    assert torch.equal(dx_det, dx_atomic), "head da differs between the atomic and the deterministic launch"
+
+
+def conv0_problem(n, H, W, pad, seed=4):
+    """-> (op, tensors to keep alive, dw holding random non-zero values, image, dz, workgroups of the launch)."""
+    from hover_net_amd import lib as L
+    g = torch.Generator().manual_seed(seed)
+    img = torch.randint(0, 256, (n, H, W, 3), generator=g, dtype=torch.uint8)
+    ho, wo = H + 2 * pad - 6, W + 2 * pad - 6
+    dz = torch.randn(n, ho, wo, 64, generator=g)
+    dw0 = torch.randn(64 * 147, generator=g) + 3.0
+    imgc, dzc, dw = img.cuda(), dz.cuda(), dw0.cuda()
+    t = L.hvn_top()
+    t.kind, t.pad_t = 6, pad
+    t.x.base, t.x.sn, t.x.sy, t.x.sx, t.x.h, t.x.w, t.x.c, t.x.sc = imgc.data_ptr(), H * W * 3, W * 3, 3, H, W, 3, 1
+    t.dy = view_of(dzc)
+    t.p[0] = dw.data_ptr()
+    cap = 1024 if "HVN_CONV0_WGRAD_VALU" in os.environ else 512          # csrc/hvn_train.hip:conv0_wgrad_wgs (the VALU form keeps more workgroups)
+    return t, (imgc, dzc), dw, img, dz, min(-(-ho // 16) * -(-wo // 16) * n, cap)
+
+
+@pytest.mark.parametrize("n,H,W,pad", [(2, 41, 54, 0), (2, 41, 54, 3), (9, 120, 120, 0)])
+def test_conv0_wgrad_stored_workgroup_sums(n, H, W, pad):
+    """HVN_T_CONV0_WGRAD through the workspace: 64 * 147 floats per workgroup.  41 x 54: partial 16 x 16 tiles on both edges;
+    9 x 120 x 120: 576 tiles on 512 workgroups."""
+    t, keep, dw, img, dz, wgs = conv0_problem(n, H, W, pad)
+    xp = F.pad(img.double().permute(0, 3, 1, 2) / 255.0, (pad, pad, pad, pad))
+    want = torch.nn.grad.conv2d_weight(xp, (64, 3, 7, 7), dz.double().permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).reshape(-1)
+    check_reduction([t], n, [dict(dst=dw, want=want, tol=2e-4, name="dw", copies=lambda ws: ws.view(wgs, 64 * 147))], wgs * 64 * 147 * 4,
+                    "conv0 wgrad, %d workgroups" % wgs)
+
+
+def test_a_workspace_one_vector_short_is_refused_before_any_launch(monkeypatch):
+    """hvn_run_train_plan_ws with hvn_train_workspace_bytes - 16: HVN_E_SIZE, "workspace" in the message, the destination untouched."""
+    from hover_net_amd import lib as L
+    _no_split_overrides(monkeypatch)
+    lib = L.lib()
+    t_w, keep_w, dw, _, _ = wgrad_problem(2, 20, 20, 64, 64, 3, 1, (1, 1), 1, 1, seed=11)
+    t_h, dev_h, _ = head_problem(3, 37, 53, 5)
+    t_c, keep_c, dw_c, _, _, _ = conv0_problem(2, 41, 54, 0)
+    for what, t, n, outs in (("wgrad", t_w, 2, [dw]), ("head", t_h, 3, [dev_h["dW"], dev_h["db"], dev_h["da"]]), ("conv0", t_c, 2, [dw_c])):
+        need = int(lib.hvn_train_workspace_bytes(ctypes.addressof(t), 1, n))
+        assert need > 16, what
+        ws = torch.zeros(need // 4, device="cuda")
+        before = [o.clone() for o in outs]
+        rc = lib.hvn_run_train_plan_ws(ctypes.addressof(t), 1, n, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream),
+                                       ctypes.c_void_p(ws.data_ptr()), need - 16)
+        torch.cuda.synchronize()
+        assert rc == -4 and b"workspace" in lib.hvn_train_last_error(), (what, rc, lib.hvn_train_last_error())
+        for o, b in zip(outs, before):
+            assert torch.equal(o.view(torch.int32), b.view(torch.int32)), what
+        assert float(ws.abs().max()) == 0.0, what
+
+
+def loss_tree_cpu(rows):
+    """hvn_loss_finalize as documented, in IEEE float64: chain j adds rows j, j + 16, ... ascending, then ch[j] += ch[j + w] for w = 8, 4, 2, 1."""
+    ch = np.zeros((16, 64), np.float64)
+    for j in range(16):
+        for r in range(j, rows.shape[0], 16):
+            ch[j] = ch[j] + rows[r]
+    for w in (8, 4, 2, 1):
+        ch[:w] = ch[:w] + ch[w:2 * w]
+    return ch[0]
+
+
+@pytest.mark.parametrize("nt,degenerate", [(0, False), (5, False), (5, True)])
+def test_loss_sums_through_stored_partials(nt, degenerate):
+    """hvn_loss.partials: hvn_loss_partial stores 64 doubles per workgroup, hvn_loss_finalize folds them.  3 x 37 x 53 pixels = 23 rows
+    (more than the 16 chains, no multiple of 16), rectangular; degenerate = np_map all background (focus sum 0) and a tp class without
+    pixels (empty dice terms)."""
+    from hover_net_amd import lib as L
+    from hover_net_amd.synth import synth_train_batch
+    from oracle import train_torch
+    lib = L.lib()
+    n, h, w = 3, 37, 53
+    full = synth_train_batch(n, "original", nt or None, seed=21)
+    batch = {k: np.ascontiguousarray(v[:, 20:20 + h, 11:11 + w]) for k, v in full.items() if k != "img"}
+    if degenerate:
+        batch["np_map"] = np.zeros_like(batch["np_map"])
+        batch["tp_map"] = np.where(batch["tp_map"] == 3, 0, batch["tp_map"])
+        assert len(np.unique(batch["tp_map"])) > 1 and 3 not in batch["tp_map"]
+    else:
+        assert 0 < batch["np_map"].sum() < batch["np_map"].size
+    g = torch.Generator().manual_seed(5)
+    logits = {"np": torch.randn(n, 2, h, w, generator=g) * 2, "hv": torch.randn(n, 2, h, w, generator=g)}
+    if nt:
+        logits = {"tp": torch.randn(n, nt, h, w, generator=g) * 2, **logits}
+    logits["np"][0, :, :4, :4] = torch.tensor([40.0, -40.0]).view(2, 1, 1)
+    lg = {k: v.clone().requires_grad_(True) for k, v in logits.items()}
+    total, terms = train_torch.loss_terms(lg, {k: torch.as_tensor(v) for k, v in batch.items()}, nt or None)
+    total.backward()
+    dev = {k: v.cuda() for k, v in logits.items()}
+    grads = {k: torch.zeros_like(v) for k, v in dev.items()}
+    t_np = torch.as_tensor(batch["np_map"]).to(torch.int32).cuda()
+    t_hv = torch.as_tensor(batch["hv_map"]).cuda()
+    t_tp = torch.as_tensor(batch["tp_map"]).to(torch.int32).cuda() if nt else None
+    sums = torch.zeros(64, dtype=torch.float64, device="cuda")
+    sobel = torch.zeros(n, h, w, 2, device="cuda")
+    rows = -(-n * h * w // 256)
+    cnt = int(lib.hvn_loss_partials_count(n, h, w))
+    assert rows == 23 and cnt == rows * 64
+    parts = torch.empty(cnt + _WS_GUARD, dtype=torch.float64, device="cuda")
+    guard = torch.full((_WS_GUARD,), _WS_SENTINEL, dtype=torch.float64, device="cuda")
+    d = L.hvn_loss()
+    d.logits_np, d.logits_hv, d.grad_np, d.grad_hv = dev["np"].data_ptr(), dev["hv"].data_ptr(), grads["np"].data_ptr(), grads["hv"].data_ptr()
+    if nt:
+        d.logits_tp, d.grad_tp, d.true_tp = dev["tp"].data_ptr(), grads["tp"].data_ptr(), t_tp.data_ptr()
+    d.true_np, d.true_hv, d.sums, d.sobel_ws = t_np.data_ptr(), t_hv.data_ptr(), sums.data_ptr(), sobel.data_ptr()
+    d.n, d.h, d.w, d.nr_types = n, h, w, nt
+    d.total_pixels = float(n * h * w)
+    for i in range(6):
+        d.weight[i] = 1.0
+    d.partials, d.partials_cap = parts.data_ptr(), cnt
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run(poison, sums0, backward=True):
+        if poison == "nan":
+            parts[:cnt] = float("nan")
+        else:
+            parts[:cnt] = torch.randn(cnt, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(78)) * 1e9
+        parts[cnt:] = guard
+        sums.copy_(sums0)
+        for v in grads.values():
+            v.fill_(float("nan"))
+        assert lib.hvn_loss_forward(ctypes.byref(d), s) == 0, lib.hvn_train_last_error()
+        if backward:
+            assert lib.hvn_loss_backward(ctypes.byref(d), s) == 0, lib.hvn_train_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(parts[cnt:].view(torch.int64), guard.view(torch.int64)), "a write behind hvn_loss_partials_count doubles"
+        return sums.cpu().numpy().copy(), parts[:cnt].cpu().numpy().reshape(rows, 64).copy(), {k: v.cpu().clone() for k, v in grads.items()}
+
+    zero = torch.zeros(64, dtype=torch.float64, device="cuda")
+    sm, rows_a, grads_a = run("nan", zero)
+    assert not np.isnan(rows_a).any(), "%d partial sums have no writer" % int(np.isnan(rows_a).sum())
+    m = n * h * w
+    got = {"loss_np_bce": sm[0] / m, "loss_hv_mse": sm[2] / (2 * m), "loss_hv_msge": sm[3] / (sm[4] + 1e-8),
+           "loss_np_dice": sum(1 - (2 * sm[8 + c] + 1e-3) / (sm[10 + c] + sm[12 + c] + 1e-3) for c in range(2))}
+    if nt:
+        got["loss_tp_bce"] = sm[1] / m
+        got["loss_tp_dice"] = sum(1 - (2 * sm[16 + c] + 1e-3) / (sm[32 + c] + sm[48 + c] + 1e-3) for c in range(nt))
+    assert set(got) == set(terms)
+    for k, v in got.items():
+        assert abs(v - float(terms[k])) <= 2e-5 * max(1.0, abs(float(terms[k]))), (k, v, float(terms[k]))
+    if degenerate:
+        assert sm[4] == 0.0 and sm[3] == 0.0 and sm[12 + 1] == 0.0 and sm[48 + 3] == 0.0 and sm[16 + 3] == 0.0
+    for k in logits:
+        close(grads_a[k], lg[k].grad, 2e-4, "dlogits " + k)
+    # the documented tree, exactly
+    tree = loss_tree_cpu(rows_a)
+    assert np.array_equal(sm, tree), np.abs(sm - tree).max()
+    # += into sums that hold something, and nothing depends on what the partials held
+    s0 = torch.randn(64, dtype=torch.float64, generator=g).cuda() * 100.0 + 7.0
+    sm_b, rows_b, _ = run("garbage", s0, backward=False)
+    assert np.array_equal(rows_b, rows_a)
+    assert np.array_equal(sm_b, s0.cpu().numpy() + tree)
+    sm_c, rows_c, grads_c = run("garbage", zero)
+    assert np.array_equal(sm_c, sm) and np.array_equal(rows_c, rows_a)
+    for k in grads_a:
+        assert torch.equal(grads_c[k], grads_a[k]), k
+    # one row short: refused, sums untouched
+    d.partials_cap = cnt - 64
+    sums.copy_(s0)
+    rc = lib.hvn_loss_forward(ctypes.byref(d), s)
+    torch.cuda.synchronize()
+    assert rc == -4 and b"partials" in lib.hvn_train_last_error(), (rc, lib.hvn_train_last_error())
+    assert torch.equal(sums.view(torch.int64), s0.view(torch.int64))
 
 
 # ---------------------------------------------------------------------------------------------------
