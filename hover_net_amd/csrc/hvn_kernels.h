@@ -297,6 +297,11 @@ int hvn_launch_adam(float *w, const float *g, float *m, float *v, long n, float 
 struct hvn_op;
 int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s);
 
+// ---- validation statistics (hvn_valid.hip) ------------------------------------------------------
+size_t hvn_valid_ws_bytes(long pixels);
+int hvn_launch_valid_stats(const float *pred, const int32_t *np_map, const float *hv_map, const int32_t *tp_map, long pixels, int c, int nr_types,
+                           long long *counts, double *hv_sse, void *ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- training targets (hvn_targets.hip) ---------------------------------------------------------
 struct hvn_aug_sample;   // include/hvn.h
 int hvn_launch_aug_shape(const uint8_t *img, const int32_t *ann, int h, int w, int c, const struct hvn_aug_sample *prm, int n, int oh, int ow,

@@ -281,6 +281,30 @@ int hvn_gen_targets(const int32_t *ann, int n, int h, int w, int crop_h, int cro
     return rc == -2 ? tfail(HVN_E_LAUNCH, "gen_targets launch failed", -1) : rc;
 }
 
+static bool valid_shape_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)n * h * w <= (1LL << 36); }
+
+size_t hvn_valid_stats_workspace_bytes(int n, int h, int w) { return valid_shape_ok(n, h, w) ? hvn_valid_ws_bytes((long)n * h * w) : 0; }
+
+int hvn_valid_stats(const float *pred, const int32_t *np_map, const float *hv_map, const int32_t *tp_map, int n, int h, int w, int c,
+                    int nr_types, int64_t *counts, double *hv_sse, void *workspace, size_t workspace_bytes, void *stream)
+{
+    t_err[0] = 0;
+    if (!pred || !np_map || !hv_map || !counts || !hv_sse) return tfail(HVN_E_ARG, "valid_stats: null pointer", -1);
+    if (!valid_shape_ok(n, h, w)) return tfail(HVN_E_ARG, "valid_stats: n, h, w must be positive (at most 2^36 pixels)", -1);
+    if (c != 3 && c != 4) return tfail(HVN_E_ARG, "valid_stats: the prediction map has 3 or 4 channels", -1);
+    if (nr_types < 0 || nr_types > 16) return tfail(HVN_E_ARG, "valid_stats: nr_types must be in [0, 16]", -1);
+    if (c == 3 && (tp_map || nr_types > 0)) return tfail(HVN_E_ARG, "valid_stats: a 3-channel map has no type channel (tp_map NULL, nr_types 0)", -1);
+    if (c == 4 && (!tp_map || nr_types == 0)) return tfail(HVN_E_ARG, "valid_stats: a 4-channel map needs tp_map and nr_types > 0", -1);
+    if (!al16(pred) || (((uintptr_t)hv_map) & 7) || (((uintptr_t)np_map | (uintptr_t)tp_map) & 3) || (((uintptr_t)counts | (uintptr_t)hv_sse) & 7))
+        return tfail(HVN_E_ARG, "valid_stats: pred must be 16-byte, hv_map / counts / hv_sse 8-byte, np_map / tp_map 4-byte aligned", -1);
+    if (!workspace || workspace_bytes < hvn_valid_stats_workspace_bytes(n, h, w))
+        return tfail(HVN_E_SIZE, "valid_stats: workspace smaller than hvn_valid_stats_workspace_bytes", -1);
+    int rc = hvn_launch_valid_stats(pred, np_map, hv_map, tp_map, (long)n * h * w, c, nr_types, (long long *)counts, hv_sse, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+    if (rc == -4) return tfail(HVN_E_SIZE, "valid_stats: workspace too small", -1);
+    return rc == -2 ? tfail(HVN_E_LAUNCH, "valid_stats launch failed", -1) : rc;
+}
+
 int hvn_augment_shape(const uint8_t *img, const int32_t *ann, int n_resident, int h, int w, int c, const hvn_aug_sample *prm, int n, int out_h,
                       int out_w, uint8_t *out_img, int32_t *out_ann, void *stream)
 {

@@ -8,7 +8,8 @@ NCHW copy), the whole forward + softmax/argmax/concat epilogue is one launch pla
 the only host sync is the final D2H of the 102 KB/tile map.
 
 `train_step` / `valid_step` (run_desc.py:12-167) run the training-mode forward, the losses, the backward pass
-and the optimizer step on the HIP path (hover_net_amd.train_engine).
+and the optimizer step on the HIP path (hover_net_amd.train_engine).  `valid_step_stats` is `valid_step` with the
+epoch's statistics accumulated on the device (hover_net_amd.valid_stats) instead of raw arrays on the host.
 
 `infer_step_device` is the same step without the D2H: it returns the device tensor so
 `post_proc.process_batch_device` can run the instance separation on-GPU with no CPU
@@ -111,6 +112,17 @@ def valid_step(batch_data, run_info):
         result["raw"]["true_tp"] = torch.squeeze(batch_data["tp_map"]).type(torch.int64).cpu().numpy()
         result["raw"]["pred_tp"] = pred[..., 0].numpy().copy()
     return result
+
+
+def valid_step_stats(batch_data, run_info):
+    """`valid_step` with the statistics kept on the device: the eval-mode forward, then `run_info["valid_stats"]` (a
+    `valid_stats.ValidStats`, next to "net" in the valid engine's run_info) adds the batch to its state on the same stream --
+    no copy to the host, no sync, nothing accumulated: "raw" is empty, and `ValidStats.track()` at the end of the epoch gives
+    what `proc_valid_step_output` gives over the accumulated `valid_step` outputs (`run_engine.DeviceValidStats`)."""
+    run_info, _state_info = run_info
+    pred = infer_step_device(batch_data["img"], run_info["net"]["desc"])     # aliases an engine buffer: read before the next run
+    run_info["valid_stats"].update(pred, batch_data)
+    return {"raw": {}}
 
 
 def proc_valid_step_output(raw_data, nr_types=None):

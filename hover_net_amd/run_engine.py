@@ -152,6 +152,21 @@ class ProcessAccumulatedRawOutput(BaseCallbacks):
         state.tracked_step_output = self.proc_func(state.epoch_accumulated_output)
 
 
+class DeviceValidStats(BaseCallbacks):
+    """EPOCH_COMPLETED of a valid engine whose step is `run_desc.valid_step_stats`: in place of AccumulateRawOutput +
+    ProcessAccumulatedRawOutput.  `stats` (a `valid_stats.ValidStats`) is merged over the ranks -- a collective: every rank's valid
+    engine must reach this point once per epoch --, read once and cleared for the next epoch."""
+
+    def __init__(self, stats):
+        super().__init__()
+        self.stats = stats
+
+    def run(self, state, event):
+        self.stats.merge_ranks()
+        state.tracked_step_output = self.stats.track()
+        self.stats.reset()
+
+
 class PeriodicSaver(BaseCallbacks):
     """`{net_name}_epoch={n}.tar` = {key: value.state_dict()} for every entry of the net's run_info except extra_info
     (desc, optimizer, lr_scheduler), written by the process whose `state.logging` is set (rank 0)."""

@@ -159,11 +159,17 @@ def _same_on_all_ranks(value, what, device=None):
 
 
 def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, on_epoch=None, allow_random_frozen_encoder=False,
-               handlers=None):
+               handlers=None, device_valid=False):
     """config: get_config(...); make_loaders(phase_idx, batch_size_dict) -> {"train": iterable, "valid": iterable|None}.
     Returns the per-epoch history [{phase, epoch, lr, train: {EMA means}, valid_steps, valid: {scalars}}] and the final net.
     `handlers`: extra (event, handler) pairs for the train engine -- any object with the reference's `.run(state, event)`
-    protocol (run_utils/callbacks/*), e.g. its logging callbacks."""
+    protocol (run_utils/callbacks/*), e.g. its logging callbacks.
+    `device_valid=True`: the valid engine runs `run_desc.valid_step_stats` + `run_engine.DeviceValidStats` in place of the
+    configured valid step + AccumulateRawOutput / ProcessAccumulatedRawOutput: the statistics are accumulated on the device
+    (`valid_stats.ValidStats`), merged over the ranks and read once per epoch.  The history's `valid` entry keeps its keys and is
+    then the score of the whole validation set, identical on every rank (the default reduces what this rank's shard held).  That
+    path keeps NO raw arrays (`epoch_accumulated_output` stays empty): callbacks that draw from them, like the reference's
+    visualisation, need the default path."""
     rank, world = _dist_info()
     if device is None:                      # one process per GPU: the launcher's LOCAL_RANK names it
         device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if torch.cuda.is_available() else "cuda"
@@ -211,11 +217,18 @@ def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, 
             os.makedirs(os.path.join(log_dir, "%02d" % pi), exist_ok=True)
             train_eng.state.logging, train_eng.state.log_dir = True, os.path.join(log_dir, "%02d" % pi)
             train_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.PeriodicSaver())
-        if loaders.get("valid") is not None:
+        if loaders.get("valid") is not None and device_valid:
+            from .valid_stats import ValidStats
+
+            stats = ValidStats(net.nr_types, device)
+            valid_eng = RE.RunEngine("valid", loaders["valid"], run_desc.valid_step_stats, dict(run_info, valid_stats=stats))
+            valid_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.DeviceValidStats(stats))
+        elif loaders.get("valid") is not None:
             valid_eng = RE.RunEngine("valid", loaders["valid"], step_fns.get("valid", {}).get("run_step", run_desc.valid_step), run_info)
             valid_eng.add_event_handler(RE.Events.STEP_COMPLETED, RE.AccumulateRawOutput())
             valid_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.ProcessAccumulatedRawOutput(
                 lambda raw: run_desc.proc_valid_step_output(raw, nr_types=net.nr_types)))
+        if valid_eng is not None:
             trig = RE.TriggerEngine("valid")
             trig.triggered_engine = valid_eng
             train_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, trig)

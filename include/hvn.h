@@ -312,6 +312,21 @@ HVN_API int64_t hvn_loss_partials_count(int n, int h, int w);
 HVN_API int hvn_loss_forward(const hvn_loss *l, void *stream);
 HVN_API int hvn_loss_backward(const hvn_loss *l, void *stream);
 
+/* Validation statistics: the scalar half of run_desc.py:262-333 proc_valid_step_output, accumulated on the device (added to the ABI
+ * without a version step: hvn_version() stays 104, the binding resolves every export by name at load time).
+ * pred: dev float32 [n][h][w][c], c = 3 | 4 = [type?, p_nuc, h, v] as PREDMAP writes it (16-byte aligned, read in place); np_map: dev
+ * int32 [n][h][w]; hv_map: dev float32 [n][h][w][2]; tp_map: dev int32 [n][h][w] with c = 4 and 0 < nr_types <= 16, NULL with c = 3 and
+ * nr_types = 0 (anything else is refused).  The call ADDS this batch to the caller's state, in stream order and with no host sync:
+ *   counts: dev int64 [4 + 2 * nr_types] = pixels, np_correct (count of (p_nuc > 0.5) == np_map; exactly 0.5 and NaN are not nucleus),
+ *           np_inter, np_total for label 1 (total = count(true == 1) + count(pred == 1)), then (tp_inter_t, tp_total_t) for t = 0 ..
+ *           nr_types - 1: the float type channel compared to the integer label; a label no t equals is counted by nobody;
+ *   hv_sse: dev float64 [1] += sum over both HV channels of (double(pred) - double(true))^2, each term a rounded product.
+ * The counts are exact integers; the float64 sum is a fixed function of the inputs and the call sequence (a fixed tree per workgroup,
+ * one partial per workgroup of 1024 pixels stored to the workspace, added in workgroup order; no atomics). */
+HVN_API size_t hvn_valid_stats_workspace_bytes(int n, int h, int w);
+HVN_API int hvn_valid_stats(const float *pred, const int32_t *np_map, const float *hv_map, const int32_t *tp_map, int n, int h, int w, int c,
+                            int nr_types, int64_t *counts, double *hv_sse, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Training targets: models/hovernet/targets.py:100-116 gen_targets (gen_instance_hv_map :17-96 with fix_mirror_padding,
  * remove_small_objects(30) on the crop, the unclamped 2-px box widening and its skip-at-the-near-border consequence).
  * ann: dev int32 [n][h][w] instance ids (0 = background); hv_map: dev float32 [n][crop_h][crop_w][2] = (x, y) offsets in
