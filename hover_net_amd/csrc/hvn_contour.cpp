@@ -15,7 +15,9 @@
 // Only the candidate for [0] keeps its points; hole borders and nested pieces are followed for their marks only.
 // OpenCV is not on the build box.  Pinned by tests/golden/proc_*.npz: the reference's own process() run over an
 // independently written python restatement of the same algorithm (oracle/cv2_shim/_suzuki.py).
-// O(crop area) per instance, so it stays on the host.
+// O(crop area) per instance and valid for ANY label map (several pieces per label, pieces inside holes).  For maps whose labels are
+// one 8-connected piece each -- the instance separation's output -- hvn_contour_dev.hip traces the same points on the device in
+// O(perimeter) steps; this file is the tracer that one is tested against, and the default.
 #include <stdint.h>
 #include <stdlib.h>
 

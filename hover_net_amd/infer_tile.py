@@ -291,13 +291,17 @@ def gather_items_to_rank0(mine, dst=0, device=None):
     return out
 
 
-def result_to_arrays(inst_h, rec_h, nr_types):
+def result_to_arrays(inst_h, rec_h, nr_types, contours_flat=None):
     """One image's / tile's finished result as arrays: instance map, record table, contour points + offsets (traced HERE, on
-    the rank that owns the item, so the host work is spread over the ranks)."""
+    the rank that owns the item, so the host work is spread over the ranks -- or handed in as `contours_flat` = (pts, offs)
+    when the owner traced them on its GPU)."""
     from . import post_proc
 
     rec_h = np.ascontiguousarray(rec_h)
-    pts, offs = post_proc.trace_contours_flat(inst_h, rec_h) if rec_h.size else (np.zeros((0, 2), np.int32), np.zeros(1, np.int64))
+    if contours_flat is not None:
+        pts, offs = contours_flat
+    else:
+        pts, offs = post_proc.trace_contours_flat(inst_h, rec_h) if rec_h.size else (np.zeros((0, 2), np.int32), np.zeros(1, np.int64))
     return [np.ascontiguousarray(inst_h, np.int32), rec_h.view(np.uint8).reshape(rec_h.shape[0], rec_h.dtype.itemsize), pts, offs]
 
 

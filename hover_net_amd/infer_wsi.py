@@ -438,7 +438,13 @@ class DeviceMerger:
 # --------------------------------------------------------------------------------------------
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
-                 patch_input_shape=None, patch_output_shape=None):
+                 patch_input_shape=None, patch_output_shape=None, device_contours=False):
+        """device_contours=True: stage 2 traces every tile's contours on the GPU (`PostProc.contours`, same arrays as the host
+        tracer) on the tile's post-processing stream instead of on the host worker thread.  The tile's instance map still goes
+        to the host, and the whole `pts` buffer at its default capacity (a quarter of the tile's pixels: 8 MB for a 2048 x 2048
+        tile, a fifth of it used) is copied with it, because the total is not known on the host when the copy is enqueued: 50 %
+        more D2H bytes per tile than the default path, and each pinned slot grows by that buffer."""
+        self.device_contours = bool(device_contours)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
         pin = patch_input_shape or (270 if net.mode == "original" else 256)     # run_infer.py:145-150
@@ -542,7 +548,7 @@ class WsiInference:
         `pred_map`: the whole map (tensor) or this rank's `SlabMap`; a tile is worked by the rank owning its top row.
         Three overlapped stages per rank: (a) the GPU instance separation + instance table of tile i+1 and its D2H into pinned
         memory are in flight (`_launch_tile`) while (b) a worker thread traces the contours of tile i on the host cores
-        (C++, multi-threaded, no GIL) and (c) the caller merges tile i-1.  One rank: results are yielded as they complete, so
+        (C++, multi-threaded, no GIL; with `device_contours` they were traced in (a) and the thread only assembles) and (c) the caller merges tile i-1.  One rank: results are yielded as they complete, so
         the sequential merge runs under the GPU work of later tiles.  Several ranks: every rank
         runs the same pipeline over the tiles whose rows it holds, then instance maps / record tables / contour arrays travel to rank 0 as
         tensors (`infer_tile.gather_items_to_rank0`) and rank 0 assembles the dicts."""
@@ -560,9 +566,9 @@ class WsiInference:
         def shift_of(i):
             return (int(tiles[i][0][1]), int(tiles[i][0][0]))      # tile origin as (x, y)
 
-        def host_half(i, inst_h, rec_h, release):
+        def host_half(i, inst_h, rec_h, release, flat):
             t0 = time.perf_counter()
-            arrs = infer_tile.result_to_arrays(inst_h, rec_h, self.nr_types)
+            arrs = infer_tile.result_to_arrays(inst_h, rec_h, self.nr_types, contours_flat=flat)   # flat: traced on the GPU, or None
             t1 = time.perf_counter()
             out = infer_tile.arrays_to_result(arrs, self.nr_types, shift_xy=shift_of(i)) if world == 1 else [np.array(a) for a in arrs]
             release()
@@ -585,11 +591,11 @@ class WsiInference:
 
             def finish():
                 i, wait = inflight.popleft()
-                inst_h, rec_h, release = wait()
+                inst_h, rec_h, release, flat = wait()
                 if world == 1 and hasattr(wait, "device_result"):
                     nz = np.flatnonzero(rec_h["area"]) if rec_h.size else np.zeros(0, np.int64)
                     self._dev_results[i] = wait.device_result + (int(nz[-1]) + 1 if nz.size else 0,)      # + the tile's largest label
-                futs.append((i, pool.submit(host_half, i, inst_h, rec_h, release)))
+                futs.append((i, pool.submit(host_half, i, inst_h, rec_h, release, flat)))
 
             for i in idxs:
                 tl, br = tiles[i][0], tiles[i][1]
@@ -607,12 +613,13 @@ class WsiInference:
                     yield (i,) + infer_tile.arrays_to_result(every[i], self.nr_types, shift_xy=shift_of(i))
 
     def _launch_tile(self, tile_map):
-        """Start the GPU half of one tile; returns wait() -> (int32 instance map, record table, release) on the host.  CUDA:
-        kernels + D2H into a pinned slot are enqueued and wait() blocks on the slot's event; `release()` frees the slot once
-        the host half is done with the arrays (they alias pinned memory)."""
+        """Start the GPU half of one tile; returns wait() -> (int32 instance map, record table, release, contours) on the host.
+        CUDA: kernels + D2H into a pinned slot are enqueued and wait() blocks on the slot's event; `release()` frees the slot
+        once the host half is done with the arrays (they alias pinned memory).  contours: None (the host half traces them), or
+        with `device_contours` the (pts, offs) arrays traced on this tile's stream."""
         if self.device.type != "cuda":
             inst_h, rec_h = self._postproc_tile(tile_map)
-            return lambda: (inst_h, rec_h, lambda: None)
+            return lambda: (inst_h, rec_h, lambda: None, None)
         t0 = time.perf_counter()
         # tiles alternate between a few post-processing lanes (own stream + own workspace): one tile's ~30 launches over 4-5
         # Mpixel leave most of the chip idle, two or three tiles in flight fill it
@@ -632,6 +639,12 @@ class WsiInference:
             slot = self._pinned_slot(inst[0].shape, rec[0].shape)
             slot["inst"].copy_(inst[0], non_blocking=True)
             slot["rec"].copy_(rec[0], non_blocking=True)
+            if self.device_contours:
+                cont = pp.contours(inst, rec)
+                for k, t in zip(("pts", "offs", "cstatus"), cont):
+                    if k not in slot:
+                        slot[k] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                    slot[k].copy_(t, non_blocking=True)
             slot["event"].record(stream)
         tm = getattr(self, "timing", None)
 
@@ -639,14 +652,22 @@ class WsiInference:
             slot["event"].synchronize()
             if tm is not None:
                 tm["gpu_launch_to_ready_s"] = tm.get("gpu_launch_to_ready_s", 0.0) + (time.perf_counter() - t0)
-            return slot["inst"].numpy(), slot["rec"].numpy().view(post_proc._REC_DTYPE).reshape(-1), slot["free"].set
+            flat = None
+            if self.device_contours:
+                pts, offs = slot["pts"].numpy(), slot["offs"].numpy()
+                if post_proc.check_contour_status(slot["cstatus"].numpy(), rec.shape[1]):    # more points than the default capacity
+                    with torch.cuda.stream(stream):
+                        pts = pp.contours(inst, rec, int(offs[-1]))[0].cpu().numpy()
+                flat = (pts[:int(offs[-1])], offs)
+            return slot["inst"].numpy(), slot["rec"].numpy().view(post_proc._REC_DTYPE).reshape(-1), slot["free"].set, flat
 
         wait.device_result = (inst[0], slot["event"])              # for the on-device merge: the local-id map stays in HBM
         return wait
 
     def _pinned_slot(self, inst_shape, rec_shape):
         """A free pinned (instance map, record table) pair for this tile shape; six per shape, waiting for the oldest when
-        all are in use (hipHostMalloc is slow, so the slots are kept)."""
+        all are in use (hipHostMalloc is slow, so the slots are kept).  With `device_contours` the slot also holds the tile's
+        contour points and offsets (and the tracer's status words), added by `_launch_tile`."""
         import threading
 
         pools = self.__dict__.setdefault("_slots", {})

@@ -14,10 +14,20 @@ from . import post_proc, run_desc
 
 
 class TilePipeline:
-    def __init__(self, model, nr_types=None, return_centroids=True, device=None):
+    def __init__(self, model, nr_types=None, return_centroids=True, device=None, contours=False, contour_max_pts=None):
+        """contours=True: every batch's contours are traced on the side stream too (`PostProc.contours`; the instance
+        separation's labels are one piece each, which is what the device tracer needs) and `submit` returns
+        (inst, records, counts, pts, offs, status).  contour_max_pts: capacity of `pts` per batch (default: a quarter of the
+        batch's pixels); a batch that needs more is traced again with the exact size in `wait()`.  With to_host=True the whole
+        `pts` buffer is copied at that capacity (2 bytes per pixel by default), whatever part of it the batch's points fill."""
         self.model = model
         self.nr_types = nr_types
         self.return_centroids = return_centroids
+        self.contours = bool(contours)
+        self.contour_max_pts = contour_max_pts
+        if self.contours and not (return_centroids or nr_types is not None):
+            raise ValueError("contours=True needs the record table (return_centroids or nr_types)")
+        self._pending = []                           # contours=True: (device result, returned result) of the batches since the last wait()
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.device = torch.device(device) if device is not None else next(net.parameters()).device
         self.side = torch.cuda.Stream(self.device)
@@ -44,7 +54,11 @@ class TilePipeline:
         path hands `infer_tile.gather_to_rank0` here, so the RCCL gather overlaps the next network
         pass too).  `to_host=True`: the results are copied to pinned host memory on the side stream
         (the reference's contract ends on the host: infer/tile.py:308-316); the returned tensors are
-        then the pinned buffers of this slot, overwritten two submits later."""
+        then the pinned buffers of this slot, overwritten two submits later.
+        With contours=True the tuple is (inst, records, counts, pts, offs, status); `status` is checked in `wait()`, not here:
+        `submit` never waits on the host."""
+        if self.contours and gather is not None:
+            raise ValueError("contours=True does not go through a gather: the multi-GPU paths carry host contour arrays")
         main = torch.cuda.current_stream(self.device)
         k = self._n & 1
         self._n += 1
@@ -74,8 +88,11 @@ class TilePipeline:
                 if self.time_gather:
                     g1.record(self.side)
                     self.gather_events.append((g0, g1))
+            dev = out
             if to_host and out is not None:
                 out = self._to_host(out, k)
+            if self.contours:
+                self._pending.append((dev, out))
             self._free[k] = torch.cuda.Event()
             self._free[k].record(self.side)
         self._last = out
@@ -100,6 +117,8 @@ class TilePipeline:
         inst = self._pp.separate(maps)
         if self.return_centroids or self.nr_types is not None:
             rec, counts = self._pp.table(inst, maps, self.nr_types)
+            if self.contours:
+                return (inst, rec, counts) + self._pp.contours(inst, rec, self.contour_max_pts)
             return inst, rec, counts
         return inst, None, None
 
@@ -130,4 +149,28 @@ class TilePipeline:
 
     def wait(self):
         self.side.synchronize()
+        if self._pending:
+            self._check_contours()
         return self._last
+
+    def _check_contours(self):
+        """contours=True: the status words of the batches since the last wait().  A flagged record raises; a batch whose points
+        did not fit is traced again with the exact size, and the new points replace the old IN the tensors `submit` returned.
+        Status and total are read from each batch's own device tensors, never from the pinned buffers: with to_host=True a
+        slot's pinned buffers hold only the NEWEST batch submitted to that slot, so an older batch of the slot is checked for
+        flags only (its host copy is gone, as `submit` says) and only the newest one is traced again and copied."""
+        pending, self._pending = self._pending, []
+        newest = {id(out[3]): i for i, (dev, out) in enumerate(pending) if out is not dev}   # per pinned buffer
+        with torch.cuda.stream(self.side):
+            status = torch.stack([dev[5] for dev, _ in pending]).cpu().numpy()
+            totals = torch.stack([dev[4][-1] for dev, _ in pending]).cpu().tolist()
+        for i, (dev, out) in enumerate(pending):
+            if not post_proc.check_contour_status(status[i], dev[1].shape[1]):
+                continue
+            if out is not dev and newest[id(out[3])] != i:
+                continue
+            with torch.cuda.stream(self.side):
+                pts, offs, st = self._pp.contours(dev[0], dev[1], int(totals[i]))
+                for old, new in ((dev[3], pts), (dev[5], st)) + (((out[3], pts), (out[5], st)) if out is not dev else ()):
+                    old.resize_(new.shape).copy_(new)    # offs is exact already
+                self.side.synchronize()

@@ -6,13 +6,17 @@
   host map; it is a thin wrapper over the batched device path.
 * `process_batch_device(pred_dev, nr_types)` is the north-star path: `[N,h,w,3|4]` float32
   maps already in HBM (straight from `run_desc.infer_step_device`) -> int32 instance maps
-  and the per-instance table in HBM, no CPU round trip per tile.
+  and the per-instance table in HBM, no CPU round trip per tile; `return_contours=True` adds the
+  contours, traced in HBM too.
 
 Instance separation (`__proc_np_hv`, post_proc.py:26-90) and the array half of the
 per-instance loop (bbox / centroid / type vote, post_proc.py:119-181) are HIP kernels in
-libhvn_hip.so.  Contour tracing (`cv2.findContours`, post_proc.py:132-135) is an O(perimeter) host
-routine of the same library over each instance's bbox crop (csrc/hvn_contour.cpp).  No CPU fallback
-exists for the GPU stages.
+libhvn_hip.so.  Contour tracing (`cv2.findContours`, post_proc.py:132-135) has two forms in the same
+library with bit-equal results: the host routine over each instance's bbox crop (csrc/hvn_contour.cpp,
+any label map; the default everywhere) and, opt-in, a mark-free border walk on the device
+(csrc/hvn_contour_dev.hip: `PostProc.contours`, `trace_contours_device`, `process(contours="device")`)
+for maps in which every label is one 8-connected piece -- which the instance separation's output is.
+No CPU fallback exists for the GPU stages.
 """
 import ctypes
 
@@ -30,6 +34,8 @@ class PostProc:
         self.device = torch.device(device)
         self._ws = None
         self._tws = None
+        self._cws = None
+        self._cpin = None
 
     def _workspace(self, n, h, w):
         need = L.lib().hvn_postproc_workspace_bytes(n, h, w)
@@ -89,6 +95,41 @@ class PostProc:
                                            self._tws.numel(), stream), "hvn_instance_table")
         return rec, counts
 
+    def contours(self, inst, rec, max_pts=None):
+        """contours[0] of every record, traced on the device (hvn_trace_contours_device) on the current stream, no host sync.
+        inst: int32 device tensor [N,h,w]; rec: `table`'s records [N,max_inst,sizeof(rec)].  PRECONDITION: every label of `inst`
+        is one 8-connected piece (true of `separate`'s output); other maps go to `trace_contours_flat`.
+        -> (pts int32 [max_pts,2] of (x, y), offs int64 [N*max_inst+1], status int32 [4]) on the device: the record at
+        (map i, slot j) owns pts[offs[i*max_inst+j]:offs[i*max_inst+j+1]]; status = (flagged records -- they own no points --,
+        1 if offs[-1] > max_pts: the records beyond max_pts were not written, smallest flagged i*max_inst+j or -1, 0).
+        max_pts defaults to N*h*w // 4 (2 bytes per pixel; dense noise blobs need 0.14 points per pixel)."""
+        assert inst.dtype == torch.int32 and inst.dim() == 3 and inst.is_cuda and rec.dtype == torch.uint8 and rec.dim() == 3 and rec.is_cuda
+        inst, rec = inst.contiguous(), rec.contiguous()
+        n, h, w = inst.shape
+        max_inst = rec.shape[1]
+        if rec.shape[0] != n or rec.shape[2] != ctypes.sizeof(L.hvn_inst_rec):
+            raise ValueError("record table %s does not belong to %d maps" % (tuple(rec.shape), n))
+        if max_pts is None:
+            max_pts = n * h * w // 4
+        max_pts = max(int(max_pts), 0)
+        need = L.lib().hvn_contours_workspace_bytes(n, max_inst)
+        if self._cws is None or self._cws.numel() < need:
+            self._cws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        pts = torch.empty((max_pts, 2), dtype=torch.int32, device=self.device)
+        offs = torch.empty((n * max_inst + 1,), dtype=torch.int64, device=self.device)
+        status = torch.empty((4,), dtype=torch.int32, device=self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hvn_trace_contours_device(inst.data_ptr(), n, h, w, rec.data_ptr(), max_inst, pts.data_ptr() if max_pts else None,
+                                                  max_pts, offs.data_ptr(), status.data_ptr(), self._cws.data_ptr(), self._cws.numel(),
+                                                  stream), "hvn_trace_contours_device")
+        return pts, offs, status
+
+    def _pinned(self, like):
+        """Pinned host buffers for `contours`' three outputs (kept: pinned allocations are slow)."""
+        if self._cpin is None or any(b.numel() < t.numel() for b, t in zip(self._cpin, like)):
+            self._cpin = tuple(torch.empty(t.numel(), dtype=t.dtype, pin_memory=True) for t in like)
+        return tuple(b[:t.numel()].view(t.shape) for b, t in zip(self._cpin, like))
+
 
 _REC_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("rmin", "<i4"), ("rmax", "<i4"), ("cmin", "<i4"), ("cmax", "<i4"),
                        ("sum_x", "<f8"), ("sum_y", "<f8"), ("type", "<i4"), ("type_count", "<i4")])
@@ -104,15 +145,60 @@ def _pp(device):
     return _DEFAULT[key]
 
 
-def process_batch_device(pred_dev, nr_types=None, return_centroids=False):
+def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False):
     """pred_dev [N,h,w,3|4] float32 on the GPU -> (inst int32 [N,h,w] device tensor,
-    records device tensor | None, counts device tensor | None)."""
+    records device tensor | None, counts device tensor | None); with return_contours=True the tuple gains
+    `PostProc.contours`' (pts, offs, status) device tensors (None each when there is no record table)."""
     pp = _pp(pred_dev.device)
     inst = pp.separate(pred_dev)
+    out = (inst, None, None)
     if return_centroids or nr_types is not None:
-        rec, counts = pp.table(inst, pred_dev.contiguous(), nr_types)
-        return inst, rec, counts
-    return inst, None, None
+        out = (inst,) + pp.table(inst, pred_dev.contiguous(), nr_types)
+    if return_contours:
+        out += pp.contours(inst, out[1]) if out[1] is not None else (None, None, None)
+    return out
+
+
+def split_contours(pts, offs, n, max_inst):
+    """Host arrays of `PostProc.contours` -> one (pts [P,2], offs int64 [max_inst+1]) per map, trace_contours_flat's form."""
+    out = []
+    for i in range(n):
+        o = offs[i * max_inst:(i + 1) * max_inst + 1]
+        out.append((pts[int(o[0]):int(o[-1])].copy(), o - o[0]))
+    return out
+
+
+def check_contour_status(status, max_inst):
+    """Raises for flagged records (status of `PostProc.contours` on the host); -> True when the points did not fit."""
+    if int(status[0]):
+        i, j = divmod(int(status[2]), max_inst)
+        raise L.HvnError("hvn_trace_contours_device: %d record(s) could not be traced, the first in map %d, label %d: the device "
+                         "tracer needs every label to be one 8-connected piece and a record table made from this map "
+                         "(trace_contours_flat handles arbitrary maps)" % (int(status[0]), i, j + 1))
+    return bool(int(status[1]))
+
+
+def trace_contours_device(inst_dev, rec_dev):
+    """Device counterpart of `trace_contours_flat` for a batch: inst_dev int32 [N,h,w] and rec_dev (`PostProc.table`'s records)
+    on the GPU -> a list with one host (pts int32 [P,2], offs int64 [max_inst+1]) per map, exactly what
+    trace_contours_flat(inst_host[i], rec_host[i]) returns.  PRECONDITION: every label is one 8-connected piece (the output
+    of the instance separation is); a record the device cannot trace raises HvnError naming its map and label.  One host
+    synchronisation (a second one in the rare case that the points exceed the default capacity).  The D2H is enqueued before
+    the total is known, so it copies `pts` at its whole capacity (N*h*w // 4 points, 2 bytes per pixel), not only the points traced."""
+    L.require_gpu()
+    pp = _pp(inst_dev.device)
+    n, max_inst = rec_dev.shape[0], rec_dev.shape[1]
+    max_pts = None
+    while True:
+        dev = pp.contours(inst_dev, rec_dev, max_pts)
+        host = pp._pinned(dev)
+        for b, t in zip(host, dev):
+            b.copy_(t, non_blocking=True)
+        torch.cuda.current_stream(pp.device).synchronize()
+        pts, offs, status = (b.numpy() for b in host)
+        if not check_contour_status(status, max_inst):
+            return split_contours(pts, offs.copy(), n, max_inst)
+        max_pts = int(offs[-1])
 
 
 def trace_contours_flat(inst_host, rec_host):
@@ -181,12 +267,16 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
     return out
 
 
-def process(pred_map, nr_types=None, return_centroids=False):
-    """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32."""
+def process(pred_map, nr_types=None, return_centroids=False, contours="host"):
+    """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32.  contours="device" traces the contours on
+    the GPU (`trace_contours_device`) instead of on the host; the result is the same."""
+    if contours not in ("host", "device"):
+        raise ValueError('contours must be "host" or "device", got %r' % (contours,))
     pred = torch.from_numpy(np.ascontiguousarray(pred_map, np.float32)).unsqueeze(0).to("cuda")
     inst, rec, _ = process_batch_device(pred, nr_types, return_centroids)
+    flat = trace_contours_device(inst, rec)[0] if rec is not None and contours == "device" else None
     pred_inst = inst[0].cpu().numpy()
     info = None
     if rec is not None:
-        info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst)
+        info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat)
     return pred_inst, info

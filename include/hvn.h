@@ -211,6 +211,23 @@ HVN_API int hvn_wsi_merge_fixing(int32_t *inst_map, int64_t map_w, int y0, int x
  * offs = host int64 [n_rec + 1] prefix offsets into pts.  Returns the total number of points or <0. */
 HVN_API long hvn_trace_contours(const int32_t *inst, int h, int w, const hvn_inst_rec *recs, int n_rec,
                                 int32_t *pts, long max_pts, int64_t *offs);
+/* DEVICE function, the batched form of the same arrays for maps in which EVERY LABEL IS ONE 8-CONNECTED PIECE (hvn_postproc's
+ * output is; arbitrary maps go to hvn_trace_contours): then contours[0] is the outer border from the label's first raster pixel,
+ * traced without marks in O(perimeter) steps, bit-equal to the host function (csrc/hvn_contour_dev.hip).  All pointers are device
+ * pointers; everything is enqueued on `stream`, nothing is allocated or synchronised.  inst: int32 [n][h][w] (not written);
+ * records: hvn_instance_table's [n][max_inst].  pts: int32 [max_pts][2] as (x, y) in map coordinates, 8-byte aligned;
+ * offs: int64 [n * max_inst + 1]: the record at (map i, slot j) owns pts[offs[i * max_inst + j] : offs[i * max_inst + j + 1]],
+ * slots in (map, slot) order (a prefix sum over the per-slot counts: the layout is a function of the input alone).
+ * A record with area > 0 is FLAGGED and owns no points when its bbox is empty or leaves the map, row rmin holds no pixel of the
+ * label inside the bbox, the walk exceeds 4 * area + 8 steps, or the walk's bounding box differs from the record's (a label of
+ * several pieces -- unless a further piece lies inside the first piece's bbox, which is NOT detected -- or a stale table).
+ * status: int32 [4] = { flagged records, 1 if offs[n * max_inst] > max_pts, smallest flagged i * max_inst + j or -1, 0 }.
+ * offs is exact for all unflagged records even when status[1] is set; then the records whose range does not fit in max_pts are
+ * not written and the caller sizes a second call from offs[n * max_inst]. */
+HVN_API size_t hvn_contours_workspace_bytes(int n, int max_inst);
+HVN_API int hvn_trace_contours_device(const int32_t *inst, int n, int h, int w, const hvn_inst_rec *records, int max_inst,
+                                      int32_t *pts, int64_t max_pts, int64_t *offs, int32_t *status, void *workspace,
+                                      size_t workspace_bytes, void *stream);
 
 
 /* -- training step: run_desc.py:12-109 train_step (forward in train() mode, losses utils.py:54-172, backward, Adam) --
