@@ -145,7 +145,8 @@ class InferManager:
 
     def process_file_list(self, run_args):
         """run_args (run_infer.py:134-172): input_dir, output_dir, batch_size, mem_usage, draw_dot, save_qupath, save_raw_map,
-        patch_input_shape, patch_output_shape (+ nr_inference_workers, nr_post_proc_workers: ignored).
+        patch_input_shape, patch_output_shape (+ nr_inference_workers, nr_post_proc_workers: ignored); device_overlay (default
+        False): rank 0 draws `overlay/` on the GPU (`viz.visualize_instances_dict(device=...)`, the same pixels).
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
@@ -158,6 +159,7 @@ class InferManager:
         draw_dot = bool(run_args.get("draw_dot", False))
         save_qupath = bool(run_args.get("save_qupath", False))
         save_raw_map = bool(run_args.get("save_raw_map", False))
+        overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
         assert (win, msk) == ((270, 80) if self.mode == "original" else (256, 164)), "patch shapes are fixed by the model mode"
@@ -192,7 +194,7 @@ class InferManager:
                 name = pathlib.Path(path).stem
                 pred_inst, inst_info = res[0], res[1]
                 raw_map = res[2] if save_raw_map else None
-                self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath)
+                self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
                 done.append(name)
         return done
 
@@ -203,12 +205,13 @@ class InferManager:
         except (AttributeError, StopIteration, TypeError):
             return None
 
-    def _write(self, output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath):
-        """proc_callback, infer/tile.py:169-208."""
+    def _write(self, output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=None):
+        """proc_callback, infer/tile.py:169-208.  `overlay_device`: None = the host overlay writer, a device = the same pixels drawn there."""
         import scipy.io as sio
 
         sio.savemat("%s/mat/%s.mat" % (output_dir, name), mat_dict(pred_inst, inst_info, self.nr_types, raw_map))
-        overlay = viz.visualize_instances_dict(img, inst_info, draw_dot=draw_dot, type_colour=self.type_info_dict, line_thickness=2)
+        overlay = viz.visualize_instances_dict(img, inst_info, draw_dot=draw_dot, type_colour=self.type_info_dict, line_thickness=2,
+                                               device=overlay_device)
         viz.save_png("%s/overlay/%s.png" % (output_dir, name), overlay)
         if save_qupath:
             vals = list(inst_info.values())

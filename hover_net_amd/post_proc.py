@@ -148,7 +148,8 @@ def _pp(device):
 def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False):
     """pred_dev [N,h,w,3|4] float32 on the GPU -> (inst int32 [N,h,w] device tensor,
     records device tensor | None, counts device tensor | None); with return_contours=True the tuple gains
-    `PostProc.contours`' (pts, offs, status) device tensors (None each when there is no record table)."""
+    `PostProc.contours`' (pts, offs, status) device tensors (None each when there is no record table); records, pts and offs
+    in that form are what `viz.overlay_from_records` draws without leaving the device."""
     pp = _pp(pred_dev.device)
     inst = pp.separate(pred_dev)
     out = (inst, None, None)

@@ -1,7 +1,11 @@
 """Overlay writer of the tile manager (`misc/viz_utils.py:94-125` `visualize_instances_dict`): contours of every instance in
 its type colour (or a random colour without a type table) and an optional centroid dot, drawn into a copy of the image.
 Host glue behind the hot path; numpy only (cv2 is absent from this image), so the line rasterisation follows
-`cv2.drawContours(thickness=2)` in intent -- closed polygon through the contour vertices, 2 px wide -- not bit for bit."""
+`cv2.drawContours(thickness=2)` in intent -- closed polygon through the contour vertices, 2 px wide -- not bit for bit.
+
+The host functions below are the default and the DEFINITION of the result.  Opt-in, the same pixels are drawn on the GPU
+(csrc/hvn_overlay.hip, `hvn_draw_overlay`): `draw_overlay_device` on flat device arrays, `overlay_from_records` straight from
+`post_proc.process_batch_device(..., return_contours=True)`, and `visualize_instances_dict(..., device="cuda")` for a dict."""
 import colorsys
 import random
 import struct
@@ -58,20 +62,170 @@ def draw_centroid_dot(img, centre, radius=3, colour=(255, 0, 0)):
     return img
 
 
-def visualize_instances_dict(input_image, inst_dict, draw_dot=False, type_colour=None, line_thickness=2):  # noqa: A002
-    """Same signature as misc/viz_utils.py:94-96.  `type_colour`: {type_id: (name, (r, g, b))}."""
-    overlay = np.array(input_image, copy=True)
+def _resolve_colours(inst_dict, type_colour):
+    """The colour of every entry, chosen the way misc/viz_utils.py:100-113 does (one `random_colors` call, consumed or not)."""
     rng_colours = (np.array(random_colors(len(inst_dict))) * 255).astype(np.uint8) if len(inst_dict) else np.zeros((0, 3), np.uint8)
+    out = []
     for idx, (_inst_id, info) in enumerate(inst_dict.items()):
         if "type" in info and type_colour is not None and info["type"] in type_colour:
-            colour = type_colour[info["type"]][1]
+            out.append(type_colour[info["type"]][1])
         else:
-            colour = rng_colours[idx].tolist()
+            out.append(rng_colours[idx].tolist())
+    return out
+
+
+def visualize_instances_dict(input_image, inst_dict, draw_dot=False, type_colour=None, line_thickness=2, *, device=None):  # noqa: A002
+    """Same signature as misc/viz_utils.py:94-96.  `type_colour`: {type_id: (name, (r, g, b))}.
+    `device` (keyword only): None draws on the host; a torch device draws the same pixels there (`draw_overlay_device`) --
+    the colours are resolved on the host first, consuming python's `random` stream identically."""
+    if device is not None:
+        return _visualize_on_device(input_image, inst_dict, draw_dot, type_colour, line_thickness, device)
+    overlay = np.array(input_image, copy=True)
+    for (_inst_id, info), colour in zip(inst_dict.items(), _resolve_colours(inst_dict, type_colour)):
         if info.get("contour") is not None:
             draw_contour(overlay, info["contour"], colour, line_thickness)
         if draw_dot:
             draw_centroid_dot(overlay, info["centroid"])
     return overlay
+
+
+# ---- the device route ------------------------------------------------------------------------------
+_I32 = np.iinfo(np.int32)
+
+
+def flatten_instances(inst_dict, colours):
+    """dict -> `hvn_draw_overlay`'s flat host arrays, one slot per entry in dict order: (pts int32 [P,2] of (x, y),
+    offs int64 [len+1], rgba uint8 [len,4] with draw flag 1, centres int32 [len,2]).  A `None` (or empty) contour owns no points;
+    its slot still draws its dot.  Contours are converted the way `draw_contour` does (int64, reshape(-1, 2)), centres the way
+    `draw_centroid_dot` does (`int()`: truncation); a contour vertex beyond int32 raises ValueError, a centre is clamped (it is
+    outside every image either way)."""
+    n = len(inst_dict)
+    chunks, offs = [], np.zeros(n + 1, np.int64)
+    rgba = np.zeros((n, 4), np.uint8)
+    centres = np.zeros((n, 2), np.int32)
+    for i, ((_inst_id, info), colour) in enumerate(zip(inst_dict.items(), colours)):
+        c = np.zeros((0, 2), np.int64) if info.get("contour") is None else np.asarray(info["contour"], np.int64).reshape(-1, 2)
+        if c.size and (c.min() < _I32.min or c.max() > _I32.max):
+            raise ValueError("contour vertex outside the int32 range")
+        chunks.append(c.astype(np.int32))
+        offs[i + 1] = offs[i] + c.shape[0]
+        rgba[i, :3] = np.asarray(colour, np.uint8)
+        rgba[i, 3] = 1
+        centres[i] = [min(max(int(info["centroid"][k]), _I32.min), _I32.max) for k in (0, 1)]
+    pts = np.concatenate(chunks, 0) if chunks else np.zeros((0, 2), np.int32)
+    return np.ascontiguousarray(pts, np.int32), offs, rgba, centres
+
+
+def unflatten_instances(pts, offs, rgba, centres):
+    """Inverse of `flatten_instances`, as a list in slot order: (contour int32 [K,2], (r, g, b), (cx, cy))."""
+    return [(pts[int(offs[i]):int(offs[i + 1])], tuple(int(v) for v in rgba[i, :3]), (int(centres[i, 0]), int(centres[i, 1])))
+            for i in range(len(offs) - 1)]
+
+
+def _check_draw_args(thickness, dot_radius):
+    if int(thickness) != thickness or not 1 <= thickness <= 7:
+        raise ValueError("thickness must be an integer in 1..7, got %r" % (thickness,))
+    if int(dot_radius) != dot_radius or not 0 <= dot_radius <= 15:
+        raise ValueError("dot_radius must be an integer in 0..15, got %r" % (dot_radius,))
+
+
+_WORKSPACE = {}
+
+
+def draw_overlay_device(images, pts, offs, rgba, centres=None, *, thickness=2, dot_radius=3, dot_colour=(255, 0, 0), out=None,
+                        return_status=False):
+    """`hvn_draw_overlay` on the current stream, no host sync: device tensors in, uint8 device tensor [n,h,w,3] out.
+    images uint8 [n,h,w,3]; pts int32 [P,2] of (x, y); offs int64 [n*slots+1] and rgba uint8 [n*slots,4] (r, g, b, draw flag) in
+    `PostProc.contours`' (image, slot) layout; centres int32 [n*slots,2] or None (no dots).  `out` may be `images` (in place).
+    return_status=True -> (overlay, status int32 [4] on the device = (slots with a bad offs range -- they draw nothing --,
+    the first of them or -1, 0, 0))."""
+    import ctypes
+
+    import torch
+
+    _check_draw_args(thickness, dot_radius)
+    if not (torch.is_tensor(images) and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 3 and images.is_cuda
+            and images.numel()):
+        raise ValueError("images must be a non-empty uint8 device tensor [n, h, w, 3]")
+    n, h, w, _ = images.shape
+    if offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 2 or (offs.numel() - 1) % n:
+        raise ValueError("offs must be int64 [n * slots + 1] with slots >= 1")
+    m = offs.numel() - 1
+    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 2:
+        raise ValueError("pts must be int32 [P, 2]")
+    if rgba.dtype != torch.uint8 or tuple(rgba.shape) != (m, 4):
+        raise ValueError("rgba must be uint8 [n * slots, 4]")
+    if centres is not None and (centres.dtype != torch.int32 or tuple(centres.shape) != (m, 2)):
+        raise ValueError("centres must be int32 [n * slots, 2]")
+    if out is not None and (out.dtype != torch.uint8 or out.shape != images.shape or not out.is_contiguous() or out.data_ptr() % 4):
+        raise ValueError("out must be a contiguous, 4-byte aligned uint8 tensor of the images' shape")
+    from . import lib as L
+
+    L.require_gpu()
+    dev = images.device
+    if not images.is_contiguous() or images.data_ptr() % 4:
+        images = images.clone(memory_format=torch.contiguous_format)
+    pts, offs, rgba = pts.contiguous(), offs.contiguous(), rgba.contiguous()
+    centres = None if centres is None else centres.contiguous()
+    if out is None:
+        out = torch.empty_like(images)
+    need = L.lib().hvn_overlay_workspace_bytes(n, h, w)
+    ws = _WORKSPACE.get(str(dev))
+    if ws is None or ws.numel() < need:
+        ws = _WORKSPACE[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    dot = (ctypes.c_uint8 * 3)(*[int(v) for v in dot_colour])
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().hvn_draw_overlay(images.data_ptr(), out.data_ptr(), n, h, w, pts.data_ptr() if pts.shape[0] else None, pts.shape[0],
+                                         offs.data_ptr(), m // n, rgba.data_ptr(), None if centres is None else centres.data_ptr(),
+                                         int(thickness), int(dot_radius), dot, status.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                "hvn_draw_overlay")
+    return (out, status) if return_status else out
+
+
+def overlay_from_records(images, rec, pts, offs, type_colours, *, draw_dot=False, thickness=2):
+    """The device-resident route from `post_proc.process_batch_device(..., nr_types, True, return_contours=True)`: images uint8
+    [n,h,w,3] on the device, rec / pts / offs as returned there, type_colours [nr_types,3] (the colour of type id t in row t; every
+    type id of the records must have a row) -> the overlays `visualize_instances_dict(image, records_to_dict(...), type_colour=...)`
+    draws, as a uint8 device tensor.  A record draws when area > 0 and its contour has at least 3 points (`records_to_dict`'s
+    rule); centres are int(centroid).  Torch ops and one library call on the current stream, no host sync."""
+    import torch
+
+    n, max_inst = rec.shape[0], rec.shape[1]
+    rec = rec.contiguous()
+    i32 = rec.view(torch.int32)                                      # label, area, rmin, rmax, cmin, cmax, -, -, -, -, type, type_count
+    f64 = rec.view(torch.float64)                                    # -, -, -, sum_x, sum_y, -
+    area = i32[..., 1].reshape(-1)
+    draw = (area > 0) & ((offs[1:] - offs[:-1]) >= 3)
+    table = torch.as_tensor(np.asarray(type_colours), device=rec.device).to(torch.uint8).reshape(-1, 3)
+    colour = table[i32[..., 10].reshape(-1).long().clamp_(0, table.shape[0] - 1)]
+    rgba = torch.cat([colour, draw.to(torch.uint8)[:, None]], 1).contiguous()
+    centres = None
+    if draw_dot:
+        a = torch.where(draw, area, torch.ones_like(area)).double()
+        cx = f64[..., 3].reshape(-1) / a + i32[..., 4].reshape(-1).double()
+        cy = f64[..., 4].reshape(-1) / a + i32[..., 2].reshape(-1).double()
+        centres = torch.where(draw[:, None], torch.stack([cx, cy], 1), torch.zeros((), dtype=torch.float64, device=rec.device)).trunc().to(torch.int32)
+    assert rgba.shape[0] == n * max_inst
+    return draw_overlay_device(images, pts, offs, rgba, centres, thickness=thickness)
+
+
+def _visualize_on_device(input_image, inst_dict, draw_dot, type_colour, line_thickness, device):
+    import torch
+
+    _check_draw_args(line_thickness, 3)
+    img = np.asarray(input_image)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("the device overlay needs a uint8 [H, W, 3] image, got %s %s" % (img.dtype, img.shape))
+    flat = flatten_instances(inst_dict, _resolve_colours(inst_dict, type_colour))
+    if not len(inst_dict):
+        return np.array(img, copy=True)
+    dev = torch.device(device)
+    pts, offs, rgba, centres = (torch.from_numpy(a).to(dev) for a in flat)
+    out = draw_overlay_device(torch.from_numpy(np.ascontiguousarray(img)[None]).to(dev), pts, offs, rgba, centres if draw_dot else None,
+                              thickness=int(line_thickness))
+    return out[0].cpu().numpy()
 
 
 def save_png(path, rgb):

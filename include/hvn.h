@@ -229,6 +229,27 @@ HVN_API int hvn_trace_contours_device(const int32_t *inst, int n, int h, int w, 
                                       int32_t *pts, int64_t max_pts, int64_t *offs, int32_t *status, void *workspace,
                                       size_t workspace_bytes, void *stream);
 
+/* -- overlay: viz.visualize_instances_dict (closed contour polylines in the instance's colour, optional centroid dots) drawn on the
+ * DEVICE, bit-equal to the host writer (csrc/hvn_overlay.hip).  All pointers are device pointers except dot_rgb (host, read during
+ * the call); everything is enqueued on `stream`, nothing is allocated or synchronised.  image, overlay: uint8 [n][h][w][3], 4-byte
+ * aligned; image == overlay (in place) is allowed.  pts: int32 [n_pts][2] as (x, y), 8-byte aligned, any int32 value (segments are
+ * clipped pixel by pixel, at a cost bounded by the image size); offs: int64 [n * slots + 1], hvn_trace_contours_device's layout:
+ * slot (i, j) of image i owns pts[offs[i * slots + j] : offs[i * slots + j + 1]] and is drawn into image i as the closed polyline
+ * through its points (one point = one stamp, none = no contour), `thickness` (1..7) px wide: every pixel of a segment
+ * (viz._segment_pixels) stamps the square of offsets -((thickness - 1) / 2) .. thickness / 2.  rgba: uint8 [n * slots][4] = r, g, b,
+ * draw flag (0 = the slot draws nothing, neither contour nor dot).  centres: int32 [n * slots][2] as (x, y), 8-byte aligned: a
+ * filled disc dx^2 + dy^2 <= dot_radius^2 (0..15) in dot_rgb per drawing slot; NULL = no dots.  Drawing order is the host's:
+ * slot by slot, a slot's dot over its contour, later slots over earlier ones (an int32 owner map per pixel, largest key wins:
+ * the result does not depend on scheduling).  A slot whose offs range is reversed or leaves [0, n_pts] draws nothing.
+ * status: int32 [4] = { such slots, the smallest i * slots + j of them or -1, 0, 0 }.
+ * HVN_E_SIZE: workspace smaller than hvn_overlay_workspace_bytes(n, h, w) (or not 16-byte aligned), thickness or dot_radius out of
+ * range, n * slots >= 2^30 - 1 (the keys are int32). */
+HVN_API size_t hvn_overlay_workspace_bytes(int n, int h, int w);
+HVN_API int hvn_draw_overlay(const uint8_t *image, uint8_t *overlay, int n, int h, int w, const int32_t *pts, int64_t n_pts,
+                             const int64_t *offs, int slots, const uint8_t *rgba, const int32_t *centres, int thickness,
+                             int dot_radius, const uint8_t dot_rgb[3], int32_t *status, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
 
 /* -- training step: run_desc.py:12-109 train_step (forward in train() mode, losses utils.py:54-172, backward, Adam) --
  * A training step is two hvn_top lists (forward, backward; hover_net_amd/train_plan.py lowers the network to them)
