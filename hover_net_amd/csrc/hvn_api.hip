@@ -346,6 +346,29 @@ int hvn_extract_patches(const uint8_t *img, int h, int w, const int32_t *coords,
     return 0;
 }
 
+int hvn_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitch, int src_y0, int src_x0, int full_h, int full_w,
+                      const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps, uint8_t *dst, int dst_h,
+                      int dst_w, void *stream)
+{
+    if (!src || !xofs || !xcoef || !yofs || !ycoef || !dst) return fail(HVN_E_ARG, "resize_window: null pointer%s", "");
+    if (taps != 2 && taps != 4) return fail(HVN_E_ARG, "resize_window: taps = %s%ld (2 = linear, 4 = cubic)", "", taps);
+    if (((uintptr_t)xofs & 3) || ((uintptr_t)yofs & 3) || ((uintptr_t)xcoef & 1) || ((uintptr_t)ycoef & 1))
+        return fail(HVN_E_ARG, "resize_window: misaligned table%s", "");
+    if (src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0 || full_h <= 0 || full_w <= 0)
+        return fail(HVN_E_ARG, "resize_window: empty source, window or destination%s", "");
+    // offsets within a row are 32-bit: 3 * width (and taps * width, the coefficient index) must fit
+    if (src_w > (1 << 29) || dst_w > (1 << 29) || dst_h > (1 << 29)) return fail(HVN_E_ARG, "resize_window: a row longer than 2^29 pixels%s", "");
+    if (src_pitch < 3 * (int64_t)src_w) return fail(HVN_E_ARG, "resize_window: src_pitch %s%ld is shorter than a source row", "", (long)src_pitch);
+    // the uploaded box must lie in the full source: taps are clamped against the full source, then translated into the box
+    if (src_y0 < 0 || src_x0 < 0 || (int64_t)src_y0 + src_h > full_h || (int64_t)src_x0 + src_w > full_w)
+        return fail(HVN_E_ARG, "resize_window: the uploaded source box leaves the full source%s", "");
+    int rc = hvn_launch_resize_window(src, src_h, src_w, src_pitch, src_y0, src_x0, full_h, full_w, xofs, xcoef, yofs, ycoef, taps, dst, dst_h,
+                                      dst_w, (hipStream_t)stream);
+    if (rc == -4) return fail(HVN_E_SIZE, "resize_window: %s%ld output rows are more than one launch takes (16 * 65535)", "", dst_h);
+    if (rc) return fail(HVN_E_LAUNCH, "resize_window: launch failed%s", "");
+    return 0;
+}
+
 int hvn_run_plan(const hvn_op *ops, int n_ops, int batch, void *stream)
 {
     if (!ops || n_ops <= 0 || batch <= 0) return fail(HVN_E_ARG, "run_plan: bad arguments%s", "");

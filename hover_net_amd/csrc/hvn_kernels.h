@@ -143,6 +143,11 @@ int hvn_launch_head(const HeadArgs &a, hipStream_t stream);
 int hvn_launch_extract_patches(const uint8_t *img, int H, int W, const int32_t *coords, int P, int win, int pad_t, int pad_l, uint8_t *out,
                                hipStream_t stream);
 
+// hvn_resample.hip: arguments as hvn_resize_window (include/hvn.h), validated by the caller; 0, -2 launch failure, -4 too many tile rows
+int hvn_launch_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitch, int src_y0, int src_x0, int full_h, int full_w,
+                             const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps, uint8_t *dst,
+                             int dst_h, int dst_w, hipStream_t stream);
+
 struct PredMapArgs {
     const float *tp, *np, *hv;  // NCHW logits
     float *y;                   // [N][H][W][3|4]

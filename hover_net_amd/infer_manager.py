@@ -221,18 +221,25 @@ class InferManager:
 
 
 # ----------------------------------------------------------------------------------------------
-def open_slide(path):
+def open_slide(path, base_mag=None, proc_mag=None):
     """Slide backend by extension.  `.npy` -> memory-mapped `ArraySlide`; plain images -> in-memory `ArraySlide`.
     OpenSlide formats (`.svs`, `.ndpi`, ... -- misc/wsi_handler.py:84-99) need the openslide binding, which this image does
-    not have: they raise, and `process_wsi_list` logs the slide as crashed like the reference does (infer/wsi.py:744-749)."""
-    from .infer_wsi import ArraySlide
+    not have: they raise, and `process_wsi_list` logs the slide as crashed like the reference does (infer/wsi.py:744-749).
+    Array and image files carry no objective power: `base_mag` states it, and a `proc_mag` that differs wraps the slide in
+    `ScaledSlide` (resampled window by window as it is read: cubic up, linear down -- there are no pyramid levels to choose
+    from).  Without `base_mag`, or with the two equal, the slide is the plain backend."""
+    from .infer_wsi import ArraySlide, ScaledSlide
 
     ext = pathlib.Path(path).suffix.lower()
     if ext == ".npy":
-        return ArraySlide(np.load(path, mmap_mode="r"))
-    if ext in (".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp"):
-        return ArraySlide(read_image(path))
-    raise ValueError("no slide backend for %r in this build (OpenSlide is not available)" % ext)
+        slide = ArraySlide(np.load(path, mmap_mode="r"))
+    elif ext in (".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp"):
+        slide = ArraySlide(read_image(path))
+    else:
+        raise ValueError("no slide backend for %r in this build (OpenSlide is not available)" % ext)
+    if base_mag is None or proc_mag is None or float(base_mag) == float(proc_mag):
+        return slide
+    return ScaledSlide(slide, base_mag, proc_mag)
 
 
 def read_mask(path):
@@ -255,7 +262,9 @@ class WsiManager(InferManager):
 
     def process_wsi_list(self, run_args):
         """run_args (run_infer.py:173-187): input_dir, output_dir, input_mask_dir, proc_mag, ambiguous_size, chunk_shape,
-        tile_shape, save_thumb, save_mask, batch_size.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        tile_shape, save_thumb, save_mask, batch_size; base_mag (optional): the magnification the files are AT, a number or a
+        {slide stem: number} mapping (a slide the mapping lacks is a "crash") -- a slide whose base_mag differs from proc_mag is resampled to proc_mag as it is read
+        (`open_slide`); absent = the files are taken as they are.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
@@ -264,6 +273,7 @@ class WsiManager(InferManager):
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
         proc_mag = run_args.get("proc_mag", 40)
+        base_mags = run_args.get("base_mag")
         _, rank, _world = infer_tile._dist()
         nested = save_thumb or save_mask                     # infer/wsi.py:700-703: json goes under json/ only then
         if rank == 0:
@@ -282,7 +292,10 @@ class WsiManager(InferManager):
                 status[name] = "skip"
                 continue
             try:
-                slide = open_slide(wsi_path)
+                if isinstance(base_mags, dict) and name not in base_mags:
+                    # processed as it is, its json would claim `mag` = proc_mag unproven: the slide is logged as crashed instead
+                    raise KeyError("run_args['base_mag'] is a mapping without an entry for slide %r" % name)
+                slide = open_slide(wsi_path, base_mags[name] if isinstance(base_mags, dict) else base_mags, proc_mag)
                 msk_path = "%s/%s.png" % (mask_dir, name)
                 mask = read_mask(msk_path) if os.path.isfile(msk_path) else tissue_mask.simple_get_mask(slide.thumbnail(32))
                 if int(np.sum(mask)) == 0:

@@ -23,7 +23,10 @@ Different by design:
     instance maps / record tables / contours travel to rank 0 as tensors, and rank 0 applies the merge callbacks in
     tile order;
   * the slide backend is any object with `.shape` and `.read_region((x, y), (w, h))`
-    (`ArraySlide` wraps a numpy array / memmap; OpenSlide is not required).
+    (`ArraySlide` wraps a numpy array / memmap; OpenSlide is not required);
+  * a slide whose files are not at the processing magnification is not resized whole on the host into a cache file
+    (misc/wsi_handler.py:167-190): `ScaledSlide` resamples each chunk where it is read -- on the GPU, from the native-resolution
+    rows the chunk needs (`read_region_device`, resample.py).
 """
 import time
 
@@ -118,6 +121,50 @@ class ArraySlide:
     def thumbnail(self, scale=32):
         """Sub-sampled view (40x -> 1.25x for scale 32), the input of the tissue-mask heuristic."""
         return np.asarray(self.array[::scale, ::scale, :3])
+
+
+class ScaledSlide:
+    """A slide at the processing magnification: `base` (any backend at `base_mag`) resampled by f = proc_mag / base_mag window
+    by window (resample.py: cubic for f > 1, linear for f < 1; misc/wsi_handler.py:167-190 resizes the WHOLE slide on the host
+    into a cache file instead).  A window is a function of its own table entries alone, so every chunk, every rank and the
+    whole-image `resample.resize_host` give the same bytes.  f == 1 needs no wrapper (the manager makes none)."""
+
+    def __init__(self, base, base_mag, proc_mag):
+        from . import resample
+
+        self.base, self.base_mag, self.proc_mag = base, base_mag, proc_mag
+        self.f = float(proc_mag) / float(base_mag)
+        assert self.f > 0 and self.f != 1.0, (base_mag, proc_mag)
+        self.base_shape = (int(base.shape[0]), int(base.shape[1]))
+        self.shape = (resample.out_size(self.base_shape[0], self.f), resample.out_size(self.base_shape[1], self.f), 3)
+
+    def _window(self, coords, size):
+        x, y = int(coords[0]), int(coords[1])
+        w, h = min(int(size[0]), self.shape[1] - x), min(int(size[1]), self.shape[0] - y)   # cut at the slide's edge, as array slicing is
+        return y, x, h, w
+
+    def _read_base(self, sy, sx, sh, sw):
+        return np.ascontiguousarray(self.base.read_region((sx, sy), (sw, sh))[..., :3])
+
+    def read_region(self, coords, size):
+        from . import resample
+
+        return resample.resize_window_host(self._read_base, self.base_shape, self.f, *self._window(coords, size))
+
+    def read_region_device(self, coords, size, device):
+        """The same window as a uint8 device tensor: the native-resolution box its taps touch goes up once (1 / f^2 of the
+        window's bytes) and is resampled there (hvn_resize_window), bit-equal to `read_region`."""
+        from . import resample
+
+        y, x, h, w = self._window(coords, size)
+        tables = resample.window_tables(self.base_shape, self.f, y, x, h, w)
+        sy, sx, sh, sw = resample.tables_box(self.base_shape, tables)
+        src = torch.from_numpy(self._read_base(sy, sx, sh, sw)).to(device)
+        return resample.resize_window_device(src, (sy, sx), self.base_shape, self.f, y, x, h, w, tables=tables)
+
+    def thumbnail(self, scale=32):
+        """`scale` is in processed pixels: the base is sub-sampled with the step that covers the same tissue."""
+        return self.base.thumbnail(max(1, int(round(scale / self.f))))
 
 
 class TiledSlide:
@@ -504,16 +551,19 @@ class WsiInference:
             y0 = int(plist[:, 0, 0, 0].min())
             y1 = int(plist[:, 0, 1, 0].max())
             x0, x1 = int(chunk[0][0][1]), int(chunk[0][1][1])
-            region = slide.read_region((x0, y0), (x1 - x0, y1 - y0))
+            size = (x1 - x0, y1 - y0)
             rel = plist[:, 0, 0] - np.array([y0, x0])           # patch input top-left inside the region
             win = int(self.pin[0])
             if self.device.type == "cuda":
-                # the region goes up once (300 MB for 10000^2); the overlapping 270^2 crops (11x the bytes) are gathered on
+                # the region goes up once (300 MB for 10000^2) -- from a slide that resamples on the GPU (ScaledSlide) as its
+                # native-resolution rows, resampled there --; the overlapping 270^2 crops (11x the bytes) are gathered on
                 # the GPU (hvn_extract_patches; every crop is in bounds, so its reflect rule never fires)
-                region_dev = torch.from_numpy(np.ascontiguousarray(region[..., :3])).to(self.device)
+                region_dev = (slide.read_region_device((x0, y0), size, self.device) if hasattr(slide, "read_region_device") else
+                              torch.from_numpy(np.ascontiguousarray(slide.read_region((x0, y0), size)[..., :3])).to(self.device))
                 patches = infer_tile.extract_patches_device(region_dev, rel.astype(np.int32), win, 0)
                 del region_dev
             else:
+                region = slide.read_region((x0, y0), size)
                 patches = torch.from_numpy(np.ascontiguousarray(np.stack([region[y:y + win, x:x + win] for y, x in rel])))
             outs = [self._step(patches[b0:b0 + self.batch_size]).clone() for b0 in range(0, patches.shape[0], self.batch_size)]
             out = torch.cat(outs, 0)

@@ -250,6 +250,23 @@ HVN_API int hvn_draw_overlay(const uint8_t *image, uint8_t *overlay, int n, int 
                              int dot_radius, const uint8_t dot_rgb[3], int32_t *status, void *workspace, size_t workspace_bytes,
                              void *stream);
 
+/* -- resample: one window of a slide resampled to the processing magnification (hover_net_amd/resample.py: OpenCV's scalar 8-bit
+ * fixed-point resize restated, 11 coefficient bits), bit-equal to resample.resize_window_host (csrc/hvn_resample.hip).  All
+ * pointers are device pointers; one launch on `stream`, nothing is allocated or synchronised; integer arithmetic only.
+ * src: uint8 [src_h][src_w][3] with rows src_pitch bytes apart: the box of the FULL source [full_h][full_w] whose top-left is
+ * (src_y0, src_x0).  dst: uint8 [dst_h][dst_w][3], contiguous, any alignment.  xofs int32 [dst_w], xcoef int16 [dst_w][taps],
+ * yofs int32 [dst_h], ycoef int16 [dst_h][taps] (taps = 4 cubic | 2 linear): resample.axis_table's entries for the window's columns
+ * and rows, ofs in FULL-source coordinates.  Tap k of an entry reads full-source index clamp(ofs + k - (taps == 4), 0, full - 1),
+ * translated by the box origin.
+ * The box must hold every such tap.  The tables are on the device, so the launcher cannot see their values: the CALLER checks the
+ * taps of the first and last entries against the box before the call (resample.resize_window_device does), and the kernel clamps
+ * the translated index into the box once more, so that no table makes a launch read outside src.
+ * HVN_E_ARG: null or misaligned pointer, taps not 2 | 4, an empty extent, a row longer than 2^29 pixels, src_pitch < 3 * src_w, a box
+ * that leaves the full source.  HVN_E_SIZE: dst_h > 16 * 65535. */
+HVN_API int hvn_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitch, int src_y0, int src_x0, int full_h, int full_w,
+                              const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps,
+                              uint8_t *dst, int dst_h, int dst_w, void *stream);
+
 
 /* -- training step: run_desc.py:12-109 train_step (forward in train() mode, losses utils.py:54-172, backward, Adam) --
  * A training step is two hvn_top lists (forward, backward; hover_net_amd/train_plan.py lowers the network to them)
