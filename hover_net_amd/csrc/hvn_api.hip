@@ -369,6 +369,43 @@ int hvn_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitc
     return 0;
 }
 
+// the tissue mask's common refusals: 0 = the extent is one the kernels index with int32
+static int tissue_extent(const char *what, int h, int w)
+{
+    if (h < 1 || w < 1) return fail(HVN_E_ARG, "%s: h or w < 1 (h = %ld)", what, h);
+    if ((int64_t)h * w > ((int64_t)1 << 30)) return fail(HVN_E_SIZE, "%s: h * w > 2^30 (h = %ld)", what, h);
+    return 0;
+}
+
+int hvn_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, void *stream)
+{
+    if (!rgb || !gray || !hist256) return fail(HVN_E_ARG, "%s: null pointer", "tissue_gray_hist");
+    if ((uintptr_t)hist256 & 3) return fail(HVN_E_ARG, "%s: misaligned hist256", "tissue_gray_hist");
+    if (int rc = tissue_extent("tissue_gray_hist", h, w)) return rc;
+    if (hvn_launch_tissue_gray_hist(rgb, h, w, gray, hist256, (hipStream_t)stream)) return fail(HVN_E_LAUNCH, "%s: launch failed", "tissue_gray_hist");
+    return 0;
+}
+
+size_t hvn_tissue_mask_workspace_bytes(int h, int w)
+{
+    if (h < 1 || w < 1 || (int64_t)h * w > ((int64_t)1 << 30)) return 0;
+    return hvn_tissue_workspace_bytes(h, w);
+}
+
+int hvn_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
+                    uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!gray || !mask || !workspace) return fail(HVN_E_ARG, "%s: null pointer", "tissue_mask");
+    if (int rc = tissue_extent("tissue_mask", h, w)) return rc;
+    if (radius < 0 || radius > 32) return fail(HVN_E_ARG, "tissue_mask: radius %s%ld outside [0, 32]", "", radius);
+    if ((uintptr_t)workspace & 15) return fail(HVN_E_ARG, "%s: workspace is not 16-byte aligned", "tissue_mask");
+    if (workspace_bytes < hvn_tissue_workspace_bytes(h, w))
+        return fail(HVN_E_SIZE, "tissue_mask: workspace smaller than hvn_tissue_mask_workspace_bytes%s (%ld bytes given)", "", (long)workspace_bytes);
+    if (hvn_launch_tissue_mask(gray, h, w, threshold, min_obj, max_hole, radius, mask, tap_objects, tap_holes, workspace, (hipStream_t)stream))
+        return fail(HVN_E_LAUNCH, "%s: launch failed", "tissue_mask");
+    return 0;
+}
+
 int hvn_run_plan(const hvn_op *ops, int n_ops, int batch, void *stream)
 {
     if (!ops || n_ops <= 0 || batch <= 0) return fail(HVN_E_ARG, "run_plan: bad arguments%s", "");

@@ -148,6 +148,12 @@ int hvn_launch_resize_window(const uint8_t *src, int src_h, int src_w, int64_t s
                              const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps, uint8_t *dst,
                              int dst_h, int dst_w, hipStream_t stream);
 
+// hvn_tissue.hip: arguments as hvn_tissue_gray_hist / hvn_tissue_mask (include/hvn.h), validated by the caller; 0, -2 launch failure
+size_t hvn_tissue_workspace_bytes(int h, int w);
+int hvn_launch_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, hipStream_t stream);
+int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
+                           uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, hipStream_t stream);
+
 struct PredMapArgs {
     const float *tp, *np, *hv;  // NCHW logits
     float *y;                   // [N][H][W][3|4]

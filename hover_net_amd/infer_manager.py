@@ -264,7 +264,8 @@ class WsiManager(InferManager):
         """run_args (run_infer.py:173-187): input_dir, output_dir, input_mask_dir, proc_mag, ambiguous_size, chunk_shape,
         tile_shape, save_thumb, save_mask, batch_size; base_mag (optional): the magnification the files are AT, a number or a
         {slide stem: number} mapping (a slide the mapping lacks is a "crash") -- a slide whose base_mag differs from proc_mag is resampled to proc_mag as it is read
-        (`open_slide`); absent = the files are taken as they are.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        (`open_slide`); absent = the files are taken as they are; device_mask (default False): a slide without a mask file takes its
+        tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`, the same bytes on every rank).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
@@ -274,6 +275,7 @@ class WsiManager(InferManager):
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
         proc_mag = run_args.get("proc_mag", 40)
         base_mags = run_args.get("base_mag")
+        mask_device = (self._collective_device() or "cuda") if run_args.get("device_mask", False) else None
         _, rank, _world = infer_tile._dist()
         nested = save_thumb or save_mask                     # infer/wsi.py:700-703: json goes under json/ only then
         if rank == 0:
@@ -297,7 +299,7 @@ class WsiManager(InferManager):
                     raise KeyError("run_args['base_mag'] is a mapping without an entry for slide %r" % name)
                 slide = open_slide(wsi_path, base_mags[name] if isinstance(base_mags, dict) else base_mags, proc_mag)
                 msk_path = "%s/%s.png" % (mask_dir, name)
-                mask = read_mask(msk_path) if os.path.isfile(msk_path) else tissue_mask.simple_get_mask(slide.thumbnail(32))
+                mask = read_mask(msk_path) if os.path.isfile(msk_path) else tissue_mask.simple_get_mask(slide.thumbnail(32), device=mask_device)
                 if int(np.sum(mask)) == 0:
                     status[name] = "empty mask"
                     continue

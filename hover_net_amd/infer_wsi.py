@@ -105,6 +105,34 @@ def select_valid(info_list, mask, proc_shape, has_output_info=True):
     return info_list[keep]
 
 
+def mask_sat(mask):
+    """Summed-area table of `mask != 0`, int64 [h + 1, w + 1] with a zero first row and column (`select_valid_sat`)."""
+    sat = np.zeros((mask.shape[0] + 1, mask.shape[1] + 1), np.int64)
+    np.cumsum(mask != 0, axis=0, dtype=np.int64, out=sat[1:, 1:])
+    np.cumsum(sat[1:, 1:], axis=1, out=sat[1:, 1:])
+    return sat
+
+
+def select_valid_sat(info_list, mask, proc_shape, has_output_info=True, sat=None):
+    """`select_valid` for all boxes at once: the same rounding, every box clamped to the mask the way a slice clamps it (an
+    empty slice is not kept), one summed-area table of `mask != 0` (`sat`: `mask_sat(mask)` made earlier, for a mask that is
+    tested many times).  What a slice does differently -- a negative rounded coordinate wraps, a mask with negative entries can
+    sum to zero -- is left to `select_valid`."""
+    info_list = np.asarray(info_list)
+    if info_list.shape[0] == 0 or info_list.shape[1:] != ((2, 2, 2) if has_output_info else (2, 2)) or mask.ndim != 2 or mask.dtype.kind not in "bu":
+        return select_valid(info_list, mask, proc_shape, has_output_info)
+    ratio = mask.shape[0] / proc_shape[0]
+    boxes = np.rint((info_list[:, 1] if has_output_info else info_list) * ratio).astype(np.int64)
+    if boxes.min() < 0:
+        return select_valid(info_list, mask, proc_shape, has_output_info)
+    if sat is None:
+        sat = mask_sat(mask)
+    y0, y1 = np.minimum(boxes[:, 0, 0], mask.shape[0]), np.minimum(boxes[:, 1, 0], mask.shape[0])
+    x0, x1 = np.minimum(boxes[:, 0, 1], mask.shape[1]), np.minimum(boxes[:, 1, 1], mask.shape[1])
+    inside = sat[y1, x1] - sat[y0, x1] - sat[y1, x0] + sat[y0, x0]
+    return info_list[np.nonzero((y1 > y0) & (x1 > x0) & (inside > 0))[0]]
+
+
 # --------------------------------------------------------------------------------------------
 class ArraySlide:
     """Slide backend over an in-memory / memory-mapped uint8 [H,W,3] array (misc/wsi_handler.py API subset)."""
@@ -485,13 +513,17 @@ class DeviceMerger:
 # --------------------------------------------------------------------------------------------
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
-                 patch_input_shape=None, patch_output_shape=None, device_contours=False):
-        """device_contours=True: stage 2 traces every tile's contours on the GPU (`PostProc.contours`, same arrays as the host
+                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False):
+        """device_mask=True: `run(slide, "auto")` takes the tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`: the
+        same bytes, on every rank alike).
+        device_contours=True: stage 2 traces every tile's contours on the GPU (`PostProc.contours`, same arrays as the host
         tracer) on the tile's post-processing stream instead of on the host worker thread.  The tile's instance map still goes
         to the host, and the whole `pts` buffer at its default capacity (a quarter of the tile's pixels: 8 MB for a 2048 x 2048
         tile, a fifth of it used) is copied with it, because the total is not known on the host when the copy is enqueued: 50 %
         more D2H bytes per tile than the default path, and each pinned slot grows by that buffer."""
         self.device_contours = bool(device_contours)
+        self.device_mask = bool(device_mask)
+        self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
         pin = patch_input_shape or (270 if net.mode == "original" else 256)     # run_infer.py:145-150
@@ -504,12 +536,23 @@ class WsiInference:
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)      # one process per GPU: ctypes HIP launches and collectives use the current device
         self.out_ch = 3 if nr_types is None else 4
+        if self.device_mask and self.device.type != "cuda":
+            raise ValueError("device_mask=True needs a model on a GPU (this one is on %s)" % self.device)
 
     # -- stage 1: raw prediction into the HBM-resident map ----------------------------------------
     def tile_lists(self, shape, mask):
         """The three phases' tile boxes after the mask test -- the same on every rank (pure geometry + mask)."""
         grid, boundary, cross = get_tile_info(shape, self.tile_shape, self.ambiguous_size)
-        return [select_valid(t, mask, shape, has_output_info=False) for t in (grid, boundary, cross)]
+        return [select_valid_sat(t, mask, shape, has_output_info=False, sat=self._mask_sat(mask)) for t in (grid, boundary, cross)]
+
+    def _mask_sat(self, mask):
+        """`mask_sat(mask)`, made once per mask (every chunk and every phase tests the same mask).  The table is kept for the
+        mask OBJECT and its count of nonzero entries, so a mask edited in place between calls gets a new table unless the edit
+        keeps that count: hand an edited mask over as a new array."""
+        key = int(np.count_nonzero(mask))
+        if self._sat[0] is not mask or self._sat[2] != key:
+            self._sat = (mask, mask_sat(mask) if mask.ndim == 2 else None, key)
+        return self._sat[1]
 
     def raw_prediction(self, slide, mask, as_slab=False):
         """The reference's chunk loop (wsi.py:329-383; every patch belongs to the FIRST chunk that selects it), restricted on each
@@ -543,7 +586,7 @@ class WsiInference:
             sel &= in_slab
             if not sel.any():
                 continue
-            plist = select_valid(np.array(patch_info[sel]), mask, shape)
+            plist = select_valid_sat(np.array(patch_info[sel]), mask, shape, sat=self._mask_sat(mask))
             if plist.shape[0] == 0:
                 continue
             self.stage1_patches += int(plist.shape[0])
@@ -749,7 +792,7 @@ class WsiInference:
         if isinstance(mask, str) and mask == "auto":
             from . import tissue_mask
 
-            mask = tissue_mask.simple_get_mask(slide.thumbnail(32))
+            mask = tissue_mask.simple_get_mask(slide.thumbnail(32), device=self.device if self.device_mask else None)
         if mask is None:
             mask = np.ones((max(1, int(shape[0]) // 32), max(1, int(shape[1]) // 32)), np.uint8)
         pred_map = self.raw_prediction(slide, mask, as_slab=True)

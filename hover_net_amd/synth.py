@@ -201,3 +201,22 @@ def synth_inst_pair(h, w, n_inst, seed=0, r_lo=3, r_hi=9, shift=(2, 1), n_merge=
         assert a.max() <= 2 ** 31 - 1
         out.append(a.astype(np.int32))
     return out[0], out[1]
+
+
+def synth_thumbnail(h, w, seed=0, tissue=0.42):
+    """A seeded 1.25x slide thumbnail for the tissue-mask path: uint8 [h, w, 3], bright noisy background, blobby stained tissue
+    over about `tissue` of the area (a smoothed random field cut at that quantile) with small tears inside it, and dark dust
+    specks of 1 - 9 px on the background.  Returns (thumb, fraction of pixels drawn as tissue)."""
+    from scipy import ndimage
+
+    rng = np.random.default_rng(seed)
+    field = ndimage.gaussian_filter(rng.standard_normal((h, w)), sigma=max(2.0, min(32.0, min(h, w) / 40.0)))
+    blob = field > np.quantile(field, 1.0 - tissue)
+    tears = ndimage.gaussian_filter(rng.standard_normal((h, w)), sigma=3.0) > 0.12
+    blob &= ~tears
+    dust = ndimage.binary_dilation(rng.random((h, w)) < 2e-4, iterations=1) & (rng.random((h, w)) < 0.7)
+    dark = blob | dust
+    thumb = np.clip(rng.normal(232, 5, (h, w, 3)), 0, 255)
+    stain = np.clip(rng.normal((150, 90, 160), 18, (h, w, 3)), 0, 255)
+    thumb[dark] = stain[dark]
+    return thumb.astype(np.uint8), float(dark.mean())

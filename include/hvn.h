@@ -267,6 +267,23 @@ HVN_API int hvn_resize_window(const uint8_t *src, int src_h, int src_w, int64_t 
                               const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps,
                               uint8_t *dst, int dst_h, int dst_w, void *stream);
 
+/* -- tissue mask: the automatic mask of whole-slide mode (infer/wsi.py:486-500 simple_get_mask) on the device, bit-equal to
+ * hover_net_amd/tissue_mask.py (csrc/hvn_tissue.hip).  All pointers are device pointers; everything is enqueued on `stream`, nothing
+ * is allocated or synchronised; integer arithmetic and integer atomics only, so equal inputs give equal bytes.
+ * hvn_tissue_gray_hist: rgb uint8 [h][w][3] -> gray uint8 [h][w] = (R*4899 + G*9617 + B*1868 + 8192) >> 14 and hist256, its 256
+ * uint32 counters (cleared by the call).  The Otsu threshold is taken from the counters on the host (tissue_mask.otsu_from_hist).
+ * hvn_tissue_mask: m0 = !(gray > threshold); objects = m0 without its 8-connected components of fewer than min_obj pixels; holes =
+ * objects with every 4-connected component of its complement of fewer than max_hole pixels filled (border components included);
+ * mask = holes dilated by the disk dy^2 + dx^2 <= radius^2.  mask, tap_objects, tap_holes: uint8 [h][w] of {0, 1}; the taps may be
+ * NULL.  gray is only read; no two of the planes may overlap.
+ * HVN_E_ARG: a null pointer (taps excepted), h or w < 1, radius outside [0, 32], a misaligned hist256 (4) or workspace (16).
+ * HVN_E_SIZE: h * w > 2^30, workspace smaller than hvn_tissue_mask_workspace_bytes(h, w) (0 for an extent that is refused).
+ * A refused call launches nothing and leaves its outputs untouched. */
+HVN_API int hvn_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, void *stream);
+HVN_API size_t hvn_tissue_mask_workspace_bytes(int h, int w);
+HVN_API int hvn_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
+                            uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, size_t workspace_bytes, void *stream);
+
 
 /* -- training step: run_desc.py:12-109 train_step (forward in train() mode, losses utils.py:54-172, backward, Adam) --
  * A training step is two hvn_top lists (forward, backward; hover_net_amd/train_plan.py lowers the network to them)
