@@ -176,6 +176,11 @@ class DevicePatchLoader:
         mine = self._share()
         return mine // self.batch_size if self.mode == "train" else -(-mine // self.batch_size)
 
+    @property
+    def n_samples(self):
+        """Samples this rank's epoch yields: whole batches only in "train" mode, every patch of the shard in "valid" mode."""
+        return len(self) * self.batch_size if self.mode == "train" else self._share()
+
     def batch(self, prm, noise=None, generator=None):
         """The device pipeline for one batch of parameter records.  `noise` / `generator`: the N(0,1) samples of the additive-noise
         records, or the torch device generator to draw them with (the loader seeds one per epoch and rank)."""

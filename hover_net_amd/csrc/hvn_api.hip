@@ -406,6 +406,26 @@ int hvn_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_ob
     return 0;
 }
 
+int hvn_viz_strip(const uint8_t *img, int n, int ih, int iw, const float *pred, int c, const int32_t *np_map, const float *hv_map,
+                  const int32_t *tp_map, int h, int w, int nr_types, const int32_t *sel, int n_sel, const uint8_t *lut, uint8_t *out,
+                  int n_blocks, void *stream)
+{
+    if (!img || !pred || !np_map || !hv_map || !lut || !out || (n_sel > 0 && !sel)) return fail(HVN_E_ARG, "%s: null pointer", "viz_strip");
+    if (n < 1 || h < 1 || w < 1 || n_blocks < 1) return fail(HVN_E_ARG, "viz_strip: n, h, w or n_blocks < 1 (h = %s%ld)", "", h);
+    if (n_sel < 0 || n_sel > 65535) return fail(HVN_E_ARG, "viz_strip: n_sel %s%ld outside [0, 65535]", "", n_sel);
+    if (ih < h || iw < w) return fail(HVN_E_ARG, "viz_strip: the image is smaller than the maps (ih = %s%ld)", "", ih);
+    if (c != 3 && c != 4) return fail(HVN_E_ARG, "viz_strip: c = %s%ld, not 3 or 4", "", c);
+    if (nr_types < 0 || nr_types > 16) return fail(HVN_E_ARG, "viz_strip: nr_types %s%ld outside [0, 16]", "", nr_types);
+    if ((nr_types > 0) != (c == 4)) return fail(HVN_E_ARG, "viz_strip: nr_types > 0 goes with c == 4 and nr_types == 0 with c == 3 (c = %s%ld)", "", c);
+    if (((uintptr_t)pred | (uintptr_t)np_map | (uintptr_t)hv_map | (uintptr_t)tp_map | (uintptr_t)sel) & 3)
+        return fail(HVN_E_ARG, "%s: misaligned pred, map or sel", "viz_strip");
+    if ((int64_t)2 * h * 5 * w > ((int64_t)1 << 30)) return fail(HVN_E_SIZE, "viz_strip: 2h * 5w > 2^30 (h = %s%ld)", "", h);
+    if (n_sel == 0) return 0;
+    if (hvn_launch_viz_strip(img, n, ih, iw, pred, c, np_map, hv_map, tp_map, h, w, nr_types, sel, n_sel, lut, out, n_blocks, (hipStream_t)stream))
+        return fail(HVN_E_LAUNCH, "%s: launch failed", "viz_strip");
+    return 0;
+}
+
 int hvn_run_plan(const hvn_op *ops, int n_ops, int batch, void *stream)
 {
     if (!ops || n_ops <= 0 || batch <= 0) return fail(HVN_E_ARG, "run_plan: bad arguments%s", "");

@@ -154,6 +154,11 @@ int hvn_launch_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray,
 int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
                            uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, hipStream_t stream);
 
+// hvn_viz.hip: arguments as hvn_viz_strip (include/hvn.h), validated by the caller (n_sel >= 1); 0, -2 launch failure
+int hvn_launch_viz_strip(const uint8_t *img, int n, int ih, int iw, const float *pred, int c, const int32_t *np_map, const float *hv_map,
+                         const int32_t *tp_map, int h, int w, int nr_types, const int32_t *sel, int n_sel, const uint8_t *lut, uint8_t *out,
+                         int n_blocks, hipStream_t stream);
+
 struct PredMapArgs {
     const float *tp, *np, *hv;  // NCHW logits
     float *y;                   // [N][H][W][3|4]

@@ -7,8 +7,8 @@ ScheduleLr}, valid engine {STEP_COMPLETED: AccumulateRawOutput; EPOCH_COMPLETED:
 This module provides the same surface -- event names, `State` fields, `add_event_handler`, `run(nr_epoch, shared_state,
 chained)`, the handler protocol -- so the reference's own callback objects (logging, visualisation) attach unchanged, and
 the data-path callbacks listed above so `hover_net_amd.train.run_phases` is the reference's wiring on the HIP step functions.
-Not rebuilt (host-only glue): tqdm progress bars, LoggingEpochOutput / LoggingGradient (tensorboard + json), VisualizeOutput,
-ConditionalSaver."""
+`VisualizeOutput` (callbacks/base.py:220-232) draws the epoch's training picture, on the device when the step kept its samples there.
+Not rebuilt (host-only glue): tqdm progress bars, LoggingEpochOutput / LoggingGradient (tensorboard + json), ConditionalSaver."""
 from enum import Enum
 
 import torch
@@ -57,6 +57,7 @@ class RunEngine:
         self.state.run_info = run_info
         self.state.log_info = log_info
         self.state.batch_size = getattr(dataloader, "batch_size", None)
+        self.state.dataloader = dataloader          # not a reference field: DeviceValidStats reads the loader's n_samples from it
         self.event_handler_dict = {event: [] for event in Events}
         self.terminate = False
 
@@ -152,19 +153,74 @@ class ProcessAccumulatedRawOutput(BaseCallbacks):
         state.tracked_step_output = self.proc_func(state.epoch_accumulated_output)
 
 
+class VisualizeOutput(BaseCallbacks):
+    """callbacks/base.py:220-232, EPOCH_COMPLETED of the train engine: the picture of the epoch's last step,
+    `state.tracked_step_output["image"]["output"] = proc_func(state.step_output["raw"])` (`proc_func`: `run_desc.viz_step_output`,
+    or a lambda that adds nr_types).  When "raw" holds device tensors (`train_step` with `extra_info["viz"] == "device"`) it is
+    `device_func` that draws, on the device, and the finished strip is what comes to the host.  `per_n_epoch` is kept and, as in
+    the reference, not consulted.  An epoch without a step draws nothing."""
+
+    def __init__(self, proc_func, per_n_epoch=1, device_func=None):
+        super().__init__()
+        self.per_n_epoch = per_n_epoch
+        self.proc_func = proc_func
+        self.device_func = device_func
+
+    def run(self, state, event):
+        if state.step_output is None:
+            return
+        raw = state.step_output["raw"]
+        img = raw.get("img") if hasattr(raw, "get") else None
+        if torch.is_tensor(img) and img.is_cuda:
+            from . import run_desc
+
+            strip = (self.device_func or run_desc.viz_step_output_device)(raw)
+            state.tracked_step_output["image"]["output"] = strip.cpu().numpy()
+        else:
+            state.tracked_step_output["image"]["output"] = self.proc_func(raw)
+
+
 class DeviceValidStats(BaseCallbacks):
     """EPOCH_COMPLETED of a valid engine whose step is `run_desc.valid_step_stats`: in place of AccumulateRawOutput +
     ProcessAccumulatedRawOutput.  `stats` (a `valid_stats.ValidStats`) is merged over the ranks -- a collective: every rank's valid
-    engine must reach this point once per epoch --, read once and cleared for the next epoch."""
+    engine must reach this point once per epoch --, read once and cleared for the next epoch.
 
-    def __init__(self, stats):
+    `viz_samples > 0` adds the epoch's picture (`tracked_step_output["image"]["output"]`, the reference draws eight patches, with
+    replacement): the handler must then ALSO be registered for EPOCH_STARTED, where it plans that epoch's samples
+    (`ValidStats.plan_viz`) from `n_samples` of the engine's loader (`state.dataloader`; `augment.DevicePatchLoader` has it), drawn from
+    `numpy.random.default_rng([seed, k])` for the k-th plan.  A loader without `n_samples` gets no picture -- how many samples an epoch
+    holds cannot be known before it ran.  Pictures come from rank 0's shard only; the other ranks plan nothing."""
+
+    def __init__(self, stats, viz_samples=0, seed=0):
         super().__init__()
         self.stats = stats
+        self.viz_samples, self.seed, self._plans = int(viz_samples), int(seed), 0
+
+    def plan(self, loader):
+        """Plan the coming epoch's picture (EPOCH_STARTED does this); returns the planned indices or None."""
+        n = getattr(loader, "n_samples", None)
+        if self.viz_samples <= 0 or not n or _rank() != 0:
+            return None
+        import numpy as np
+
+        idx = np.random.default_rng([self.seed, self._plans]).integers(0, int(n), size=self.viz_samples)
+        self._plans += 1
+        self.stats.plan_viz(idx, getattr(loader, "input_shape", None))
+        return idx
 
     def run(self, state, event):
+        if event == Events.EPOCH_STARTED:
+            self.plan(getattr(state, "dataloader", None))
+            return
         self.stats.merge_ranks()
         state.tracked_step_output = self.stats.track()
         self.stats.reset()
+
+
+def _rank():
+    import torch.distributed as dist
+
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 class PeriodicSaver(BaseCallbacks):

@@ -7,8 +7,11 @@ engines the way opt.py:96-140 does (ScalarMovingAverage, TrackLr, PeriodicSaver,
 AccumulateRawOutput, ProcessAccumulatedRawOutput) and run them; checkpoints are `{"desc", "optimizer", "lr_scheduler"}`
 state_dicts per epoch like the reference's PeriodicSaver.
 
+`run_phases(viz=N)` adds the reference's pictures (opt.py:108-139: a strip of the last training step per epoch, a strip of
+validation patches per validation run), drawn on the device where the data already is.
+
 Deliberately not rebuilt (host glue that never touches the GPU path): tensorboard / JSON logging
-callbacks, visualisation, the file-list dataset and its imgaug augmentation pipeline -- any iterable of the
+callbacks, the file-list dataset and its imgaug augmentation pipeline -- any iterable of the
 reference loader's batch dicts is accepted instead (`SyntheticLoader` provides seeded synthetic ones).
 
 Multi-GPU: one process per GPU (`torchrun --nproc-per-node N`, device = LOCAL_RANK); at the start of every phase rank 0's
@@ -159,7 +162,7 @@ def _same_on_all_ranks(value, what, device=None):
 
 
 def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, on_epoch=None, allow_random_frozen_encoder=False,
-               handlers=None, device_valid=False):
+               handlers=None, device_valid=False, viz=0):
     """config: get_config(...); make_loaders(phase_idx, batch_size_dict) -> {"train": iterable, "valid": iterable|None}.
     Returns the per-epoch history [{phase, epoch, lr, train: {EMA means}, valid_steps, valid: {scalars}}] and the final net.
     `handlers`: extra (event, handler) pairs for the train engine -- any object with the reference's `.run(state, event)`
@@ -168,8 +171,13 @@ def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, 
     configured valid step + AccumulateRawOutput / ProcessAccumulatedRawOutput: the statistics are accumulated on the device
     (`valid_stats.ValidStats`), merged over the ranks and read once per epoch.  The history's `valid` entry keeps its keys and is
     then the score of the whole validation set, identical on every rank (the default reduces what this rank's shard held).  That
-    path keeps NO raw arrays (`epoch_accumulated_output` stays empty): callbacks that draw from them, like the reference's
-    visualisation, need the default path."""
+    path keeps NO raw arrays (`epoch_accumulated_output` stays empty); the validation picture is drawn on the device instead.
+    `viz > 0`: pictures.  The train engine gets `run_engine.VisualizeOutput` and `train_step` keeps its two samples on the device
+    (`extra_info["viz"] = "device"`: no copy to the host per step); the valid engine draws `viz` patches of rank 0's shard through
+    `DeviceValidStats(viz_samples=viz)` on the device path (a loader with `n_samples` is needed), and the reference's eight through
+    `proc_valid_step_output(image=True)` on the default path.  The strips are in the engines' `tracked_step_output["image"]["output"]`
+    (uint8 arrays; `handlers` see them); with `log_dir`, rank 0 also writes them as `train_epoch=%d.png` / `valid_epoch=%d.png` into
+    the phase directory.  The history rows stay scalar."""
     rank, world = _dist_info()
     if device is None:                      # one process per GPU: the launcher's LOCAL_RANK names it
         device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if torch.cuda.is_available() else "cuda"
@@ -201,7 +209,8 @@ def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, 
         opt_cls, opt_args = info["optimizer"]
         optimizer = opt_cls(net.parameters(), **opt_args)
         scheduler = info["lr_scheduler"](optimizer)
-        run_info = {"net": {"desc": net, "optimizer": optimizer, "lr_scheduler": scheduler, "extra_info": info["extra_info"]}}
+        extra_info = dict(info["extra_info"], viz="device") if viz > 0 else info["extra_info"]
+        run_info = {"net": {"desc": net, "optimizer": optimizer, "lr_scheduler": scheduler, "extra_info": extra_info}}
         loaders = make_loaders(pi, phase["batch_size"])
         if hasattr(loaders["train"], "__len__"):
             _same_on_all_ranks(len(loaders["train"]), "phase %d: number of training batches per epoch" % pi, device)
@@ -222,16 +231,33 @@ def run_phases(config, make_loaders, log_dir=None, nr_epochs=None, device=None, 
 
             stats = ValidStats(net.nr_types, device)
             valid_eng = RE.RunEngine("valid", loaders["valid"], run_desc.valid_step_stats, dict(run_info, valid_stats=stats))
-            valid_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.DeviceValidStats(stats))
+            dvs = RE.DeviceValidStats(stats, viz_samples=viz, seed=pi)
+            if viz > 0:
+                valid_eng.add_event_handler(RE.Events.EPOCH_STARTED, dvs)
+            valid_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, dvs)
         elif loaders.get("valid") is not None:
             valid_eng = RE.RunEngine("valid", loaders["valid"], step_fns.get("valid", {}).get("run_step", run_desc.valid_step), run_info)
             valid_eng.add_event_handler(RE.Events.STEP_COMPLETED, RE.AccumulateRawOutput())
             valid_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.ProcessAccumulatedRawOutput(
-                lambda raw: run_desc.proc_valid_step_output(raw, nr_types=net.nr_types)))
+                lambda raw: run_desc.proc_valid_step_output(raw, nr_types=net.nr_types, image=viz > 0)))
+        if viz > 0:                                         # before the valid trigger, like opt.py:108-139
+            train_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, RE.VisualizeOutput(run_desc.viz_step_output))
         if valid_eng is not None:
             trig = RE.TriggerEngine("valid")
             trig.triggered_engine = valid_eng
             train_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, trig)
+        if viz > 0 and log_dir is not None and rank == 0:
+
+            class _SavePictures(RE.BaseCallbacks):          # after the valid trigger: both strips of the epoch exist
+                def run(_self, state, event):
+                    from . import viz as V
+
+                    for name, eng in (("train", train_eng), ("valid", valid_eng)):
+                        strip = None if eng is None else eng.state.tracked_step_output.get("image", {}).get("output")
+                        if strip is not None:
+                            V.save_png(os.path.join(state.log_dir, "%s_epoch=%d.png" % (name, state.curr_epoch)), strip)
+
+            train_eng.add_event_handler(RE.Events.EPOCH_COMPLETED, _SavePictures())
         for extra in (handlers or ()):                      # e.g. the reference's own logging / visualisation callbacks
             train_eng.add_event_handler(*extra)
 

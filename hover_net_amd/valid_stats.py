@@ -7,8 +7,10 @@ sync, `merge_ranks` makes it the state of the whole validation set on every rank
 the divisions there, with `proc_valid_step_output`'s own float64 expressions.  The counts are exact, so np_acc and the Dice scores
 equal the host path's bit for bit; hv_mse is the same non-negative float64 terms added in another (fixed) order.
 
-Nothing here keeps predictions, targets or images: callbacks that draw from the epoch's raw arrays (the reference's visualisation)
-need the default `valid_step` / `proc_valid_step_output` path.
+Nothing here keeps predictions, targets or images.  The epoch's picture (the "image" half of `proc_valid_step_output`, the
+reference's visualisation of eight validation patches) does not need them either: `plan_viz` names the samples of the coming epoch
+to draw, and `update` draws each of them that falls into its batch straight into its block of one device strip (`viz.strip_device`,
+one more launch); `track` brings scalars and strip to the host in one copy.
 """
 import ctypes
 
@@ -50,9 +52,45 @@ class ValidStats:
         self.counts = self._buf[:-1]
         self.hv_sse = self._buf[-1:].view(torch.float64)
         self._ws = None
+        self._plan, self._img_hw, self._strip, self._drawn, self._seen = None, None, None, None, 0
+        self.viz_missing = 0
 
     def reset(self):
+        """Clear the counts, the plan of `plan_viz` and its strip: the next epoch draws nothing unless it is planned again."""
         self._buf.zero_()
+        self._plan, self._img_hw, self._strip, self._drawn, self._seen = None, None, None, None, 0
+
+    def plan_viz(self, indices, img_hw=None):
+        """Draw the samples `indices` of the epoch that starts now: positions in this rank's sample sequence (the order in which
+        `update` sees them, counted from 0 at the last `reset`), any order, duplicates allowed.  Block j of the strip is sample
+        indices[j].  `img_hw`: the (height, width) the feed's images must have, checked in `update` (None: not checked).  A
+        planned index the epoch never reaches leaves its block zero and is counted in `viz_missing` by `track`."""
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        if (idx < 0).any():
+            raise ValueError("plan_viz: negative sample index")
+        if self._seen:
+            raise ValueError("plan_viz after the epoch's first update: call it after reset()")
+        self._plan = idx
+        self._img_hw = None if img_hw is None else (int(img_hw[0]), int(img_hw[1]))
+        self._drawn = np.zeros(idx.shape[0], bool)
+        self._strip = None
+
+    def _draw(self, pred_dev, feed, np_map, hv_map, tp_map):
+        from . import viz
+
+        n, h, w, _c = (int(v) for v in pred_dev.shape)
+        img = torch.as_tensor(feed["img"])
+        if self._img_hw is not None and tuple(int(v) for v in img.shape[1:3]) != self._img_hw:
+            raise ValueError("plan_viz was told images of %s, the feed's are %s" % (self._img_hw, tuple(img.shape[1:3])))
+        typed = self.nr_types is not None       # `launch` has refused a typed state without type truths
+        if self._strip is None and self._plan.shape[0]:
+            self._strip = torch.zeros((self._plan.shape[0] * 2 * h, (5 if typed else 4) * w, 3), dtype=torch.uint8, device=self.device)
+        hit = np.nonzero((self._plan >= self._seen) & (self._plan < self._seen + n))[0]
+        if hit.size:
+            sel = np.stack([self._plan[hit] - self._seen, hit], 1)
+            viz.strip_device(img.to(self.device, torch.uint8, non_blocking=True).contiguous(), pred_dev, np_map, hv_map, tp_map, sel,
+                             out=self._strip, nr_types=self.nr_types)
+            self._drawn[hit] = True
 
     def _feed(self, x, dtype, shape):
         return torch.as_tensor(x).to(self.device, dtype, non_blocking=True).reshape(shape).contiguous()
@@ -77,6 +115,9 @@ class ValidStats:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
         launch(pred_dev, np_map, hv_map, tp_map, (n, h, w, c), self.nr_types or 0, self.counts, self.hv_sse, self._ws)
+        if self._plan is not None:
+            self._draw(pred_dev, feed, np_map, hv_map, tp_map)
+        self._seen += n
 
     def merge_ranks(self):
         """Make the state the whole validation set's on every rank.  A collective: EVERY rank of the process group must call it, once
@@ -99,9 +140,7 @@ class ValidStats:
         self.counts.copy_(counts)
         self.hv_sse.copy_(total)
 
-    def scalars(self):
-        """The dict of `proc_valid_step_output(...)["scalar"]` from one device-to-host copy of the state."""
-        host = self._buf.cpu().numpy()
+    def _scalars_of(self, host):
         c, hv_sse = host[:-1], host[-1:].view(np.float64)[0]
         nr_pixels = int(c[0])
 
@@ -114,5 +153,17 @@ class ValidStats:
         out["hv_mse"] = hv_sse / nr_pixels
         return out
 
+    def scalars(self):
+        """The dict of `proc_valid_step_output(...)["scalar"]` from one device-to-host copy of the state."""
+        return self._scalars_of(self._buf.cpu().numpy())
+
     def track(self):
-        return {"scalar": self.scalars(), "image": {}}
+        """`proc_valid_step_output`'s dict.  Without a plan "image" is empty; with one (and at least one `update`) it holds the strip
+        under "output", and state and strip come to the host in ONE copy.  The strip is this rank's: `merge_ranks` does not touch it."""
+        if self._plan is None or self._strip is None:
+            self.viz_missing = 0 if self._plan is None else int(self._plan.shape[0])
+            return {"scalar": self.scalars(), "image": {}}
+        nb = self._buf.numel() * 8
+        host = torch.cat([self._buf.view(torch.uint8), self._strip.reshape(-1)]).cpu().numpy()
+        self.viz_missing = int((~self._drawn).sum())
+        return {"scalar": self._scalars_of(host[:nb].view(np.int64)), "image": {"output": host[nb:].reshape(tuple(self._strip.shape)).copy()}}

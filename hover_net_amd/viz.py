@@ -228,6 +228,136 @@ def _visualize_on_device(input_image, inst_dict, draw_dot, type_colour, line_thi
     return out[0].cpu().numpy()
 
 
+# ---- the run loop's picture (models/hovernet/run_desc.py:201-256 viz_step_output) -------------------------------------------------
+# matplotlib's "jet" as its published segment points (x, y below, y above), per channel
+_JET = (((0.0, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.0, 0.5, 0.5)),
+        ((0.0, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.64, 1, 1), (0.91, 0, 0), (1.0, 0, 0)),
+        ((0.0, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.0, 0, 0)))
+_JET_LUT = None
+MAX_TYPES = 16      # the kernel's cap on nr_types
+
+
+def jet_lut():
+    """uint8 [256,3] = `(plt.get_cmap("jet")(np.arange(256))[:, :3] * 255).astype("uint8")` without matplotlib: the linear
+    interpolation of a 256-entry segmented colormap (gamma 1) between `_JET`'s points, in float64, truncated like the reference does."""
+    global _JET_LUT
+    if _JET_LUT is None:
+        n = 256
+        xind = (n - 1) * np.linspace(0, 1, n)
+        lut = np.empty((n, 3), np.float64)
+        for ch, data in enumerate(_JET):
+            d = np.array(data, np.float64)
+            x, y0, y1 = d[:, 0] * (n - 1), d[:, 1], d[:, 2]
+            ind = np.searchsorted(x, xind)[1:-1]
+            dist = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+            lut[:, ch] = np.clip(np.concatenate([[y1[0]], dist * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]]), 0.0, 1.0)
+        _JET_LUT = (lut * 255).astype(np.uint8)
+        _JET_LUT.setflags(write=False)
+    return _JET_LUT
+
+
+def colorize(ch, vmin, vmax):
+    """The reference's `colorize` (run_desc.py:218-229) as float32 arithmetic and a table: clamp to [vmin, vmax], (v - vmin) /
+    float32(vmax - vmin) -- the reference's `+ 1.0e-16` vanishes in double for every range it uses --, times 256, truncated, 256 ->
+    255, looked up in `jet_lut()`; NaN -> (0, 0, 0).  uint8 [..., 3] of `np.squeeze(ch)`'s shape.  This is the definition the
+    device kernel (csrc/hvn_viz.hip) is held to."""
+    v = np.squeeze(np.asarray(ch).astype(np.float32))
+    bad = np.isnan(v)
+    v = np.where(v > vmax, np.float32(vmax), v)
+    v = np.where(v < vmin, np.float32(vmin), v)
+    with np.errstate(invalid="ignore"):
+        t = ((v - np.float32(vmin)) / np.float32(float(vmax - vmin) + 1.0e-16)) * np.float32(256.0)
+        k = np.minimum(np.where(bad, np.float32(0), t).astype(np.int64), 255)
+    out = np.array(jet_lut()[k])        # a copy also for a map that squeezes to one value
+    out[bad] = 0
+    return out
+
+
+_LUT_DEV = {}
+
+
+def strip_device(img, pred, np_map, hv_map, tp_map, sel, out=None, n_blocks=None, nr_types=None):
+    """`hvn_viz_strip` (include/hvn.h) on the current stream of `img`'s device, no host sync unless `sel` is a device tensor (then
+    one, to check it): the picture `run_desc.viz_step_output` draws, as a uint8 device tensor [n_blocks * 2h, ncol * w, 3].
+    img uint8 [n,ih,iw,3]; pred float32 [n,h,w,3] = (p_nuc, h, v), or [n,h,w,4] = (type, p_nuc, h, v) with `nr_types`; np_map int32
+    [n,h,w]; hv_map float32 [n,h,w,2]; tp_map int32 [n,h,w] or None (no TP column); all contiguous device tensors.  sel: pairs
+    (sample in the batch, block of the strip), int [n_sel,2] as a host sequence / array, or an int32 device tensor; a pair out of
+    range raises ValueError before anything is launched.  Every pair draws its block (two pairs naming one block race); the other
+    blocks keep what `out` holds (a new `out` is zeroed).  n_blocks defaults to out's, else to n_sel."""
+    import ctypes
+
+    import torch
+
+    from . import lib as L
+
+    nt = 0 if nr_types is None else int(nr_types)
+    if nr_types is not None and not 0 < nt <= MAX_TYPES:
+        raise ValueError("nr_types must be None or in [1, %d]" % MAX_TYPES)
+
+    def dev_tensor(t, dtype, what):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.device == img.device):
+            raise ValueError("%s must be a contiguous %s tensor on the image's device" % (what, dtype))
+
+    if not (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[-1] == 3 and img.is_contiguous()
+            and img.numel()):
+        raise ValueError("img must be a non-empty contiguous uint8 device tensor [n, ih, iw, 3]")
+    dev = img.device
+    n, ih, iw, _ = (int(v) for v in img.shape)
+    dev_tensor(pred, torch.float32, "pred")
+    if pred.dim() != 4 or int(pred.shape[0]) != n or int(pred.shape[3]) != (4 if nt else 3) or not pred.numel():
+        raise ValueError("pred must be [n, h, w, %d] (nr_types = %r), got %s" % (4 if nt else 3, nr_types, tuple(pred.shape)))
+    h, w, c = (int(v) for v in pred.shape[1:])
+    if ih < h or iw < w:
+        raise ValueError("the image (%d x %d) is smaller than the maps (%d x %d)" % (ih, iw, h, w))
+    dev_tensor(np_map, torch.int32, "np_map")
+    dev_tensor(hv_map, torch.float32, "hv_map")
+    if tuple(np_map.shape) != (n, h, w) or tuple(hv_map.shape) != (n, h, w, 2):
+        raise ValueError("np_map must be [n, h, w] and hv_map [n, h, w, 2]")
+    if tp_map is not None:
+        dev_tensor(tp_map, torch.int32, "tp_map")
+        if tuple(tp_map.shape) != (n, h, w):
+            raise ValueError("tp_map must be [n, h, w]")
+    ncol = 5 if nt and tp_map is not None else 4
+    if torch.is_tensor(sel) and sel.is_cuda:
+        dev_tensor(sel, torch.int32, "sel")
+        sel_dev, sel_host = sel, sel.cpu().numpy()
+    else:
+        sel_host = np.asarray(sel.cpu() if torch.is_tensor(sel) else sel, np.int64).reshape(-1, 2)
+        sel_dev = None
+    sel_host = sel_host.reshape(-1, 2)
+    n_sel = int(sel_host.shape[0])
+    if out is not None:
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev and out.dim() == 3
+                and int(out.shape[0]) % (2 * h) == 0 and int(out.shape[0]) > 0 and tuple(out.shape[1:]) == (ncol * w, 3)):
+            raise ValueError("out must be a contiguous uint8 device tensor [n_blocks * %d, %d, 3]" % (2 * h, ncol * w))
+        if n_blocks is not None and int(n_blocks) != int(out.shape[0]) // (2 * h):
+            raise ValueError("n_blocks = %d, but out holds %d blocks" % (n_blocks, int(out.shape[0]) // (2 * h)))
+        n_blocks = int(out.shape[0]) // (2 * h)
+    n_blocks = n_sel if n_blocks is None else int(n_blocks)
+    if n_blocks < 1 and n_sel == 0:
+        return torch.zeros((0, ncol * w, 3), dtype=torch.uint8, device=dev)
+    if n_blocks < 1:
+        raise ValueError("n_blocks must be at least 1")
+    if n_sel and ((sel_host[:, 0] < 0) | (sel_host[:, 0] >= n) | (sel_host[:, 1] < 0) | (sel_host[:, 1] >= n_blocks)).any():
+        raise ValueError("sel: a pair names a sample outside [0, %d) or a block outside [0, %d)" % (n, n_blocks))
+    if out is None:
+        out = torch.zeros((n_blocks * 2 * h, ncol * w, 3), dtype=torch.uint8, device=dev)
+    if n_sel == 0:
+        return out
+    L.require_gpu()
+    if sel_dev is None:
+        sel_dev = torch.from_numpy(np.ascontiguousarray(sel_host, np.int32)).to(dev, non_blocking=True)
+    lut = _LUT_DEV.get(str(dev))
+    if lut is None:
+        lut = _LUT_DEV[str(dev)] = torch.from_numpy(np.array(jet_lut())).to(dev)
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().hvn_viz_strip(img.data_ptr(), n, ih, iw, pred.data_ptr(), c, np_map.data_ptr(), hv_map.data_ptr(),
+                                      None if tp_map is None else tp_map.data_ptr(), h, w, nt, sel_dev.data_ptr(), n_sel, lut.data_ptr(),
+                                      out.data_ptr(), n_blocks, stream), "hvn_viz_strip")
+    return out
+
+
 def save_png(path, rgb):
     """uint8 [H,W,3] -> PNG.  PIL when present, else a minimal zlib writer (8-bit RGB, filter 0)."""
     rgb = np.ascontiguousarray(rgb, np.uint8)

@@ -284,6 +284,24 @@ HVN_API size_t hvn_tissue_mask_workspace_bytes(int h, int w);
 HVN_API int hvn_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
                             uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, size_t workspace_bytes, void *stream);
 
+/* -- run-loop picture: models/hovernet/run_desc.py:201-256 viz_step_output on the device, bit-equal to hover_net_amd/viz.py
+ * (csrc/hvn_viz.hip).  All pointers are device pointers; one launch on `stream`, nothing is allocated or synchronised; integer and
+ * float32 work only, so equal inputs give equal bytes.
+ * out is a strip of n_blocks blocks of 2h rows of ncol * w RGB pixels, ncol = 5 when nr_types > 0 and tp_map is not NULL (which
+ * needs c == 4), else 4.  Each pair (sample, block) of `sel` draws one block: rows [2 * block * h, 2 * block * h + 2h), the truths
+ * in the upper h rows and the predictions in the lower.  Column 0 of both is img[sample] cropped at (int((ih - h) * 0.5),
+ * int((iw - w) * 0.5)); then np_map | p_nuc over 0..1, the two planes of hv_map | pred's h, v over -1..1, and tp_map | pred's
+ * channel 0 over 0..nr_types.  A value v becomes lut[k], k = min(255, (int)(((clamp(v, vmin, vmax) - vmin) / (float)(vmax - vmin))
+ * * 256)) with a correctly rounded float32 divide; NaN becomes (0, 0, 0).  Integer maps are converted to float32 first.
+ * A pair whose sample is outside [0, n) or whose block is outside [0, n_blocks) draws nothing; bytes of out outside the named
+ * blocks are never written; two pairs that name one block race (either may win, byte by byte).  n_sel == 0 launches nothing.
+ * HVN_E_ARG (nothing launched, out untouched): a null pointer (tp_map excepted; sel only when n_sel > 0), n, h, w or n_blocks < 1,
+ * n_sel < 0 or > 65535, ih < h, iw < w, c not 3 | 4, (nr_types > 0) != (c == 4), nr_types < 0 or > 16, a misaligned pred,
+ * np_map, hv_map, tp_map or sel (4).  HVN_E_SIZE: 2h * 5w > 2^30. */
+HVN_API int hvn_viz_strip(const uint8_t *img, int n, int ih, int iw, const float *pred, int c, const int32_t *np_map, const float *hv_map,
+                          const int32_t *tp_map, int h, int w, int nr_types, const int32_t *sel, int n_sel, const uint8_t *lut,
+                          uint8_t *out, int n_blocks, void *stream);
+
 
 /* -- training step: run_desc.py:12-109 train_step (forward in train() mode, losses utils.py:54-172, backward, Adam) --
  * A training step is two hvn_top lists (forward, backward; hover_net_amd/train_plan.py lowers the network to them)
