@@ -78,3 +78,111 @@ def run_conv_case(n, xbuf_shape, xview, ybuf_shape, yview, wt, *, stride=1, pad=
     got = arena[:, b.offset:b.offset + b.size].view(n, b.h, b.w, b.c)
     want = A.tensor(b)
     return got, want
+
+
+def run_dot_conv(n, x, wt, *, stride=1, pad=(0, 0), x3=0, force_tile=None, x2=None, wt2=None, stride2=1, winograd=0):
+    """One BARE convolution -- no bn, bias, relu, prologue or residual: every output element is a dot product -- on exactly the values
+    given (tests/test_gpu_x3_budget.py).  x [n, h, w, cin] (and x2 [n, h2, w2, cin2], the fused shortcut's second K source) go into the
+    arena as they are, everything else there is NaN; wt [cout, cin, k, k] (wt2 [cout, cin2, 1, 1]) float64 or float32.  x3 = 0 | 9 | 6: the
+    fp32 pipe or the bf16x3 kernels; force_tile: the launch form.  winograd = m: the convolution as F(m x m, k x k), and the op under
+    test is its batched transform-domain product alone.
+    -> (got, a, w, A):
+       got [B, M, cout] fp32 numpy: the op's whole output (B = 1, M = n * ho * wo pixels | B = the transform positions, M = n * tiles);
+       a [B, M, K], w [B, cout, K] fp32 numpy: the operands of those dot products as the kernel got them -- a gathered (im2col) from
+           the GPU arena after the run, w unpacked from the fp32 packing the engine uploaded (and split);
+       A: the interpreter arena (plan_interp.Arena) holding what the GPU arena held before the run."""
+    from hover_net_amd.engine import Engine
+    import plan_interp
+
+    x = torch.as_tensor(np.ascontiguousarray(x, np.float32))
+    cout, cin, k, _ = wt.shape
+    _, h, w_, _ = x.shape
+    ho, wo = (h + pad[0] + pad[1] - k) // stride + 1, (w_ + pad[0] + pad[1] - k) // stride + 1
+    P = MiniPlan()
+    xv = PL.View(P.buf("x", h, w_, cin))
+    ybuf = P.buf("y", ho, wo, cout)
+    x2v = None
+    if winograd:
+        assert x2 is None and stride == 1
+        P.conv_winograd("case", xv, PL.View(ybuf), np.asarray(wt, np.float64), pad=pad, m=winograd)
+        ybuf.first = 0              # the output may not take the place of V: it is read back after the run
+    else:
+        kw = {}
+        if x2 is not None:
+            x2 = torch.as_tensor(np.ascontiguousarray(x2, np.float32))
+            x2v = PL.View(P.buf("x2", x2.shape[1], x2.shape[2], x2.shape[3]))
+            kw = dict(x2=x2v, wt2=np.asarray(wt2, np.float64), stride2=stride2)
+        P.conv("case", xv, PL.View(ybuf), np.asarray(wt, np.float64), stride=stride, pad=pad, **kw)
+    oi = [i for i, o in enumerate(P.ops) if o.kind == PL.OP_CONV]
+    assert len(oi) == 1
+    op = P.ops[oi[0]]
+    assert op.bias is None and op.pre is None and op.post is None and op.res is None and not op.relu
+    if x3:
+        assert op.tile_n in (128, 64)
+        op.extra["x3"] = x3
+    P.pack()
+    eng = Engine(P, max_batch=n, n_split=1, n_lanes=0)
+    if force_tile is not None:
+        eng.ops[oi[0]].tile_n = force_tile
+    eng.arena.fill_(float("nan"))
+    eng.buffer(xv, n).copy_(x)
+    if x2v is not None:
+        eng.buffer(x2v, n).copy_(x2)
+    A = plan_interp.Arena(P, n)
+    A.flat.copy_(eng.arena.cpu())
+    eng.run_raw(n)
+    torch.cuda.synchronize()
+    assert eng.ops[oi[0]].act_dtype == {0: 0, 9: 2, 6: 3}[x3] and (force_tile is None or eng.ops[oi[0]].tile_n == force_tile)
+    if winograd:
+        n2, t1 = op.x.buf.h, op.x.buf.w
+        v = eng.buffer(PL.View(op.x.buf), n).cpu()                                  # [n, n2, t1, cin]: what WINO_IN wrote and the product read
+        a = v.permute(1, 0, 2, 3).reshape(n2, n * t1, cin).numpy()
+        got = eng.buffer(PL.View(op.y.buf), n).cpu().permute(1, 0, 2, 3).reshape(n2, n * t1, cout).numpy()
+        wk = op.w[:, :cout].reshape(n2, cout, cin)                                  # [n2, cout_pad, cin / 32, 1, 32]
+        return got, np.ascontiguousarray(a), np.ascontiguousarray(wk), A
+    xs = eng.buffer(xv, n).cpu()
+    assert torch.equal(xs, x)
+    cols = torch.nn.functional.unfold(torch.nn.functional.pad(xs.permute(0, 3, 1, 2), (pad[0], pad[1], pad[0], pad[1])), k, stride=stride)
+    a = cols.permute(0, 2, 1).reshape(n * ho * wo, cin * k * k)                     # k index = (channel, tap), as unpack_conv orders it
+    wk = PL.unpack_conv(op.w, cout)                                                 # [cout, cin (+ cin2), taps]
+    if x2v is not None:
+        assert k == 1
+        a2 = eng.buffer(x2v, n).cpu()[:, ::stride2, ::stride2][:, :ho, :wo]
+        a = torch.cat([a, a2.reshape(n * ho * wo, -1)], 1)
+    got = eng.buffer(PL.View(ybuf), n).cpu().reshape(1, n * ho * wo, cout).numpy()
+    return got, np.ascontiguousarray(a.numpy())[None], np.ascontiguousarray(wk.reshape(cout, -1))[None], A
+
+
+def view_of(t, step=1):
+    """hvn_view over a whole contiguous [N, H, W, C] cuda tensor (every step-th pixel)."""
+    from hover_net_amd import lib as L
+    n, H, W, C = t.shape
+    v = L.hvn_view()
+    v.base = t.data_ptr()
+    v.sn, v.sy, v.sx = H * W * C, step * W * C, step * C
+    v.h, v.w, v.c, v.sc = (H + step - 1) // step, (W + step - 1) // step, C, 1
+    return v
+
+
+def run_train_ops(tops, batch, stored_parts=False):
+    """hvn_run_train_plan over `tops` (cross-workgroup sums by fp32 atomics), or -- stored_parts -- hvn_run_train_plan_ws with the
+    workspace it asks for (per-split copies added in a fixed order).  -> the workspace's size in bytes (0: no split summed anything)."""
+    import ctypes
+
+    from hover_net_amd import lib as L
+    L.require_gpu()
+    lib = L.lib()
+    arr = (L.hvn_top * len(tops))()
+    for i, t in enumerate(tops):
+        ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(t), ctypes.sizeof(L.hvn_top))
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    need = 0
+    if stored_parts:
+        need = int(lib.hvn_train_workspace_bytes(arr, len(tops), batch))
+        ws = torch.full((need // 4 + 64,), float("nan"), device="cuda")
+        rc = lib.hvn_run_train_plan_ws(arr, len(tops), batch, stream, ctypes.c_void_p(ws.data_ptr()), need)
+    else:
+        rc = lib.hvn_run_train_plan(arr, len(tops), batch, stream)
+    assert rc == 0, lib.hvn_train_last_error().decode()
+    torch.cuda.synchronize()
+    return need
