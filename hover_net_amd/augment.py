@@ -131,7 +131,8 @@ def _cropping_center(x, crop_shape):
 class DevicePatchLoader:
     """`FileLoader` + `DataLoader` of the training run (run_train.py:106-133) as one object over a patch set resident in HBM.
 
-    patches: list of `.npy` paths or one uint8/int32 array [P,H,W,5] (RGB, instance id, type -- train_loader.py:84-89).
+    patches: list of `.npy` paths or one uint8/int32 array [P,H,W,5] (RGB, instance id, type -- train_loader.py:84-89);
+    `DevicePatchLoader.from_images` takes the whole images those patches were cut from instead.
     Iterating yields `batch_size` feed dicts per step on the device: {"img" uint8 [B,ih,iw,3], "np_map" int32 [B,mh,mw],
     "hv_map" float32 [B,mh,mw,2], "tp_map" int32 [B,mh,mw] (with_type)} -- what `run_desc.train_step` / `valid_step` consume.
     mode "train": shuffled every epoch, ragged last batch dropped (DataLoader(shuffle=True, drop_last=True)); "valid": in order,
@@ -158,18 +159,52 @@ class DevicePatchLoader:
             assert data.ndim == 4 and data.shape[-1] >= 4, "patches: [P, H, W, 5] = RGB + instance id (+ type)"
             self.img = torch.from_numpy(np.ascontiguousarray(data[..., :3]).astype(np.uint8)).to(self.device)
             self.ann = torch.from_numpy(np.ascontiguousarray(data[..., 3:5]).astype(np.int32)).to(self.device)
+        self.store = None
+        self._configure(input_shape, mask_shape, batch_size, mode, with_type, seed, rank, world)
+
+    def _configure(self, input_shape, mask_shape, batch_size, mode, with_type, seed, rank, world):
         self.with_type = bool(with_type)
         if self.with_type:
-            assert self.ann.shape[-1] == 2, "with_type needs the type plane (channel 4)"
+            assert (self.ann.shape[-1] if self.store is None else self.store.c) == 2, "with_type needs the type plane (channel 4)"
         self.input_shape, self.mask_shape = tuple(int(v) for v in input_shape), tuple(int(v) for v in mask_shape)
         self.batch_size, self.mode = int(batch_size), mode
         self.seed, self.rank, self.world = int(seed), int(rank), int(world)
         self.epoch = 0
 
+    @classmethod
+    def from_images(cls, images, anns, input_shape, mask_shape, batch_size, win=(540, 540), step=(164, 164), kind="mirror", mode="train",
+                    with_type=False, seed=0, device="cuda", rank=0, world=1):
+        """The same loader over WHOLE images (`patching.ImageStore`: uint8 [H_i,W_i,3] images, int32 [H_i,W_i,1|2] annotations): its
+        patches are the ones extract_patches.py would have written with (win, step, kind), in that order, and are read through the
+        store's tables instead of being stored (~(win / step)^2 times fewer resident bytes).  Epoch order, rank slices, parameter draws
+        and noise are those of the constructor's form, so both forms yield the same batches for the same seed."""
+        from . import patching
+
+        assert mode in ("train", "valid")
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        self.img = self.ann = None
+        self.store = patching.ImageStore(images, anns, win, step, kind, device=self.device)
+        self._configure(input_shape, mask_shape, batch_size, mode, with_type, seed, rank, world)
+        return self
+
+    def _source(self):
+        """(patches, patch height, patch width) of whichever form holds the data."""
+        if self.store is not None:
+            return (self.store.n_patches,) + self.store.win
+        return tuple(self.img.shape[:3])
+
+    def _gather(self, prm):
+        if self.store is not None:
+            from . import patching
+
+            return patching.augment_shape_images(self.store, prm, self.input_shape)
+        return augment_shape(self.img, self.ann, prm, self.input_shape)
+
     def _share(self):
         """Patches per epoch on this rank: train = the same count on every rank (P // world, like DistributedSampler(drop_last=True) --
         `train.run_phases` refuses ranks that disagree on the number of steps: their collectives would not pair up); valid = every patch."""
-        p = self.img.shape[0]
+        p = self._source()[0]
         return p // self.world if self.mode == "train" else len(range(self.rank, p, self.world))
 
     def __len__(self):
@@ -184,7 +219,7 @@ class DevicePatchLoader:
     def batch(self, prm, noise=None, generator=None):
         """The device pipeline for one batch of parameter records.  `noise` / `generator`: the N(0,1) samples of the additive-noise
         records, or the torch device generator to draw them with (the loader seeds one per epoch and rank)."""
-        img, ann = augment_shape(self.img, self.ann, prm, self.input_shape)
+        img, ann = self._gather(prm)
         if (prm["kind"] != 3).any() or (prm["order"] >= 0).any():
             if noise is None and (prm["kind"] == 2).any():
                 noise = torch.randn((len(prm),) + self.input_shape + (3,), dtype=torch.float32, device=self.device, generator=generator)
@@ -196,7 +231,7 @@ class DevicePatchLoader:
         return feed
 
     def __iter__(self):
-        p, h, w = self.img.shape[:3]
+        p, h, w = self._source()
         order_rng = np.random.default_rng([self.seed, self.epoch])                 # the same permutation on every rank
         rng = np.random.default_rng([self.seed, self.epoch, self.rank + 1])        # this rank's augmentation draws
         gen = None
@@ -210,3 +245,5 @@ class DevicePatchLoader:
             src = mine[b * self.batch_size:(b + 1) * self.batch_size]
             prm = draw_params(rng, src, h, w) if self.mode == "train" else identity_params(len(src), src)
             yield self.batch(prm, generator=gen)
+        if self.store is not None and self.device.type == "cuda":
+            self.store.check()                                                      # one read per epoch: no sample was refused by the kernel

@@ -10,6 +10,8 @@
 //                     the sampled order, per pixel on the cropped image.
 // Both are byte movers on < 1 MB per sample (HBM / L2 bound; no MFMA).  The parameters of every sample are drawn on the host
 // (`hover_net_amd/augment.py`) and arrive as one `hvn_aug_sample` record per output sample.
+//   hvn_aug_shape_images_k   the shape gather over whole images in place of the patch set (`hover_net_amd/patching.py`): the
+//                     patches extract_patches.py would have written are windows of reflect-padded images and are never stored.
 // Arithmetic mirrors oracle/augment_np.py operation for operation (float64 where numpy promotes to float64, float32 in the
 // HSV -> RGB step, integer tables for RGB -> HSV / grey), so the parity tests are bit-exact.
 #include <hip/hip_runtime.h>
@@ -43,6 +45,71 @@ __global__ __launch_bounds__(AUG_T) void hvn_aug_shape_k(const uint8_t *img, con
     if (ok) {
         const long src = ((long)s.src * H + (long)fy) * W + (long)fx;
         const uint8_t *si = img + src * 3;
+        di[0] = si[0];
+        di[1] = si[1];
+        di[2] = si[2];
+        for (int c = 0; c < C; ++c) da[c] = ann[src * C + c];
+    } else {
+        di[0] = di[1] = di[2] = 0;
+        for (int c = 0; c < C; ++c) da[c] = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same gather with the resident set replaced by WHOLE images (misc/patch_extractor.py:58-133 folded in): patch `src` is the
+// win_h x win_w window at (row, col) of image `image`'s reflect-padded plane, so the patch frame's (fy, fx) reads image row
+// refl(row + fy), column refl(col + fx) -- hvn_reflect's index map (hvn_net_ops.hip), numpy "reflect" for any pad width.  For
+// "valid" windows the mirror is the identity.  Every index taken from memory is checked before it is used: a sample whose
+// chain src -> patch -> image -> pixels leaves the declared tables is written as zeros and counted once in status[0].
+__device__ inline int aug_reflect(long i, int n)
+{
+    if (n == 1) return 0;
+    const long p = 2 * ((long)n - 1);
+    long j = i % p;
+    if (j < 0) j += p;
+    return (int)(j < n ? j : p - j);
+}
+
+__global__ __launch_bounds__(AUG_T) void hvn_aug_shape_images_k(const uint8_t *pix, const int32_t *ann, const hvn_image_rec *images,
+                                                                 const hvn_patch_rec *patches, int n_images, int n_patches, long total_pixels, int H,
+                                                                 int W, int C, const hvn_aug_sample *prm, int oh, int ow, int y0, int x0, uint8_t *oimg,
+                                                                 int32_t *oann, int32_t *status, long total)
+{
+    const long i = (long)blockIdx.x * AUG_T + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % ow);
+    const long t = i / ow;
+    const int y = (int)(t % oh);
+    const int n = (int)(t / oh);
+    const hvn_aug_sample &s = prm[n];
+    uint8_t *di = oimg + i * 3;
+    int32_t *da = oann + i * C;
+    bool ok = s.src >= 0 && s.src < n_patches;
+    hvn_patch_rec pr = {0, 0, 0};
+    hvn_image_rec im = {0, 0, 0};
+    if (ok) {
+        pr = patches[s.src];
+        ok = pr.image >= 0 && pr.image < n_images;
+    }
+    if (ok) {
+        im = images[pr.image];
+        ok = im.h > 0 && im.w > 0 && im.offset >= 0 && im.offset <= total_pixels && (long)im.h * im.w <= total_pixels - im.offset;
+    }
+    if (!ok) {
+        if (x == 0 && y == 0 && status) atomicAdd(status, 1);
+        di[0] = di[1] = di[2] = 0;
+        for (int c = 0; c < C; ++c) da[c] = 0;
+        return;
+    }
+    const int xs = s.flip_lr ? ow - 1 - x : x;
+    const int ys = s.flip_ud ? oh - 1 - y : y;
+    const double xd = (double)(xs + x0), yd = (double)(ys + y0);
+    const double sxf = s.inv[0] * xd + s.inv[1] * yd + s.inv[2];
+    const double syf = s.inv[3] * xd + s.inv[4] * yd + s.inv[5];
+    const double fx = floor(sxf + 0.5), fy = floor(syf + 0.5);
+    if (fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H) {
+        const long src = im.offset + (long)aug_reflect((long)pr.row + (long)fy, im.h) * im.w + aug_reflect((long)pr.col + (long)fx, im.w);
+        const uint8_t *si = pix + src * 3;
         di[0] = si[0];
         di[1] = si[1];
         di[2] = si[2];
@@ -202,6 +269,17 @@ int hvn_launch_aug_shape(const uint8_t *img, const int32_t *ann, int h, int w, i
     const int y0 = (int)((h - oh) * 0.5), x0 = (int)((w - ow) * 0.5);   // cropping_center / CropToFixedSize(position="center")
     hipLaunchKernelGGL(hvn_aug_shape_k, dim3((unsigned)((total + AUG_T - 1) / AUG_T)), dim3(AUG_T), 0, stream, img, ann, h, w, c, prm, oh, ow, y0, x0,
                        oimg, oann, total);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int hvn_launch_aug_shape_images(const uint8_t *pix, const int32_t *ann, const hvn_image_rec *images, const hvn_patch_rec *patches, int n_images,
+                                int n_patches, long total_pixels, int win_h, int win_w, int c, const hvn_aug_sample *prm, int n, int oh, int ow,
+                                uint8_t *oimg, int32_t *oann, int32_t *status, hipStream_t stream)
+{
+    const long total = (long)n * oh * ow;
+    const int y0 = (int)((win_h - oh) * 0.5), x0 = (int)((win_w - ow) * 0.5);   // the crop of hvn_launch_aug_shape, in the patch frame
+    hipLaunchKernelGGL(hvn_aug_shape_images_k, dim3((unsigned)((total + AUG_T - 1) / AUG_T)), dim3(AUG_T), 0, stream, pix, ann, images, patches,
+                       n_images, n_patches, total_pixels, win_h, win_w, c, prm, oh, ow, y0, x0, oimg, oann, status, total);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

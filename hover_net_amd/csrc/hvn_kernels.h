@@ -322,6 +322,11 @@ int hvn_launch_valid_stats(const float *pred, const int32_t *np_map, const float
 struct hvn_aug_sample;   // include/hvn.h
 int hvn_launch_aug_shape(const uint8_t *img, const int32_t *ann, int h, int w, int c, const struct hvn_aug_sample *prm, int n, int oh, int ow,
                          uint8_t *oimg, int32_t *oann, hipStream_t stream);
+struct hvn_image_rec;
+struct hvn_patch_rec;
+int hvn_launch_aug_shape_images(const uint8_t *pix, const int32_t *ann, const struct hvn_image_rec *images, const struct hvn_patch_rec *patches,
+                                int n_images, int n_patches, long total_pixels, int win_h, int win_w, int c, const struct hvn_aug_sample *prm, int n,
+                                int oh, int ow, uint8_t *oimg, int32_t *oann, int32_t *status, hipStream_t stream);
 int hvn_launch_aug_input(const uint8_t *src, const struct hvn_aug_sample *prm, const float *noise, int n, int h, int w, uint8_t *dst, hipStream_t stream);
 size_t hvn_targets_ws_bytes(int n, int h, int w);
 int hvn_launch_gen_targets(const int32_t *ann, int n, int h, int w, int ch, int cw, float *hv, int32_t *np_map, void *ws, size_t ws_bytes,

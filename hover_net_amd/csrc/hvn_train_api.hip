@@ -315,6 +315,19 @@ int hvn_augment_shape(const uint8_t *img, const int32_t *ann, int n_resident, in
     return rc ? tfail(HVN_E_LAUNCH, "augment_shape launch failed", -1) : 0;
 }
 
+int hvn_augment_shape_images(const uint8_t *pixels, const int32_t *ann, const hvn_image_rec *images, const hvn_patch_rec *patches, int n_images,
+                             int n_patches, int64_t total_pixels, int win_h, int win_w, int c, const hvn_aug_sample *prm, int n, int out_h, int out_w,
+                             uint8_t *out_img, int32_t *out_ann, int32_t *status, void *stream)
+{
+    if (!pixels || !ann || !images || !patches || !prm || !out_img || !out_ann || n_images <= 0 || n_patches <= 0 || total_pixels <= 0 ||
+        total_pixels >= (1LL << 40) || n <= 0 || win_h <= 0 || win_w <= 0 || c < 1 || c > 4 || out_h <= 0 || out_w <= 0 || out_h > win_h ||
+        out_w > win_w || (((uintptr_t)images) & 7) || (((uintptr_t)patches | (uintptr_t)status) & 3))
+        return tfail(HVN_E_ARG, "augment_shape_images: bad arguments", -1);
+    int rc = hvn_launch_aug_shape_images(pixels, ann, images, patches, n_images, n_patches, (long)total_pixels, win_h, win_w, c, prm, n, out_h, out_w,
+                                         out_img, out_ann, status, (hipStream_t)stream);
+    return rc ? tfail(HVN_E_LAUNCH, "augment_shape_images launch failed", -1) : 0;
+}
+
 int hvn_augment_input(const uint8_t *src, const hvn_aug_sample *prm, const float *noise, int n, int h, int w, uint8_t *dst, void *stream)
 {
     if (!src || !prm || !dst || src == dst || n <= 0 || h <= 0 || w <= 0) return tfail(HVN_E_ARG, "augment_input: bad arguments", -1);

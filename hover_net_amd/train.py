@@ -112,6 +112,36 @@ def device_loaders(train_patches, valid_patches, mode, with_type, seed=0, device
     return make
 
 
+def image_loaders(train_set, valid_set, mode, with_type, win=(540, 540), step=(164, 164), kind="mirror", seed=0, device=None):
+    """`device_loaders` without the offline extract_patches.py run: `*_set` = (images, anns), lists of uint8 [H_i,W_i,3] and int32
+    [H_i,W_i,1|2] arrays (`dataset.get_dataset(name).load_img / load_ann`), or None.  The whole images are uploaded once per split
+    (`augment.DevicePatchLoader.from_images`) and the (win, step, kind) patches are read out of them by the augmentation gather."""
+    from . import augment
+
+    act, out = ((270, 270), (80, 80)) if mode == "original" else ((256, 256), (164, 164))
+    rank, world = _dist_info()
+    if device is None:
+        device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
+    cache = {}
+
+    def make(phase_idx, batch_size):
+        out_d = {}
+        for split, data in (("train", train_set), ("valid", valid_set)):
+            if data is None:
+                out_d[split] = None
+                continue
+            if split not in cache:
+                cache[split] = augment.DevicePatchLoader.from_images(data[0], data[1], act, out, batch_size[split], win=win, step=step, kind=kind,
+                                                                     mode=split, with_type=with_type, seed=seed, device=device, rank=rank,
+                                                                     world=world)
+            ld = cache[split]
+            ld.batch_size = int(batch_size[split])      # phase 1 runs smaller batches over the same resident images
+            out_d[split] = ld
+        return out_d
+
+    return make
+
+
 def _dist_info():
     import torch.distributed as dist
 

@@ -447,6 +447,25 @@ typedef struct hvn_aug_sample {
  * out_ann: dev int32 [n][oh][ow][c]; prm: dev hvn_aug_sample[n] with 0 <= src < P. */
 HVN_API int hvn_augment_shape(const uint8_t *img, const int32_t *ann, int n_resident, int h, int w, int c, const hvn_aug_sample *prm, int n,
                               int out_h, int out_w, uint8_t *out_img, int32_t *out_ann, void *stream);
+/* The same gather over WHOLE images instead of an extracted patch set (extract_patches.py + misc/patch_extractor.py:58-133 folded in).
+ * pixels: dev uint8 [total_pixels][3] and ann: dev int32 [total_pixels][c], the images back to back, row-major; images: dev
+ * hvn_image_rec[n_images] (offset in pixels; offset + h * w <= total_pixels); patches: dev hvn_patch_rec[n_patches], the window
+ * [row, row + win_h) x [col, col + win_w) of image `image` in UNPADDED coordinates (negative / past the edge = the mirror pad).
+ * Patch frame arithmetic is hvn_augment_shape's with h = win_h, w = win_w; the pixel then comes from image row refl(row + fy, h_i),
+ * column refl(col + fx, w_i), refl = numpy "reflect" as an index map (period 2(n - 1); n == 1 -> 0).  prm[k].src indexes `patches`.
+ * The kernel checks 0 <= src < n_patches, 0 <= image < n_images, h, w > 0 and the image's extent against total_pixels before it
+ * reads through them: a sample that fails is written as zeros and, when status != NULL, adds 1 to status[0] (dev int32, zeroed by
+ * the caller). */
+typedef struct hvn_image_rec {
+    int64_t offset;            /* first pixel of the image in `pixels` / `ann` */
+    int32_t h, w;
+} hvn_image_rec;
+typedef struct hvn_patch_rec {
+    int32_t image, row, col;
+} hvn_patch_rec;
+HVN_API int hvn_augment_shape_images(const uint8_t *pixels, const int32_t *ann, const hvn_image_rec *images, const hvn_patch_rec *patches,
+                                     int n_images, int n_patches, int64_t total_pixels, int win_h, int win_w, int c, const hvn_aug_sample *prm,
+                                     int n, int out_h, int out_w, uint8_t *out_img, int32_t *out_ann, int32_t *status, void *stream);
 /* src / dst: dev uint8 [n][h][w][3] (must not alias: the blurs read neighbours); noise: dev float32 [n][h][w][3] standard normal samples
  * (may be NULL when no record has kind 2). */
 HVN_API int hvn_augment_input(const uint8_t *src, const hvn_aug_sample *prm, const float *noise, int n, int h, int w, uint8_t *dst, void *stream);
