@@ -146,7 +146,9 @@ class InferManager:
     def process_file_list(self, run_args):
         """run_args (run_infer.py:134-172): input_dir, output_dir, batch_size, mem_usage, draw_dot, save_qupath, save_raw_map,
         patch_input_shape, patch_output_shape (+ nr_inference_workers, nr_post_proc_workers: ignored); device_overlay (default
-        False): rank 0 draws `overlay/` on the GPU (`viz.visualize_instances_dict(device=...)`, the same pixels).
+        False): rank 0 draws `overlay/` on the GPU (`viz.visualize_instances_dict(device=...)`, the same pixels); save_features
+        (default False): every nucleus of `json/` gains "features" (`features.derive`: shape and colour; `.mat`, overlay and
+        qupath are as without it).
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
@@ -159,6 +161,7 @@ class InferManager:
         draw_dot = bool(run_args.get("draw_dot", False))
         save_qupath = bool(run_args.get("save_qupath", False))
         save_raw_map = bool(run_args.get("save_raw_map", False))
+        save_features = bool(run_args.get("save_features", False))
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -170,7 +173,8 @@ class InferManager:
             for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
-            images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map))
+            images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
+            **({"return_features": True} if save_features else {})))
         done = []
         self.rounds = []                                   # files per caching round (inspected by the tests)
         while pending:
@@ -265,7 +269,8 @@ class WsiManager(InferManager):
         tile_shape, save_thumb, save_mask, batch_size; base_mag (optional): the magnification the files are AT, a number or a
         {slide stem: number} mapping (a slide the mapping lacks is a "crash") -- a slide whose base_mag differs from proc_mag is resampled to proc_mag as it is read
         (`open_slide`); absent = the files are taken as they are; device_mask (default False): a slide without a mask file takes its
-        tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`, the same bytes on every rank).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`, the same bytes on every rank); save_features (default False): every nucleus of the json
+        gains "features" (`features.derive`, shape features only: colour features on slides are out of scope).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
@@ -312,7 +317,8 @@ class WsiManager(InferManager):
                 else:
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
-                                                 ambiguous_size=int(run_args.get("ambiguous_size", 128)))
+                                                 ambiguous_size=int(run_args.get("ambiguous_size", 128)),
+                                                 **({"features": True} if run_args.get("save_features", False) else {}))
                     _inst_map, inst_info = wsi.run(slide, mask)
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)

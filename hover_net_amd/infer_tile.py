@@ -305,14 +305,17 @@ def result_to_arrays(inst_h, rec_h, nr_types, contours_flat=None):
     return [np.ascontiguousarray(inst_h, np.int32), rec_h.view(np.uint8).reshape(rec_h.shape[0], rec_h.dtype.itemsize), pts, offs]
 
 
-def arrays_to_result(arrs, nr_types, with_info=True, shift_xy=None):
+def arrays_to_result(arrs, nr_types, with_info=True, shift_xy=None, *, feat_b=None, with_colour=False):
+    """`feat_b`: the item's feature bytes (`PostProc.features`, uint8 [max_inst, sizeof(hvn_inst_feat)]) -- the dict entries gain
+    "features" (`post_proc.records_to_dict(feat_host=...)`)."""
     from . import post_proc
 
     inst_h, rec_b, pts, offs = arrs
     if not with_info:
         return np.array(inst_h), None
     rec_h = np.ascontiguousarray(rec_b).view(post_proc._REC_DTYPE).reshape(-1)
-    return np.array(inst_h), post_proc.records_to_dict(rec_h, nr_types, contours_flat=(np.array(pts), np.array(offs)), shift_xy=shift_xy)
+    return np.array(inst_h), post_proc.records_to_dict(rec_h, nr_types, contours_flat=(np.array(pts), np.array(offs)), shift_xy=shift_xy,
+                                                       feat_host=feat_b, with_colour=with_colour)
 
 
 def run_sharded(items, step_fn, batch_size, gather=True):
@@ -333,11 +336,15 @@ def run_sharded(items, step_fn, batch_size, gather=True):
 
 
 # --------------------------------------------------------------------------------------------
-def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384):
+def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384, *,
+                   return_features=False):
     """images: list of uint8 [H,W,3] arrays (RGB).  Returns a list of (pred_inst int32 [H,W] numpy, inst_info_dict | None)
     in input order: complete on rank 0 (the writer); the other ranks hold their own images' results and None elsewhere.
     `return_raw=True` appends the stitched float32 prediction map [H,W,3|4] to each tuple (`--save_raw_map`,
     infer/tile.py:193-194); it travels to rank 0 with the other arrays.
+    `return_features=True` (implies the instance dict) adds "features" to every dict entry: shape and colour features of the
+    nucleus (`features.derive`) from one more pass over the instance map and the image this call uploaded anyway
+    (`PostProc.features`); the feature bytes travel to rank 0 as one more array of the item.
     The images are worked off in groups of at most `max_patches` network patches (3.6 GB of uint8 patches + 1.7 GB of maps at the
     default), so that a large cache round of `process_file_list` never has all its overlapping patches in HBM at once; every rank
     forms the same groups (the collectives inside stay matched)."""
@@ -355,35 +362,41 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         groups.append(cur)
     out = [None] * len(images)
     for grp in groups:
-        for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids, return_raw)):
+        more = {"return_features": True} if return_features else {}
+        for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
+                                                    return_raw, **more)):
             out[i] = res
     return out
 
 
-def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw):
+def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False):
     """One group of `process_images`.
 
     Pipeline per call: patch extraction -> sharded HIP network (`run_desc.infer_step_device`)
     -> one all_to_all of the per-patch maps to the images' owners (`route_to_owners`) -> per-image stitch on the GPU -> on-GPU instance
     separation + instance table (`post_proc.process_batch_device`) for the images this rank owns
-    -> tensor gather of instance maps / record tables / contours to rank 0 (`gather_items_to_rank0`)."""
+    -> tensor gather of instance maps / record tables / contours to rank 0 (`gather_items_to_rank0`).
+    An item's arrays: [0:4] `result_to_arrays`, [4] the raw map with `return_raw`, LAST the feature bytes with `return_features`."""
     from . import post_proc, run_desc
 
     net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
     win = 270 if net.mode == "original" else 256
     msk = 80 if net.mode == "original" else 164   # run_infer.py:145-150
     dev = next(net.parameters()).device
-    infos, patches = [], []
+    _, rank, world = _dist()
+    infos, patches, uploaded = [], [], {}
     for i, img in enumerate(images):
         if dev.type == "cuda":      # source image up once, reflect padding + overlapping crops on the GPU
             info, pad_tl = patch_grid(img.shape, win, msk)
-            patches.append(extract_patches_device(torch.from_numpy(np.ascontiguousarray(img)).to(dev), info, win, pad_tl))
+            img_dev = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+            patches.append(extract_patches_device(img_dev, info, win, pad_tl))
+            if return_features and i % world == rank:
+                uploaded[i] = img_dev           # the colour features of the images this rank owns read it again
         else:                       # host geometry (CPU tests of the sharding logic)
             padded, info = prepare_patching(img, win, msk)
             patches.append(torch.from_numpy(extract_patches(padded, info, win)))
         infos.append(info)
     all_patches = torch.cat(patches, 0)
-    _, rank, world = _dist()
     # network: contiguous patch shards; then every per-patch map goes to the ONE rank that stitches its image (image i -> rank
     # i % world) with a single all_to_all -- not to every rank
     local = run_sharded(all_patches, lambda b: run_desc.infer_step_device(b.to(dev), model), batch_size, gather=False)
@@ -396,12 +409,19 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
         n = counts[i]
         if i % world == rank:
             full = stitch(pred[k:k + n], infos[i], img.shape).contiguous()
-            inst, rec, _ = post_proc.process_batch_device(full.unsqueeze(0), nr_types, return_centroids)
+            if return_features:
+                img_dev = uploaded.pop(i) if i in uploaded else torch.from_numpy(np.ascontiguousarray(img)).to(full.device)
+                inst, rec, _, feat = post_proc.process_batch_device(full.unsqueeze(0), nr_types, True, return_features=True,
+                                                                    image=img_dev.unsqueeze(0))
+            else:
+                inst, rec, _ = post_proc.process_batch_device(full.unsqueeze(0), nr_types, return_centroids)
             inst_h = inst[0].cpu().numpy()
             rec_h = rec[0].cpu().numpy().view(post_proc._REC_DTYPE).reshape(-1) if rec is not None else np.zeros(0, post_proc._REC_DTYPE)
             mine[i] = result_to_arrays(inst_h, rec_h, nr_types)
             if return_raw:
                 mine[i].append(full.cpu().numpy())
+            if return_features:
+                mine[i].append(feat[0].cpu().numpy())
             k += n
     every = gather_items_to_rank0(mine, device=dev)          # the instance maps + record tables + contours travel as tensors to rank 0
     if every is None:                            # not rank 0: keeps only what it computed itself
@@ -411,6 +431,7 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
         if i not in every:
             out.append(None)
             continue
-        res = arrays_to_result(every[i][:4], nr_types, with_info=(return_centroids or nr_types is not None))
+        res = arrays_to_result(every[i][:4], nr_types, with_info=(return_centroids or nr_types is not None),
+                               feat_b=every[i][-1] if return_features else None, with_colour=True)
         out.append(res + (np.array(every[i][4]),) if return_raw else res)
     return out

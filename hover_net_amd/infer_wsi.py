@@ -513,8 +513,12 @@ class DeviceMerger:
 # --------------------------------------------------------------------------------------------
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
-                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False):
-        """device_mask=True: `run(slide, "auto")` takes the tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`: the
+                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False):
+        """features=True: every entry of the instance dict gains "features" (`features.derive`): the SHAPE features of the nucleus,
+        computed per post-processed tile right after its record table (`PostProc.features`, image=None) and carried wherever the
+        record bytes go (pinned slot, remote ranks, merger entries).  They are translation-invariant, so the tile origin does not
+        touch them.  Colour features on slides are out of scope: stage 2 holds the prediction map, not the slide's pixels.
+        device_mask=True: `run(slide, "auto")` takes the tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`: the
         same bytes, on every rank alike).
         device_contours=True: stage 2 traces every tile's contours on the GPU (`PostProc.contours`, same arrays as the host
         tracer) on the tile's post-processing stream instead of on the host worker thread.  The tile's instance map still goes
@@ -523,6 +527,7 @@ class WsiInference:
         more D2H bytes per tile than the default path, and each pinned slot grows by that buffer."""
         self.device_contours = bool(device_contours)
         self.device_mask = bool(device_mask)
+        self.features = bool(features)
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
@@ -659,11 +664,14 @@ class WsiInference:
         def shift_of(i):
             return (int(tiles[i][0][1]), int(tiles[i][0][0]))      # tile origin as (x, y)
 
-        def host_half(i, inst_h, rec_h, release, flat):
+        def host_half(i, inst_h, rec_h, release, flat, feat_h):
             t0 = time.perf_counter()
             arrs = infer_tile.result_to_arrays(inst_h, rec_h, self.nr_types, contours_flat=flat)   # flat: traced on the GPU, or None
             t1 = time.perf_counter()
-            out = infer_tile.arrays_to_result(arrs, self.nr_types, shift_xy=shift_of(i)) if world == 1 else [np.array(a) for a in arrs]
+            if world == 1:
+                out = infer_tile.arrays_to_result(arrs, self.nr_types, shift_xy=shift_of(i), feat_b=feat_h)
+            else:
+                out = [np.array(a) for a in arrs + ([feat_h] if feat_h is not None else [])]    # the feature bytes: one more array of the item
             release()
             if tm is not None:
                 tm["contours_s"] = tm.get("contours_s", 0.0) + (t1 - t0)
@@ -684,11 +692,11 @@ class WsiInference:
 
             def finish():
                 i, wait = inflight.popleft()
-                inst_h, rec_h, release, flat = wait()
+                inst_h, rec_h, release, flat, feat_h = wait()
                 if world == 1 and hasattr(wait, "device_result"):
                     nz = np.flatnonzero(rec_h["area"]) if rec_h.size else np.zeros(0, np.int64)
                     self._dev_results[i] = wait.device_result + (int(nz[-1]) + 1 if nz.size else 0,)      # + the tile's largest label
-                futs.append((i, pool.submit(host_half, i, inst_h, rec_h, release, flat)))
+                futs.append((i, pool.submit(host_half, i, inst_h, rec_h, release, flat, feat_h)))
 
             for i in idxs:
                 tl, br = tiles[i][0], tiles[i][1]
@@ -703,16 +711,18 @@ class WsiInference:
             every = infer_tile.gather_items_to_rank0(mine, device=self.device)
             if every is not None:
                 for i in range(tiles.shape[0]):
-                    yield (i,) + infer_tile.arrays_to_result(every[i], self.nr_types, shift_xy=shift_of(i))
+                    yield (i,) + infer_tile.arrays_to_result(every[i][:4], self.nr_types, shift_xy=shift_of(i),
+                                                             feat_b=every[i][4] if self.features else None)
 
     def _launch_tile(self, tile_map):
-        """Start the GPU half of one tile; returns wait() -> (int32 instance map, record table, release, contours) on the host.
+        """Start the GPU half of one tile; returns wait() -> (int32 instance map, record table, release, contours, feature bytes |
+        None) on the host.
         CUDA: kernels + D2H into a pinned slot are enqueued and wait() blocks on the slot's event; `release()` frees the slot
         once the host half is done with the arrays (they alias pinned memory).  contours: None (the host half traces them), or
         with `device_contours` the (pts, offs) arrays traced on this tile's stream."""
         if self.device.type != "cuda":
-            inst_h, rec_h = self._postproc_tile(tile_map)
-            return lambda: (inst_h, rec_h, lambda: None, None)
+            res = self._postproc_tile(tile_map)
+            return lambda: (res[0], res[1], lambda: None, None, res[2] if len(res) > 2 else None)
         t0 = time.perf_counter()
         # tiles alternate between a few post-processing lanes (own stream + own workspace): one tile's ~30 launches over 4-5
         # Mpixel leave most of the chip idle, two or three tiles in flight fill it
@@ -732,6 +742,11 @@ class WsiInference:
             slot = self._pinned_slot(inst[0].shape, rec[0].shape)
             slot["inst"].copy_(inst[0], non_blocking=True)
             slot["rec"].copy_(rec[0], non_blocking=True)
+            if self.features:
+                feat = pp.features(inst, rec)
+                if "feat" not in slot:
+                    slot["feat"] = torch.empty(feat[0].shape, dtype=torch.uint8, pin_memory=True)
+                slot["feat"].copy_(feat[0], non_blocking=True)
             if self.device_contours:
                 cont = pp.contours(inst, rec)
                 for k, t in zip(("pts", "offs", "cstatus"), cont):
@@ -752,7 +767,8 @@ class WsiInference:
                     with torch.cuda.stream(stream):
                         pts = pp.contours(inst, rec, int(offs[-1]))[0].cpu().numpy()
                 flat = (pts[:int(offs[-1])], offs)
-            return slot["inst"].numpy(), slot["rec"].numpy().view(post_proc._REC_DTYPE).reshape(-1), slot["free"].set, flat
+            return (slot["inst"].numpy(), slot["rec"].numpy().view(post_proc._REC_DTYPE).reshape(-1), slot["free"].set, flat,
+                    slot["feat"].numpy() if self.features else None)
 
         wait.device_result = (inst[0], slot["event"])              # for the on-device merge: the local-id map stays in HBM
         return wait
@@ -779,9 +795,11 @@ class WsiInference:
         return slot
 
     def _postproc_tile(self, tile_map):
-        """One tile of the prediction map -> (int32 instance map, record table) on the host, synchronously."""
-        inst, rec, _ = post_proc.process_batch_device(tile_map.contiguous().unsqueeze(0), self.nr_types, True)
-        return inst[0].cpu().numpy(), rec[0].cpu().numpy().view(post_proc._REC_DTYPE).reshape(-1)
+        """One tile of the prediction map -> (int32 instance map, record table) on the host, synchronously (+ the feature bytes
+        with `features`)."""
+        out = post_proc.process_batch_device(tile_map.contiguous().unsqueeze(0), self.nr_types, True, return_features=self.features)
+        res = (out[0][0].cpu().numpy(), out[1][0].cpu().numpy().view(post_proc._REC_DTYPE).reshape(-1))
+        return res + (out[3][0].cpu().numpy(),) if self.features else res
 
     def run(self, slide, mask=None):
         """slide: object with .shape / .read_region; mask: uint8 tissue mask at any scale, None = all tissue, "auto" = the

@@ -18,7 +18,7 @@ VARIANTS = {
 }
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("hvn_conv.hip", "hvn_conv_chain.hip", "hvn_conv_chain_x3.hip", "hvn_conv_chain_x3r.hip", "hvn_conv_bf16.hip", "hvn_conv_bf16g.hip", "hvn_conv_chain_bf16.hip", "hvn_conv_x3.hip", "hvn_conv_x3g.hip", "hvn_net_ops.hip", "hvn_postproc.hip", "hvn_api.hip", "hvn_train.hip", "hvn_wgrad_x3.hip", "hvn_targets.hip", "hvn_wsi_merge.hip",
-           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_contour_dev.hip", "hvn_metrics.hip", "hvn_valid.hip", "hvn_overlay.hip", "hvn_resample.hip", "hvn_tissue.hip", "hvn_viz.hip")
+           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_contour_dev.hip", "hvn_metrics.hip", "hvn_valid.hip", "hvn_overlay.hip", "hvn_resample.hip", "hvn_tissue.hip", "hvn_viz.hip", "hvn_features.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                "-fvisibility=hidden", "-Wno-unused-value", "-pthread")
 
@@ -63,6 +63,12 @@ class hvn_inst_rec(ctypes.Structure):
                 ("type", ctypes.c_int32), ("type_count", ctypes.c_int32)]
 
 
+class hvn_inst_feat(ctypes.Structure):
+    """One slot of hvn_instance_features (include/hvn.h), parallel to hvn_inst_rec."""
+    _fields_ = [("sxx", ctypes.c_int64), ("syy", ctypes.c_int64), ("sxy", ctypes.c_int64), ("seen", ctypes.c_int32),
+                ("per", ctypes.c_int32 * 3), ("csum", ctypes.c_int64 * 3), ("csq", ctypes.c_int64 * 3)]
+
+
 EXPORTS = (
     "hvn_version", "hvn_build_id", "hvn_last_error", "hvn_device_ok", "hvn_run_plan", "hvn_run_op", "hvn_profile_enable",
     "hvn_profile_conv_ms", "hvn_profile_conv_launches", "hvn_profile_conv_ms_list", "hvn_postproc_workspace_bytes", "hvn_postproc",
@@ -78,6 +84,7 @@ EXPORTS = (
     "hvn_resize_window",
     "hvn_tissue_gray_hist", "hvn_tissue_mask_workspace_bytes", "hvn_tissue_mask",
     "hvn_viz_strip",
+    "hvn_instance_features_workspace_bytes", "hvn_instance_features",
 )
 
 
@@ -261,6 +268,10 @@ def lib():
         L.hvn_viz_strip.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.hvn_instance_features_workspace_bytes.restype = ctypes.c_size_t
+        L.hvn_instance_features_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.hvn_instance_features.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.hvn_extract_patches.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.hvn_gen_targets_workspace_bytes.restype = ctypes.c_size_t

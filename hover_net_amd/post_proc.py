@@ -23,7 +23,18 @@ import ctypes
 import numpy as np
 import torch
 
+from . import features as F
 from . import lib as L
+
+
+def _check_image(image, nhw, device):
+    """The RGB image that goes with `nhw` = (N, h, w) label maps on `device`: uint8 device tensor [N,h,w,3]."""
+    if not torch.is_tensor(image) or image.dtype != torch.uint8:
+        raise TypeError("image must be a uint8 tensor, got %s" % (image.dtype if torch.is_tensor(image) else type(image).__name__))
+    if tuple(image.shape) != tuple(nhw) + (3,):
+        raise ValueError("image %s does not match the maps: expected %s" % (tuple(image.shape), tuple(nhw) + (3,)))
+    if image.device != device:
+        raise ValueError("image is on %s, the maps on %s" % (image.device, device))
 
 
 class PostProc:
@@ -36,6 +47,7 @@ class PostProc:
         self._tws = None
         self._cws = None
         self._cpin = None
+        self._fws = None
 
     def _workspace(self, n, h, w):
         need = L.lib().hvn_postproc_workspace_bytes(n, h, w)
@@ -124,6 +136,33 @@ class PostProc:
                                                   stream), "hvn_trace_contours_device")
         return pts, offs, status
 
+    def features(self, inst, rec, image=None):
+        """The morphometric sums of every record (hvn_instance_features) on the current stream, no host sync.
+        inst: int32 device tensor [N,h,w]; rec: `table`'s records [N,max_inst,sizeof(rec)]; image: uint8 device tensor [N,h,w,3]
+        (RGB; adds the colour sums) or None.  -> uint8 device tensor [N,max_inst,sizeof(hvn_inst_feat)]: `features.FEAT_DTYPE`
+        slots parallel to the records; `features.derive` makes the float features of them on the host.  Any label map is valid;
+        a table that was not made from `inst` shows as seen != area."""
+        if not (torch.is_tensor(inst) and inst.dtype == torch.int32 and inst.dim() == 3 and inst.is_cuda):
+            raise ValueError("inst must be an int32 device tensor [N,h,w]")
+        n, h, w = inst.shape
+        if not (torch.is_tensor(rec) and rec.dtype == torch.uint8 and rec.dim() == 3 and rec.is_cuda and rec.shape[0] == n
+                and rec.shape[2] == ctypes.sizeof(L.hvn_inst_rec)):
+            raise ValueError("record table does not belong to %d maps" % n)
+        if image is not None:
+            _check_image(image, (n, h, w), inst.device)
+            image = image.contiguous()
+        inst, rec = inst.contiguous(), rec.contiguous()
+        max_inst = rec.shape[1]
+        need = L.lib().hvn_instance_features_workspace_bytes(n, h, w, max_inst)
+        if need and (self._fws is None or self._fws.numel() < need):
+            self._fws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        feat = torch.empty((n, max_inst, ctypes.sizeof(L.hvn_inst_feat)), dtype=torch.uint8, device=self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hvn_instance_features(inst.data_ptr(), image.data_ptr() if image is not None else None, n, h, w, rec.data_ptr(),
+                                              max_inst, feat.data_ptr(), self._fws.data_ptr() if need else None, need, stream),
+                "hvn_instance_features")
+        return feat
+
     def _pinned(self, like):
         """Pinned host buffers for `contours`' three outputs (kept: pinned allocations are slow)."""
         if self._cpin is None or any(b.numel() < t.numel() for b, t in zip(self._cpin, like)):
@@ -145,11 +184,17 @@ def _pp(device):
     return _DEFAULT[key]
 
 
-def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False):
+def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False, *, return_features=False, image=None):
     """pred_dev [N,h,w,3|4] float32 on the GPU -> (inst int32 [N,h,w] device tensor,
     records device tensor | None, counts device tensor | None); with return_contours=True the tuple gains
     `PostProc.contours`' (pts, offs, status) device tensors (None each when there is no record table); records, pts and offs
-    in that form are what `viz.overlay_from_records` draws without leaving the device."""
+    in that form are what `viz.overlay_from_records` draws without leaving the device.  return_features=True appends
+    `PostProc.features`' tensor as the LAST element (None when there is no record table); `image` (uint8 device tensor
+    [N,h,w,3]) adds the colour sums."""
+    if image is not None and not return_features:
+        raise ValueError("image is only used with return_features=True")
+    if image is not None:       # refuse a bad image before anything is launched
+        _check_image(image, tuple(pred_dev.shape[:3]), pred_dev.device)
     pp = _pp(pred_dev.device)
     inst = pp.separate(pred_dev)
     out = (inst, None, None)
@@ -157,6 +202,8 @@ def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return
         out = (inst,) + pp.table(inst, pred_dev.contiguous(), nr_types)
     if return_contours:
         out += pp.contours(inst, out[1]) if out[1] is not None else (None, None, None)
+    if return_features:
+        out += (pp.features(inst, out[1], image) if out[1] is not None else None,)
     return out
 
 
@@ -227,7 +274,7 @@ def trace_contours(inst_host, rec_host):
     return {int(rec_host["label"][i]): pts[offs[i]:offs[i + 1]].copy() for i in range(rec_host.shape[0]) if rec_host["area"][i] > 0}
 
 
-def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shift_xy=None):
+def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shift_xy=None, *, feat_host=None, with_colour=False):
     """One tile's records (numpy structured array) -> the reference's inst_info_dict.  With `inst_host`
     the contours are traced too (or taken from `contours_flat` = trace_contours_flat's result, e.g. traced on another
     rank) and, like the reference (post_proc.py:140-143), instances whose contour
@@ -235,8 +282,17 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
     computed for the whole tile at once; only the dict assembly is a python loop (a WSI has ~10^6 instances).
     `shift_xy` = (x0, y0): the tile's origin in the slide, added to bbox, centroid and contour the way the WSI merge
     callbacks do (wsi.py:580-584: `+ top_left` with top_left = (x, y) on all three, i.e. x is added to the bbox ROWS --
-    the reference's quirk, kept) -- vectorised here instead of three small-array additions per instance there."""
+    the reference's quirk, kept) -- vectorised here instead of three small-array additions per instance there.
+    `feat_host` (`features.FEAT_DTYPE` slots parallel to `rec_host`, from `PostProc.features`) adds "features": {...}
+    (`features.derive`; the colour entries with `with_colour`) to every entry; they are translation-invariant, `shift_xy` does
+    not touch them."""
     r = rec_host[rec_host["area"] > 0]
+    feats = None
+    if feat_host is not None:
+        feat_host = np.ascontiguousarray(feat_host).view(F.FEAT_DTYPE).reshape(-1)
+        if feat_host.shape != rec_host.shape:
+            raise ValueError("feat_host %s is not parallel to the records %s" % (feat_host.shape, rec_host.shape))
+        feats = F.to_dicts(F.derive(r, feat_host[rec_host["area"] > 0], with_colour))
     if contours_flat is not None:
         pts, offs = contours_flat
         if shift_xy is not None:
@@ -265,19 +321,34 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
                 continue
         out[lab] = {"bbox": bbox[i], "centroid": cent[i], "contour": contour,
                     "type_prob": None if tprob is None else tprob[i], "type": None if types is None else types[i]}
+        if feats is not None:
+            out[lab]["features"] = feats[i]
     return out
 
 
-def process(pred_map, nr_types=None, return_centroids=False, contours="host"):
+def process(pred_map, nr_types=None, return_centroids=False, contours="host", *, features=False, image=None):
     """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32.  contours="device" traces the contours on
-    the GPU (`trace_contours_device`) instead of on the host; the result is the same."""
+    the GPU (`trace_contours_device`) instead of on the host; the result is the same.  features=True adds "features" to every
+    entry of the dict (`features.derive`; it implies return_centroids); `image` (host uint8 [H,W,3], RGB) adds mean_rgb / std_rgb."""
     if contours not in ("host", "device"):
         raise ValueError('contours must be "host" or "device", got %r' % (contours,))
+    img_dev = None
+    if image is not None:
+        if not features:
+            raise ValueError("image is only used with features=True")
+        image = np.asarray(image)
+        if image.dtype != np.uint8:
+            raise TypeError("image must be uint8, got %s" % image.dtype)
+        if image.shape != tuple(np.shape(pred_map)[:2]) + (3,):
+            raise ValueError("image %s does not match the map: expected %s" % (image.shape, tuple(np.shape(pred_map)[:2]) + (3,)))
+        img_dev = torch.from_numpy(np.ascontiguousarray(image)).unsqueeze(0).to("cuda")
     pred = torch.from_numpy(np.ascontiguousarray(pred_map, np.float32)).unsqueeze(0).to("cuda")
-    inst, rec, _ = process_batch_device(pred, nr_types, return_centroids)
+    inst, rec, _ = process_batch_device(pred, nr_types, return_centroids or features)
+    feat = _pp(pred.device).features(inst, rec, img_dev) if features and rec is not None else None
     flat = trace_contours_device(inst, rec)[0] if rec is not None and contours == "device" else None
     pred_inst = inst[0].cpu().numpy()
     info = None
     if rec is not None:
-        info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat)
+        info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat,
+                               feat_host=None if feat is None else feat[0].cpu().numpy(), with_colour=image is not None)
     return pred_inst, info

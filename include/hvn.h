@@ -169,6 +169,31 @@ HVN_API int hvn_instance_table(const int32_t *inst, const float *pred, int n, in
                                int nr_types, hvn_inst_rec *records, int32_t *counts, int max_inst,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* -- per-instance morphometric sums (csrc/hvn_features.hip): what regionprops-style shape and stain features are made of, as exact
+ * integers; hover_net_amd/features.py derives the float features (axes, eccentricity, orientation, perimeter, circularity, mean and
+ * std colour) on the host.  The mask of a label is inst == label INSIDE the record's bbox clamped to the map (for a table made
+ * from this map: the whole label); everything else, other labels and the outside of the map included, is background.  Any label
+ * map is valid (labels of several pieces, holes, other labels inside the bbox).
+ * per[]: scikit-image's 4-neighbourhood perimeter estimator without floats.  A mask pixel is a border pixel when one of its
+ * 4-neighbours is not in the mask; with n4 / nd = its 4- / diagonal neighbours that are border pixels of the same label,
+ * per[0] counts (n4, nd) in {(2,0),(3,0),(2,1),(3,1),(2,2),(3,2)}, per[1] {(0,2),(1,3)}, per[2] {(1,1),(1,2)}; every other
+ * combination counts nowhere.  perimeter = per[0] + per[1] * sqrt(2) + per[2] * (1 + sqrt(2)) / 2. */
+typedef struct hvn_inst_feat {           /* slot j describes label j+1, parallel to hvn_inst_rec */
+    int64_t sxx, syy, sxy;               /* sums of (x-cmin)^2, (y-rmin)^2, (x-cmin)(y-rmin) over the label's pixels */
+    int32_t seen;                        /* pixels == label found inside the record's bbox (== rec.area for a table made from this map) */
+    int32_t per[3];                      /* border-pixel class counts */
+    int64_t csum[3], csq[3];             /* sums of c, c^2 per RGB channel over the label's pixels; 0 when image == NULL */
+} hvn_inst_feat;
+/* All pointers are device pointers; everything is enqueued on `stream`, nothing is allocated or synchronised.  inst: int32
+ * [n][h][w]; image: uint8 [n][h][w][3] or NULL; records: hvn_instance_table's [n][max_inst]; feats: [n][max_inst], 8-byte
+ * aligned.  A slot with area <= 0 (or a bbox that misses the map) gets an all-zero record; a stale or foreign table cannot make
+ * the kernel read outside the map (the bbox is clamped) and shows as seen != area.  The workspace size is 0 (workspace may be
+ * NULL).  HVN_E_ARG: a null pointer (image and workspace excepted), n, h, w or max_inst < 1, h * w >= 2^31, a misaligned pointer.
+ * HVN_E_SIZE: n * max_inst >= 2^31. */
+HVN_API size_t hvn_instance_features_workspace_bytes(int n, int h, int w, int max_inst);   /* may return 0 */
+HVN_API int hvn_instance_features(const int32_t *inst, const uint8_t *image, int n, int h, int w, const hvn_inst_rec *records,
+                                  int max_inst, hvn_inst_feat *feats, void *workspace, size_t workspace_bytes, void *stream);
+
 /* -- instance-segmentation metrics: the exact integer tables behind metrics/stats_utils.py (get_fast_pq, get_fast_aji,
  * get_fast_aji_plus, get_dice_1, get_fast_dice_2, get_dice_2, remap_label); hover_net_amd/metrics.py does the float arithmetic.
  * All maps: dev int32 [n][h][w], h * w <= 2^30, n <= 65535.
