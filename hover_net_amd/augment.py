@@ -15,18 +15,13 @@ The draws come from this module's own generator, not imgaug's: the augmentation 
 stream is not (imgaug is not in this image, and per-worker seeding makes the reference's own stream irreproducible anyway).
 Kernel parity: tests/test_gpu_augment.py against oracle/augment_np.py with the same explicit parameters, bit for bit.
 No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import lib as L
 from . import targets
 
-AUG_DTYPE = np.dtype([("inv", "<f8", (6,)), ("src", "<i4"), ("flip_lr", "<i4"), ("flip_ud", "<i4"), ("kind", "<i4"), ("p0", "<i4"), ("p1", "<i4"),
-                      ("per_channel", "<i4"), ("noise_scale", "<f4"), ("order", "<i4", (4,)), ("hue", "<f8"), ("sat", "<f8"), ("bright", "<f8"),
-                      ("contrast", "<f8")], align=True)
-assert AUG_DTYPE.itemsize == 128, AUG_DTYPE.itemsize      # == sizeof(hvn_aug_sample), include/hvn.h
+AUG_DTYPE = np.dtype(L.hvn_aug_sample)
 
 
 def affine_matrix(h, w, scale_xy, translate_px, shear_deg, rotate_deg):
@@ -94,8 +89,8 @@ def augment_shape(img_dev, ann_dev, prm, out_hw):
     prm_dev = _upload(prm, img_dev.device)
     oimg = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=img_dev.device)
     oann = torch.empty((n, oh, ow, c), dtype=torch.int32, device=img_dev.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(img_dev.device).cuda_stream)
-    rc = L.lib().hvn_augment_shape(img_dev.data_ptr(), ann_dev.data_ptr(), p, h, w, c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(), stream)
+    rc = L.lib().hvn_augment_shape(img_dev.data_ptr(), ann_dev.data_ptr(), p, h, w, c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
+                                   L.stream_ptr(img_dev.device))
     if rc:
         raise L.HvnError("hvn_augment_shape failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
     return oimg, oann
@@ -114,8 +109,8 @@ def augment_input(img_dev, prm, noise=None):
         assert noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n, h, w, 3) and noise.is_contiguous()
     prm_dev = _upload(prm, img_dev.device)
     out = torch.empty_like(img_dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(img_dev.device).cuda_stream)
-    rc = L.lib().hvn_augment_input(img_dev.data_ptr(), prm_dev.data_ptr(), noise.data_ptr() if noise is not None else None, n, h, w, out.data_ptr(), stream)
+    rc = L.lib().hvn_augment_input(img_dev.data_ptr(), prm_dev.data_ptr(), noise.data_ptr() if noise is not None else None, n, h, w, out.data_ptr(),
+                                   L.stream_ptr(img_dev.device))
     if rc:
         raise L.HvnError("hvn_augment_input failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
     return out

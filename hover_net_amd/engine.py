@@ -303,8 +303,8 @@ class Engine:
         CHAIN launch that has more than one form (`tune.candidates`) is timed once per distinct shape on each of them at the batch it is
         launched with, on whatever the arena holds -- MFMA time does not depend on the values -- and bound to `tune.pick`'s answer.
         All forms of a launch produce the same bits, so the choice is invisible in the results.  ~1 s per engine."""
-        lib = L.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        run_op = L.lib().hvn_run_op
+        stream = L.stream_ptr(self.device)
         osz = ctypes.sizeof(L.hvn_op)
         base = ctypes.addressof(self.ops)
         # the encoder launches of a split engine run on sub-batches: their shapes are timed at the sub-batch size
@@ -321,7 +321,7 @@ class Engine:
 
             def measure(tn):
                 o.tile_n = tn
-                return T.time_launch(lambda: L.check(lib.hvn_run_op(base + i * osz, nb, stream), "hvn_run_op (autotune)"))
+                return T.time_launch(lambda: L.check(run_op(base + i * osz, nb, stream), "hvn_run_op (autotune)"))
 
             o.tile_n = T.pick(T.CACHE, T.launch_key(self.device, family, o, nb), cands, measure, forced=T.forced_form(o))
         torch.cuda.synchronize(self.device)
@@ -355,8 +355,7 @@ class Engine:
 
     def run_raw(self, n):
         """Run the bound plan on whatever the arena holds (per-kernel tests: no CONV0 input)."""
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(L.lib().hvn_run_plan(ctypes.addressof(self.ops), len(self.ops), n, ctypes.c_void_p(stream)), "hvn_run_plan")
+        L.call("hvn_run_plan", ctypes.addressof(self.ops), len(self.ops), n, L.stream_ptr(self.device))
 
     def _shifted_ops(self, first):
         """A copy of the bound descriptors whose per-sample views start at sample `first`."""
@@ -385,12 +384,13 @@ class Engine:
 
     def _launch(self, ops, n_ops, cnt, stream, lane_streams, start=0):
         """One sub-batch from op `start`: encoder on `stream`, decoder branches fanned out over `lane_streams`."""
-        lib = L.lib()
+        run_plan = L.lib().hvn_run_plan
         base = ctypes.addressof(ops)
         osz = ctypes.sizeof(L.hvn_op)
+        sp = L.stream_ptr(stream=stream)
         lanes = getattr(self.plan, "lanes", None)
         if not lanes or not lane_streams or n_ops != len(self.ops):
-            L.check(lib.hvn_run_plan(base + start * osz, n_ops - start, cnt, ctypes.c_void_p(stream.cuda_stream)), "hvn_run_plan")
+            L.check(run_plan(base + start * osz, n_ops - start, cnt, sp), "hvn_run_plan")
             return
         branch_i = 0
         pending = []
@@ -402,14 +402,14 @@ class Engine:
                 for ev in pending:          # join before the shared epilogue
                     stream.wait_event(ev)
                 pending = []
-                L.check(lib.hvn_run_plan(base + lo * osz, hi - lo, cnt, ctypes.c_void_p(stream.cuda_stream)), "hvn_run_plan")
+                L.check(run_plan(base + lo * osz, hi - lo, cnt, sp), "hvn_run_plan")
             else:
                 st = stream if branch_i == 0 else lane_streams[(branch_i - 1) % len(lane_streams)]
                 if st is not stream:
                     fork = torch.cuda.Event()
                     fork.record(stream)
                     st.wait_event(fork)
-                L.check(lib.hvn_run_plan(base + lo * osz, hi - lo, cnt, ctypes.c_void_p(st.cuda_stream)), "hvn_run_plan")
+                L.check(run_plan(base + lo * osz, hi - lo, cnt, sp if st is stream else L.stream_ptr(stream=st)), "hvn_run_plan")
                 if st is not stream:
                     ev = torch.cuda.Event()
                     ev.record(st)
@@ -440,6 +440,7 @@ class Engine:
             fork = torch.cuda.Event()
             fork.record(main)
             bounds = [n * k // split for k in range(split + 1)]
+            run_plan = L.lib().hvn_run_plan
             for k in range(split):
                 first, cnt = bounds[k], bounds[k + 1] - bounds[k]
                 ops = self._shifted_ops(first)
@@ -449,7 +450,7 @@ class Engine:
                 st = main if k == 0 else self._streams[k - 1]
                 if k:
                     st.wait_event(fork)
-                L.check(L.lib().hvn_run_plan(ctypes.addressof(ops), enc_end, cnt, ctypes.c_void_p(st.cuda_stream)), "hvn_run_plan")
+                L.check(run_plan(ctypes.addressof(ops), enc_end, cnt, L.stream_ptr(stream=st)), "hvn_run_plan")
                 if k:
                     join = torch.cuda.Event()
                     join.record(st)

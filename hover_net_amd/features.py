@@ -13,15 +13,11 @@ from an instance map.  With S = area, Sx = sum_x, Sy = sum_y of the record (all 
     equivalent_diameter = sqrt(4 S / pi),  extent = S / bbox area,  circularity = 4 pi S / perimeter^2  (0 when perimeter == 0)
     mean_rgb = csum / S,  std_rgb = sqrt((S csq - csum^2) / S^2) (population; only with an image)
 """
-import ctypes
-
 import numpy as np
 
 from . import lib as L
 
-FEAT_DTYPE = np.dtype([("sxx", "<i8"), ("syy", "<i8"), ("sxy", "<i8"), ("seen", "<i4"), ("per", "<i4", (3,)),
-                       ("csum", "<i8", (3,)), ("csq", "<i8", (3,))])
-assert FEAT_DTYPE.itemsize == ctypes.sizeof(L.hvn_inst_feat)
+FEAT_DTYPE = np.dtype(L.hvn_inst_feat)
 
 SHAPE_FIELDS = ("area", "vxx", "vyy", "vxy", "major_axis_length", "minor_axis_length", "eccentricity", "orientation", "perimeter",
                 "equivalent_diameter", "extent", "circularity")

@@ -69,8 +69,6 @@ def patch_grid(shape, window_size, mask_size):
 def extract_patches_device(img_dev, info, window_size, pad_tl):
     """img_dev: uint8 device tensor [H,W,3] (unpadded) -> uint8 device tensor [P,win,win,3]: reflect padding and the
     overlapping crops are produced on the GPU (hvn_extract_patches), so each source pixel crosses PCIe once."""
-    import ctypes
-
     from . import lib as L
 
     L.require_gpu()
@@ -78,9 +76,8 @@ def extract_patches_device(img_dev, info, window_size, pad_tl):
     img_dev = img_dev.contiguous()
     coords = torch.from_numpy(np.ascontiguousarray(info[:, :2], np.int32)).to(img_dev.device)
     out = torch.empty((info.shape[0], window_size, window_size, 3), dtype=torch.uint8, device=img_dev.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(img_dev.device).cuda_stream)
-    L.check(L.lib().hvn_extract_patches(img_dev.data_ptr(), img_dev.shape[0], img_dev.shape[1], coords.data_ptr(), info.shape[0],
-                                        window_size, pad_tl, pad_tl, out.data_ptr(), stream), "hvn_extract_patches")
+    L.call("hvn_extract_patches", img_dev.data_ptr(), img_dev.shape[0], img_dev.shape[1], coords.data_ptr(), info.shape[0],
+           window_size, pad_tl, pad_tl, out.data_ptr(), L.stream_ptr(img_dev.device))
     return out
 
 

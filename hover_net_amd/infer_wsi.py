@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import infer_tile, post_proc, run_desc
+from . import lib as L
 
 
 # --------------------------------------------------------------------------------------------
@@ -409,11 +410,6 @@ class DeviceMerger:
     which also yields the next tile's id offset -- the one true sequential dependency of wsi.py:569-677."""
 
     def __init__(self, proc_shape, device, cap=1 << 20):
-        import ctypes
-
-        from . import lib as L
-
-        self._L, self._ct = L, ctypes
         self.device = torch.device(device)
         self.inst_map = torch.zeros((int(proc_shape[0]), int(proc_shape[1])), dtype=torch.int32, device=self.device)
         self.inst_info = {}
@@ -457,8 +453,8 @@ class DeviceMerger:
         with torch.cuda.stream(self.stream):
             p = self._pred(pred_inst, ready)
             h, w = int(p.shape[0]), int(p.shape[1])
-            self._L.check(self._L.lib().hvn_wsi_merge_normal(self.inst_map.data_ptr(), self.inst_map.shape[1], int(tile_tl[0]), int(tile_tl[1]), h, w,
-                                                             p.data_ptr(), int(off), self._ct.c_void_p(self.stream.cuda_stream)), "hvn_wsi_merge_normal")
+            L.call("hvn_wsi_merge_normal", self.inst_map.data_ptr(), self.inst_map.shape[1], int(tile_tl[0]), int(tile_tl[1]), h, w,
+                   p.data_ptr(), int(off), L.stream_ptr(stream=self.stream))
             p.record_stream(self.stream)
 
     def fixing(self, pred_inst, info, tile_tl, tile_br, ready=None, n_local=None):
@@ -481,10 +477,10 @@ class DeviceMerger:
         with torch.cuda.stream(self.stream):
             p = self._pred(pred_inst, ready)
             h, w = int(p.shape[0]), int(p.shape[1])
-            self._L.check(self._L.lib().hvn_wsi_merge_fixing(
-                self.inst_map.data_ptr(), self.inst_map.shape[1], int(tile_tl[0]), int(tile_tl[1]), h, w, p.data_ptr(), n_local, int(off), self.epoch,
-                self.flags.data_ptr(), self.cap, self.removed.data_ptr(), self.removed_cap, self.counters.data_ptr(), self.touching.data_ptr(),
-                self._ct.c_void_p(self.stream.cuda_stream)), "hvn_wsi_merge_fixing")
+            L.call("hvn_wsi_merge_fixing",
+                   self.inst_map.data_ptr(), self.inst_map.shape[1], int(tile_tl[0]), int(tile_tl[1]), h, w, p.data_ptr(), n_local, int(off), self.epoch,
+                   self.flags.data_ptr(), self.cap, self.removed.data_ptr(), self.removed_cap, self.counters.data_ptr(), self.touching.data_ptr(),
+                   L.stream_ptr(stream=self.stream))
             p.record_stream(self.stream)
             self._h_counters.copy_(self.counters, non_blocking=True)
             self._h_removed[:4096].copy_(self.removed[:4096], non_blocking=True)

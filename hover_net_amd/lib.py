@@ -1,7 +1,11 @@
-"""ctypes binding of libhvn_hip.so (include/hvn.h).  No fallback: if the library is
-missing or no gfx950 device is visible, every entry point raises."""
+"""ctypes binding of libhvn_hip.so, generated from include/hvn.h at import: the header is the only description of the ABI.
+`parse_header` turns its structs into ctypes.Structure classes (module attributes under their header names) and its prototypes into
+the argtypes / restype that `lib()` sets on every export; nothing here restates a declaration, and one the reader cannot map raises.
+`stream_ptr`, `grown` and `call` are the one call path of the package's launch sites.  No fallback: if the library is missing or no
+gfx950 device is visible, every entry point raises."""
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,73 +27,57 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-fvisibility=hidden", "-Wno-unused-value", "-pthread")
 
 
-class hvn_view(ctypes.Structure):
-    _fields_ = [("base", ctypes.c_void_p), ("sn", ctypes.c_int64), ("sy", ctypes.c_int64), ("sx", ctypes.c_int64),
-                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("c", ctypes.c_int32), ("sc", ctypes.c_int32)]
-
-
-class hvn_op(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "kh", "kw", "stride", "pad_t", "pad_l", "relu", "cout", "tile_n", "x_dtype", "groups", "_rsv")] + \
-               [("x", hvn_view), ("res", hvn_view), ("y", hvn_view), ("x2", hvn_view)] + \
-               [(k, ctypes.c_void_p) for k in ("w", "bias", "pre_scale", "pre_shift", "post_scale", "post_shift")] + \
-               [("batch_stride", ctypes.c_int64 * 3), ("nbatch", ctypes.c_int32), ("act_dtype", ctypes.c_int32)] + \
-               [("y2", hvn_view), ("w2", ctypes.c_void_p), ("bias2", ctypes.c_void_p), ("cout2", ctypes.c_int32), ("_rsv2", ctypes.c_int32)]
-
-
-class hvn_top(ctypes.Structure):
-    """One launch of the training step (include/hvn.h, training section)."""
-    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "kh", "kw", "stride", "pad_t", "pad_l", "groups", "cout", "cin_g", "mode", "lead_pad", "_pad")] + \
-               [("x", hvn_view), ("y", hvn_view), ("dx", hvn_view), ("dy", hvn_view), ("p", ctypes.c_void_p * 6),
-                ("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("net", ctypes.POINTER(hvn_op)),
-                ("batch_stride", ctypes.c_int64 * 3), ("nbatch", ctypes.c_int32), ("_pad2", ctypes.c_int32)]
-
-
-class hvn_pack_desc(ctypes.Structure):
-    """One entry of HVN_T_PACK_MULTI's device table (include/hvn.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + [(k, ctypes.c_int32) for k in ("cout", "cin_g", "groups", "taps", "mode", "lead_pad")] + \
-               [("gmat", ctypes.c_void_p)]
-
-
-class hvn_loss(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("logits_np", "logits_hv", "logits_tp", "true_np", "true_tp", "true_hv",
-                                               "grad_np", "grad_hv", "grad_tp", "sums", "sobel_ws")] + \
-               [(k, ctypes.c_int32) for k in ("n", "h", "w", "nr_types")] + [("total_pixels", ctypes.c_double), ("weight", ctypes.c_float * 6),
-                                                                             ("partials", ctypes.c_void_p), ("partials_cap", ctypes.c_int64)]
-
-
-class hvn_inst_rec(ctypes.Structure):
-    _fields_ = [("label", ctypes.c_int32), ("area", ctypes.c_int32), ("rmin", ctypes.c_int32), ("rmax", ctypes.c_int32),
-                ("cmin", ctypes.c_int32), ("cmax", ctypes.c_int32), ("sum_x", ctypes.c_double), ("sum_y", ctypes.c_double),
-                ("type", ctypes.c_int32), ("type_count", ctypes.c_int32)]
-
-
-class hvn_inst_feat(ctypes.Structure):
-    """One slot of hvn_instance_features (include/hvn.h), parallel to hvn_inst_rec."""
-    _fields_ = [("sxx", ctypes.c_int64), ("syy", ctypes.c_int64), ("sxy", ctypes.c_int64), ("seen", ctypes.c_int32),
-                ("per", ctypes.c_int32 * 3), ("csum", ctypes.c_int64 * 3), ("csq", ctypes.c_int64 * 3)]
-
-
-EXPORTS = (
-    "hvn_version", "hvn_build_id", "hvn_last_error", "hvn_device_ok", "hvn_run_plan", "hvn_run_op", "hvn_profile_enable",
-    "hvn_profile_conv_ms", "hvn_profile_conv_launches", "hvn_profile_conv_ms_list", "hvn_postproc_workspace_bytes", "hvn_postproc",
-    "hvn_postproc_taps", "hvn_postproc_stats", "hvn_instance_table_workspace_bytes", "hvn_instance_table", "hvn_trace_contours",
-    "hvn_run_train_plan", "hvn_run_train_plan_ws", "hvn_train_workspace_bytes", "hvn_train_last_error", "hvn_loss_partials_count", "hvn_loss_forward", "hvn_loss_backward", "hvn_adam_step",
-    "hvn_extract_patches", "hvn_gen_targets", "hvn_gen_targets_workspace_bytes", "hvn_augment_shape", "hvn_augment_input", "hvn_augment_shape_images",
-    "hvn_wsi_merge_normal", "hvn_wsi_merge_fixing",
-    "hvn_pair_table_workspace_bytes", "hvn_pair_table", "hvn_label_range", "hvn_remap_label_workspace_bytes", "hvn_remap_label",
-    "hvn_label_areas", "hvn_label_permute",
-    "hvn_valid_stats_workspace_bytes", "hvn_valid_stats",
-    "hvn_contours_workspace_bytes", "hvn_trace_contours_device",
-    "hvn_overlay_workspace_bytes", "hvn_draw_overlay",
-    "hvn_resize_window",
-    "hvn_tissue_gray_hist", "hvn_tissue_mask_workspace_bytes", "hvn_tissue_mask",
-    "hvn_viz_strip",
-    "hvn_instance_features_workspace_bytes", "hvn_instance_features",
-)
-
-
 class HvnError(RuntimeError):
     pass
+
+
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "hvn.h")
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "long": ctypes.c_long,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def parse_header(text):
+    """(structs, protos) of a header written in hvn.h's forms: every `typedef struct NAME { ... } NAME;` as a ctypes.Structure, in
+    header order, and every `HVN_API <ret> name(args);` as name -> (restype, argtypes).  Not a C grammar: a declaration outside these
+    forms, or of a type the tables below do not map, raises HvnError naming it -- none is ever skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.S | re.M)
+    structs, protos = {}, {}
+    for chunk in re.split(r"\btypedef\s+struct\b", text)[1:]:
+        m = re.match(r"\s*(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", chunk)
+        if not m or m.group(1) != m.group(3):
+            raise HvnError("hvn.h: cannot read `typedef struct %s ...`" % " ".join(chunk.split())[:60])
+        name, body, fields = m.group(1), m.group(2), []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            base, _, rest = re.sub(r"\bconst\b", " ", decl).strip().partition(" ")
+            for d in rest.split(","):
+                m = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*", d)
+                if m and m.group(1):            # a pointer: to a struct declared above, else opaque
+                    t = ctypes.POINTER(structs[base]) if base in structs else ctypes.c_void_p
+                else:
+                    t = structs.get(base) or _SCALARS.get(base)
+                if not m or t is None:
+                    raise HvnError("hvn.h: cannot map `%s` of struct %s" % (decl, name))
+                fields.append((m.group(2), t * int(m.group(3)) if m.group(3) else t))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    for decl in re.findall(r"\bHVN_API\b([^;]*);", text):
+        m = re.fullmatch(r"([^()]*?)(\w+)\s*\(([^()]*)\)\s*", decl)
+        if not m:
+            raise HvnError("hvn.h: cannot read `HVN_API %s`" % " ".join(decl.split()))
+        ret, name, args = " ".join(m.group(1).split()), m.group(2), m.group(3)
+        restype = ctypes.c_char_p if ret == "const char *" else _SCALARS.get(ret)
+        params = [ctypes.c_void_p if "*" in a or "[" in a else _SCALARS.get(" ".join(a.replace("const ", " ").split()[:-1]))
+                  for a in ([] if args.strip() == "void" else args.split(","))]
+        if restype is None or None in params:
+            raise HvnError("hvn.h: cannot map `%s %s(%s)`" % (ret, name, " ".join(args.split())))
+        protos[name] = (restype, params)
+    return structs, protos
+
+
+# include/hvn.h is the one description of the ABI: the structs become module attributes under their header names (hvn_op, hvn_view,
+# hvn_top, ...; np.dtype(<struct>) is the numpy view of a record), the prototypes the argtypes / restype that lib() sets.
+STRUCTS, PROTOS = parse_header(open(HEADER).read())
+globals().update(STRUCTS)
+EXPORTS = tuple(PROTOS)
 
 
 def source_id():
@@ -226,98 +214,36 @@ def lib():
         if os.path.isdir(CSRC) and not os.environ.get("HVN_LIB_VARIANT") and built != source_id():
             raise HvnError("%s was built from other sources (library %s, sources %s): run `python -c 'import __graft_entry__ as g; g.build()'`"
                            % (os.path.basename(path), built, source_id()))
-        L.hvn_last_error.restype = ctypes.c_char_p
-        L.hvn_profile_conv_ms.restype = ctypes.c_double
-        L.hvn_profile_conv_ms_list.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.hvn_postproc_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_postproc_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_run_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.hvn_run_op.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.hvn_postproc.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_postproc_taps.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_postproc_stats.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_instance_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                         ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_instance_table_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_instance_table_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_trace_contours.restype = ctypes.c_long
-        L.hvn_trace_contours.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
-        L.hvn_contours_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_contours_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.hvn_trace_contours_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_overlay_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_overlay_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_draw_overlay.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_resize_window.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.hvn_tissue_gray_hist.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_tissue_mask_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_tissue_mask_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.hvn_tissue_mask.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_viz_strip.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.hvn_instance_features_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_instance_features_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_instance_features.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_extract_patches.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_gen_targets_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_gen_targets_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_gen_targets.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_augment_shape.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_augment_shape_images.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_augment_input.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                        ctypes.c_void_p]
-        L.hvn_wsi_merge_normal.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_void_p]
-        L.hvn_wsi_merge_fixing.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_pair_table_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_pair_table_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_pair_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_label_range.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_remap_label_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_remap_label_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32]
-        L.hvn_remap_label.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_label_areas.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_label_permute.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_valid_stats_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_valid_stats_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_valid_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        L.hvn_train_last_error.restype = ctypes.c_char_p
-        L.hvn_run_train_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.hvn_run_train_plan_ws.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-        L.hvn_train_workspace_bytes.restype = ctypes.c_size_t
-        L.hvn_train_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-        L.hvn_loss_partials_count.restype = ctypes.c_int64
-        L.hvn_loss_partials_count.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.hvn_loss_forward.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_loss_backward.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.hvn_adam_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+        for name, (restype, argtypes) in PROTOS.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                if os.environ.get("HVN_LIB_VARIANT"):   # another checkout's library (variant "prev") may predate an entry point
+                    continue
+                raise HvnError("%s does not export %s, which include/hvn.h declares" % (os.path.basename(path), name))
+            fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
+
+
+def stream_ptr(device=None, stream=None):
+    """hipStream_t of `stream`, or of `device`'s current stream, as the void* every entry point takes."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device)
+    return ctypes.c_void_p(stream.cuda_stream)
+
+
+def grown(buf, nbytes, device):
+    """`buf` if it already holds `nbytes`, else a fresh uint8 workspace of that size (the caller keeps whichever cache it had)."""
+    if buf is not None and buf.numel() >= nbytes:
+        return buf
+    import torch
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def call(name, *args):
+    """One status-returning entry point: raises HvnError with the library's text unless it returns HVN_OK."""
+    check(getattr(lib(), name)(*args), name)
 
 
 def check(rc, what):

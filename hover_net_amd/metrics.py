@@ -89,14 +89,6 @@ def _device_maps(x, dev):
     return t.to(dev).contiguous()
 
 
-def _stream(dev):
-    import ctypes
-
-    import torch
-
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 # ------------------------------------------------------------------------------------------------------------------ the tables
 class PairTable:
     """The pair table of one image: `t`, `p`, `count` (int64 [K]) = every distinct (true id, pred id) pair other than (0, 0)
@@ -193,8 +185,8 @@ def device_triples(true, pred, dev=None):
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             tri = torch.empty((m, h * w, 3), dtype=torch.int32, device=dev)
             cnt = torch.empty(m, dtype=torch.int32, device=dev)
-            L.check(L.lib().hvn_pair_table(tt[i0:i0 + m].data_ptr(), pt[i0:i0 + m].data_ptr(), m, h, w, tri.data_ptr(), cnt.data_ptr(),
-                                           ws.data_ptr(), need, _stream(dev)), "hvn_pair_table")
+            L.call("hvn_pair_table", tt[i0:i0 + m].data_ptr(), pt[i0:i0 + m].data_ptr(), m, h, w, tri.data_ptr(), cnt.data_ptr(),
+                   ws.data_ptr(), need, L.stream_ptr(dev))
             k = cnt.cpu().numpy().astype(np.int64)
             flat = torch.cat([tri[j, :int(k[j])] for j in range(m)]).cpu().numpy().astype(np.int64)
             del ws, tri
@@ -451,7 +443,7 @@ def remap_device(maps, by_size=False):
     dev = maps.device
     rng = torch.empty((n, 2), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        L.check(L.lib().hvn_label_range(maps.data_ptr(), n, h, w, rng.data_ptr(), _stream(dev)), "hvn_label_range")
+        L.call("hvn_label_range", maps.data_ptr(), n, h, w, rng.data_ptr(), L.stream_ptr(dev))
         r = rng.cpu().numpy()
         if (r[:, 0] < 0).any():
             raise ValueError("negative labels are not instance ids")
@@ -471,21 +463,21 @@ def remap_device(maps, by_size=False):
                 m, mx = m + 1, grown
             need = L.lib().hvn_remap_label_workspace_bytes(m, h, w, mx)
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            L.check(L.lib().hvn_remap_label(maps[i0:i0 + m].data_ptr(), m, h, w, mx, out[i0:i0 + m].data_ptr(), n_ids[i0:i0 + m].data_ptr(),
-                                            ws.data_ptr(), need, _stream(dev)), "hvn_remap_label")
+            L.call("hvn_remap_label", maps[i0:i0 + m].data_ptr(), m, h, w, mx, out[i0:i0 + m].data_ptr(), n_ids[i0:i0 + m].data_ptr(),
+                   ws.data_ptr(), need, L.stream_ptr(dev))
             del ws
             i0 += m
         if by_size:
             k = n_ids.cpu().numpy().astype(np.int64)
             kmax = int(k.max())
             areas = torch.empty((n, kmax + 1), dtype=torch.int32, device=dev)
-            L.check(L.lib().hvn_label_areas(out.data_ptr(), n, h, w, kmax, areas.data_ptr(), _stream(dev)), "hvn_label_areas")
+            L.call("hvn_label_areas", out.data_ptr(), n, h, w, kmax, areas.data_ptr(), L.stream_ptr(dev))
             a = areas.cpu().numpy().astype(np.int64)
             perm = np.tile(np.arange(kmax + 1, dtype=np.int32), (n, 1))
             for i in range(n):
                 perm[i, 1:k[i] + 1][np.argsort(-a[i, 1:k[i] + 1], kind="stable")] = np.arange(1, k[i] + 1, dtype=np.int32)
             dperm = torch.from_numpy(perm).to(dev)
-            L.check(L.lib().hvn_label_permute(out.data_ptr(), n, h, w, kmax, dperm.data_ptr(), _stream(dev)), "hvn_label_permute")
+            L.call("hvn_label_permute", out.data_ptr(), n, h, w, kmax, dperm.data_ptr(), L.stream_ptr(dev))
             torch.cuda.current_stream(dev).synchronize()
     return out
 

@@ -8,8 +8,6 @@ Constructor signature = torch's (`FusedAdam(params, lr=..., betas=...)`), so the
 slab-backed (the engine has not been built yet, or a foreign tensor) are updated with one launch per tensor.
 Parameters without a gradient keep a zero gradient in the slab: m and v stay 0 and the update is exactly 0,
 which is what torch.optim.Adam's "skip params with grad None" does."""
-import ctypes
-
 import torch
 
 from . import lib as L
@@ -62,7 +60,7 @@ class FusedAdam(torch.optim.Optimizer):
             st["step"] = st.get("step", 0) + 1
             slab = self._slab(group)
             dev = group["params"][0].device
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = L.stream_ptr(dev)
             if slab is not None:
                 ws, gs, lo, hi = slab
                 lo = lo // 4 * 4

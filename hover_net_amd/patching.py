@@ -12,17 +12,13 @@ a device table and reads the whole image through the periodic mirror, so the pat
     augment_shape_images / extract_device   the gather (any parameter records / identity records = the extractor itself)
 
 Parity: tests/test_patching_host.py (live reference and tests/golden/patching_ref.npz), tests/test_gpu_patching.py.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import lib as L
 from .augment import _upload, identity_params
 
-IMAGE_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4")], align=True)
-PATCH_DTYPE = np.dtype([("image", "<i4"), ("row", "<i4"), ("col", "<i4")], align=True)
-assert IMAGE_DTYPE.itemsize == 16 and PATCH_DTYPE.itemsize == 12      # == sizeof(hvn_image_rec), sizeof(hvn_patch_rec), include/hvn.h
+IMAGE_DTYPE, PATCH_DTYPE = np.dtype(L.hvn_image_rec), np.dtype(L.hvn_patch_rec)
 
 
 def _pair(v):
@@ -197,12 +193,11 @@ def _launch(store, prm, out_hw, status=None, **declared):
     oimg = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
     oann = torch.empty((n, oh, ow, store.c), dtype=torch.int32, device=dev)
     status = store.status if status is None else status
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     rc = L.lib().hvn_augment_shape_images(store.pixels.data_ptr(), store.ann.data_ptr(), store.image_dev.data_ptr(), store.patch_dev.data_ptr(),
                                           int(declared.get("n_images", store.n_images)), int(declared.get("n_patches", store.n_patches)),
                                           int(declared.get("total_pixels", store.total_pixels)),
                                           store.win[0], store.win[1], store.c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
-                                          status.data_ptr(), stream)
+                                          status.data_ptr(), L.stream_ptr(dev))
     if rc:
         raise L.HvnError("hvn_augment_shape_images failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
     return oimg, oann

@@ -50,9 +50,7 @@ class PostProc:
         self._fws = None
 
     def _workspace(self, n, h, w):
-        need = L.lib().hvn_postproc_workspace_bytes(n, h, w)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = L.grown(self._ws, L.lib().hvn_postproc_workspace_bytes(n, h, w), self.device)
         return self._ws
 
     def separate(self, pred, taps=False):
@@ -66,16 +64,15 @@ class PostProc:
         ws = self._workspace(n, h, w)
         self._last_nhw = (n, h, w)
         inst = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = L.stream_ptr(self.device)
         if not taps:
-            L.check(L.lib().hvn_postproc(pred.data_ptr(), n, h, w, c, c - 3, inst.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                    "hvn_postproc")
+            L.call("hvn_postproc", pred.data_ptr(), n, h, w, c, c - 3, inst.data_ptr(), ws.data_ptr(), ws.numel(), stream)
             return inst
         blb = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
         dist = torch.empty((n, h, w), dtype=torch.float64, device=self.device)
         marker = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
-        L.check(L.lib().hvn_postproc_taps(pred.data_ptr(), n, h, w, c, c - 3, inst.data_ptr(), blb.data_ptr(), dist.data_ptr(),
-                                          marker.data_ptr(), ws.data_ptr(), ws.numel(), stream), "hvn_postproc_taps")
+        L.call("hvn_postproc_taps", pred.data_ptr(), n, h, w, c, c - 3, inst.data_ptr(), blb.data_ptr(), dist.data_ptr(),
+               marker.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         return inst, blb, dist, marker
 
     def flood_stats(self, stream=None):
@@ -85,8 +82,7 @@ class PostProc:
             return None
         n, h, w = self._last_nhw
         out = (ctypes.c_longlong * 10)()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        L.check(L.lib().hvn_postproc_stats(self._ws.data_ptr(), self._ws.numel(), n, h, w, out, ctypes.c_void_p(st.cuda_stream)), "hvn_postproc_stats")
+        L.call("hvn_postproc_stats", self._ws.data_ptr(), self._ws.numel(), n, h, w, out, L.stream_ptr(self.device, stream))
         keys = ("components", "small_window", "bitmap_window", "hbm_window", "to_heap_by_marker_tie", "to_heap_by_full_frontier",
                 "component_heap_replays", "whole_tile_replays", "maps_flagged", "largest_component_box")
         return {k: int(v) for k, v in zip(keys, out)}
@@ -96,15 +92,11 @@ class PostProc:
         n, h, w = inst.shape
         max_inst = h * w // 13 + 1   # an opened marker component holds at least one 13-px element
         nt = int(nr_types or 0)
-        need = L.lib().hvn_instance_table_workspace_bytes(n, max_inst, nt)
-        if self._tws is None or self._tws.numel() < need:
-            self._tws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._tws = L.grown(self._tws, L.lib().hvn_instance_table_workspace_bytes(n, max_inst, nt), self.device)
         rec = torch.empty((n, max_inst, ctypes.sizeof(L.hvn_inst_rec)), dtype=torch.uint8, device=self.device)
         counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(L.lib().hvn_instance_table(inst.data_ptr(), pred.data_ptr() if nt else None, n, h, w, pred.shape[-1], nt,
-                                           rec.data_ptr(), counts.data_ptr(), max_inst, self._tws.data_ptr(),
-                                           self._tws.numel(), stream), "hvn_instance_table")
+        L.call("hvn_instance_table", inst.data_ptr(), pred.data_ptr() if nt else None, n, h, w, pred.shape[-1], nt,
+               rec.data_ptr(), counts.data_ptr(), max_inst, self._tws.data_ptr(), self._tws.numel(), L.stream_ptr(self.device))
         return rec, counts
 
     def contours(self, inst, rec, max_pts=None):
@@ -124,16 +116,12 @@ class PostProc:
         if max_pts is None:
             max_pts = n * h * w // 4
         max_pts = max(int(max_pts), 0)
-        need = L.lib().hvn_contours_workspace_bytes(n, max_inst)
-        if self._cws is None or self._cws.numel() < need:
-            self._cws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._cws = L.grown(self._cws, L.lib().hvn_contours_workspace_bytes(n, max_inst), self.device)
         pts = torch.empty((max_pts, 2), dtype=torch.int32, device=self.device)
         offs = torch.empty((n * max_inst + 1,), dtype=torch.int64, device=self.device)
         status = torch.empty((4,), dtype=torch.int32, device=self.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(L.lib().hvn_trace_contours_device(inst.data_ptr(), n, h, w, rec.data_ptr(), max_inst, pts.data_ptr() if max_pts else None,
-                                                  max_pts, offs.data_ptr(), status.data_ptr(), self._cws.data_ptr(), self._cws.numel(),
-                                                  stream), "hvn_trace_contours_device")
+        L.call("hvn_trace_contours_device", inst.data_ptr(), n, h, w, rec.data_ptr(), max_inst, pts.data_ptr() if max_pts else None,
+               max_pts, offs.data_ptr(), status.data_ptr(), self._cws.data_ptr(), self._cws.numel(), L.stream_ptr(self.device))
         return pts, offs, status
 
     def features(self, inst, rec, image=None):
@@ -154,13 +142,11 @@ class PostProc:
         inst, rec = inst.contiguous(), rec.contiguous()
         max_inst = rec.shape[1]
         need = L.lib().hvn_instance_features_workspace_bytes(n, h, w, max_inst)
-        if need and (self._fws is None or self._fws.numel() < need):
-            self._fws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if need:
+            self._fws = L.grown(self._fws, need, self.device)
         feat = torch.empty((n, max_inst, ctypes.sizeof(L.hvn_inst_feat)), dtype=torch.uint8, device=self.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(L.lib().hvn_instance_features(inst.data_ptr(), image.data_ptr() if image is not None else None, n, h, w, rec.data_ptr(),
-                                              max_inst, feat.data_ptr(), self._fws.data_ptr() if need else None, need, stream),
-                "hvn_instance_features")
+        L.call("hvn_instance_features", inst.data_ptr(), image.data_ptr() if image is not None else None, n, h, w, rec.data_ptr(),
+               max_inst, feat.data_ptr(), self._fws.data_ptr() if need else None, need, L.stream_ptr(self.device))
         return feat
 
     def _pinned(self, like):
@@ -170,9 +156,7 @@ class PostProc:
         return tuple(b[:t.numel()].view(t.shape) for b, t in zip(self._cpin, like))
 
 
-_REC_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("rmin", "<i4"), ("rmax", "<i4"), ("cmin", "<i4"), ("cmax", "<i4"),
-                       ("sum_x", "<f8"), ("sum_y", "<f8"), ("type", "<i4"), ("type_count", "<i4")])
-assert _REC_DTYPE.itemsize == ctypes.sizeof(L.hvn_inst_rec)
+_REC_DTYPE = np.dtype(L.hvn_inst_rec)
 
 _DEFAULT = {}
 

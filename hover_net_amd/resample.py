@@ -181,8 +181,6 @@ def resize_window_device(src_dev, src_origin, full_shape, f, y0, x0, h, w, kind=
     contiguous tensor; `tables` = the window's `window_tables`, when the caller has made them already).  The coefficient tables are made here on the host and uploaded: the device does integer arithmetic only.
     A box that does not hold every clamped tap of the window is refused BEFORE the launch (lib.HvnError, `out` untouched): the
     tables live on the device, so the launcher cannot see their end values; it checks the box against the full source."""
-    import ctypes
-
     import torch
 
     from . import lib as L
@@ -205,8 +203,7 @@ def resize_window_device(src_dev, src_origin, full_shape, f, y0, x0, h, w, kind=
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
     assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (h, w, 3) and out.device == dev
     tabs = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (xo, xc, yo, yc)]
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    L.check(L.lib().hvn_resize_window(src_dev.data_ptr(), sh, sw, int(src_dev.stride(0)), sy0, sx0, int(full_shape[0]), int(full_shape[1]),
-                                      tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(), tabs[3].data_ptr(), int(xc.shape[1]),
-                                      out.data_ptr(), h, w, stream), "hvn_resize_window")
+    L.call("hvn_resize_window", src_dev.data_ptr(), sh, sw, int(src_dev.stride(0)), sy0, sx0, int(full_shape[0]), int(full_shape[1]),
+           tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(), tabs[3].data_ptr(), int(xc.shape[1]),
+           out.data_ptr(), h, w, L.stream_ptr(dev))
     return out

@@ -4,8 +4,6 @@
 instance-id map); `gen_targets_device(ann_dev, crop_shape)` is the batched form for a GPU-side input pipeline: int32
 `[N,H,W]` instance maps in HBM -> float32 `[N,ch,cw,2]` HV targets and `[N,ch,cw]` nucleus masks in HBM, bit-exact with
 the reference (tests/test_gpu_targets.py).  Kernels: csrc/hvn_targets.hip.  No CPU fallback."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -20,14 +18,12 @@ def gen_targets_device(ann_dev, crop_shape):
     ann_dev = ann_dev.contiguous()
     n, h, w = ann_dev.shape
     ch, cw = int(crop_shape[0]), int(crop_shape[1])
-    need = L.lib().hvn_gen_targets_workspace_bytes(n, h, w)
     key = str(ann_dev.device)
-    if key not in _WS or _WS[key].numel() < need:
-        _WS[key] = torch.empty(need, dtype=torch.uint8, device=ann_dev.device)
+    _WS[key] = L.grown(_WS.get(key), L.lib().hvn_gen_targets_workspace_bytes(n, h, w), ann_dev.device)
     hv = torch.empty((n, ch, cw, 2), dtype=torch.float32, device=ann_dev.device)
     npm = torch.empty((n, ch, cw), dtype=torch.int32, device=ann_dev.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(ann_dev.device).cuda_stream)
-    rc = L.lib().hvn_gen_targets(ann_dev.data_ptr(), n, h, w, ch, cw, hv.data_ptr(), npm.data_ptr(), _WS[key].data_ptr(), _WS[key].numel(), stream)
+    rc = L.lib().hvn_gen_targets(ann_dev.data_ptr(), n, h, w, ch, cw, hv.data_ptr(), npm.data_ptr(), _WS[key].data_ptr(), _WS[key].numel(),
+                                 L.stream_ptr(ann_dev.device))
     if rc:
         raise L.HvnError("hvn_gen_targets failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
     return {"hv_map": hv, "np_map": npm}

@@ -90,8 +90,6 @@ def _plane(t, channels):
 
 def gray_hist_device(thumb_dev):
     """uint8 device [h,w,3] -> (grey uint8 device [h,w], its 256 counters int32 device), `rgb_to_gray` and `np.bincount`."""
-    import ctypes
-
     import torch
 
     from . import lib as L
@@ -100,16 +98,13 @@ def gray_hist_device(thumb_dev):
     with torch.cuda.device(thumb_dev.device):
         gray = torch.empty((h, w), dtype=torch.uint8, device=thumb_dev.device)
         hist = torch.empty(256, dtype=torch.int32, device=thumb_dev.device)        # uint32 counters: a plane has at most 2^30 pixels
-        stream = ctypes.c_void_p(torch.cuda.current_stream(thumb_dev.device).cuda_stream)
-        L.check(L.lib().hvn_tissue_gray_hist(thumb_dev.data_ptr(), h, w, gray.data_ptr(), hist.data_ptr(), stream), "hvn_tissue_gray_hist")
+        L.call("hvn_tissue_gray_hist", thumb_dev.data_ptr(), h, w, gray.data_ptr(), hist.data_ptr(), L.stream_ptr(thumb_dev.device))
     return gray, hist
 
 
 def mask_from_gray_device(gray_dev, t, min_obj=16 * 16, max_hole=128 * 128, radius=16, taps=False):
     """The chain after the threshold is known, on a grey plane in HBM: uint8 device [h,w] of {0,1}; with `taps` also the planes
     after the object filter and after the hole filter, `(mask, a, b)`.  No synchronisation."""
-    import ctypes
-
     import torch
 
     from . import lib as L
@@ -118,12 +113,10 @@ def mask_from_gray_device(gray_dev, t, min_obj=16 * 16, max_hole=128 * 128, radi
     dev = gray_dev.device
     with torch.cuda.device(dev):
         need = int(L.lib().hvn_tissue_mask_workspace_bytes(h, w))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        ws = L.grown(None, max(need, 1), dev)
         out = [torch.empty((h, w), dtype=torch.uint8, device=dev) for _ in range(3 if taps else 1)]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(L.lib().hvn_tissue_mask(gray_dev.data_ptr(), h, w, int(t), int(min_obj), int(max_hole), int(radius), out[0].data_ptr(),
-                                        out[1].data_ptr() if taps else None, out[2].data_ptr() if taps else None,
-                                        ws.data_ptr(), need, stream), "hvn_tissue_mask")
+        L.call("hvn_tissue_mask", gray_dev.data_ptr(), h, w, int(t), int(min_obj), int(max_hole), int(radius), out[0].data_ptr(),
+               out[1].data_ptr() if taps else None, out[2].data_ptr() if taps else None, ws.data_ptr(), need, L.stream_ptr(dev))
     return tuple(out) if taps else out[0]
 
 

@@ -709,7 +709,7 @@ class TrainEngine:
 
     # -- one step ------------------------------------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return L.stream_ptr(self.device)
 
     def load_batch(self, batch):
         """batch: the reference loader's dict (img uint8 NHWC, np_map, hv_map, tp_map?) of tensors / arrays."""

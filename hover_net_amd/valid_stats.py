@@ -12,8 +12,6 @@ reference's visualisation of eight validation patches) does not need them either
 to draw, and `update` draws each of them that falls into its batch straight into its block of one device strip (`viz.strip_device`,
 one more launch); `track` brings scalars and strip to the host in one copy.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -28,10 +26,9 @@ def launch(pred, np_map, hv_map, tp_map, shape, nr_types, counts, hv_sse, worksp
     lib = L.lib()
     n, h, w, c = (int(v) for v in shape)
     with torch.cuda.device(counts.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(counts.device).cuda_stream)
         rc = lib.hvn_valid_stats(pred.data_ptr(), np_map.data_ptr(), hv_map.data_ptr(), None if tp_map is None else tp_map.data_ptr(), n, h, w, c,
                                  int(nr_types), counts.data_ptr(), hv_sse.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                 stream)
+                                 L.stream_ptr(counts.device))
     if rc != 0:
         raise L.HvnError("hvn_valid_stats failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
 
@@ -111,9 +108,7 @@ class ValidStats:
         tp_map = None
         if self.nr_types is not None and feed.get("tp_map") is not None:
             tp_map = self._feed(feed["tp_map"], torch.int32, (n, h, w))
-        need = int(L.lib().hvn_valid_stats_workspace_bytes(n, h, w))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        self._ws = L.grown(self._ws, max(int(L.lib().hvn_valid_stats_workspace_bytes(n, h, w)), 1), self.device)
         launch(pred_dev, np_map, hv_map, tp_map, (n, h, w, c), self.nr_types or 0, self.counts, self.hv_sse, self._ws)
         if self._plan is not None:
             self._draw(pred_dev, feed, np_map, hv_map, tp_map)

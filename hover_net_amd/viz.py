@@ -169,18 +169,13 @@ def draw_overlay_device(images, pts, offs, rgba, centres=None, *, thickness=2, d
     centres = None if centres is None else centres.contiguous()
     if out is None:
         out = torch.empty_like(images)
-    need = L.lib().hvn_overlay_workspace_bytes(n, h, w)
-    ws = _WORKSPACE.get(str(dev))
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACE[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _WORKSPACE[str(dev)] = L.grown(_WORKSPACE.get(str(dev)), L.lib().hvn_overlay_workspace_bytes(n, h, w), dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
     dot = (ctypes.c_uint8 * 3)(*[int(v) for v in dot_colour])
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(L.lib().hvn_draw_overlay(images.data_ptr(), out.data_ptr(), n, h, w, pts.data_ptr() if pts.shape[0] else None, pts.shape[0],
-                                         offs.data_ptr(), m // n, rgba.data_ptr(), None if centres is None else centres.data_ptr(),
-                                         int(thickness), int(dot_radius), dot, status.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                "hvn_draw_overlay")
+        L.call("hvn_draw_overlay", images.data_ptr(), out.data_ptr(), n, h, w, pts.data_ptr() if pts.shape[0] else None, pts.shape[0],
+               offs.data_ptr(), m // n, rgba.data_ptr(), None if centres is None else centres.data_ptr(),
+               int(thickness), int(dot_radius), dot, status.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr(dev))
     return (out, status) if return_status else out
 
 
@@ -284,8 +279,6 @@ def strip_device(img, pred, np_map, hv_map, tp_map, sel, out=None, n_blocks=None
     (sample in the batch, block of the strip), int [n_sel,2] as a host sequence / array, or an int32 device tensor; a pair out of
     range raises ValueError before anything is launched.  Every pair draws its block (two pairs naming one block race); the other
     blocks keep what `out` holds (a new `out` is zeroed).  n_blocks defaults to out's, else to n_sel."""
-    import ctypes
-
     import torch
 
     from . import lib as L
@@ -351,10 +344,9 @@ def strip_device(img, pred, np_map, hv_map, tp_map, sel, out=None, n_blocks=None
     if lut is None:
         lut = _LUT_DEV[str(dev)] = torch.from_numpy(np.array(jet_lut())).to(dev)
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(L.lib().hvn_viz_strip(img.data_ptr(), n, ih, iw, pred.data_ptr(), c, np_map.data_ptr(), hv_map.data_ptr(),
-                                      None if tp_map is None else tp_map.data_ptr(), h, w, nt, sel_dev.data_ptr(), n_sel, lut.data_ptr(),
-                                      out.data_ptr(), n_blocks, stream), "hvn_viz_strip")
+        L.call("hvn_viz_strip", img.data_ptr(), n, ih, iw, pred.data_ptr(), c, np_map.data_ptr(), hv_map.data_ptr(),
+               None if tp_map is None else tp_map.data_ptr(), h, w, nt, sel_dev.data_ptr(), n_sel, lut.data_ptr(),
+               out.data_ptr(), n_blocks, L.stream_ptr(dev))
     return out
 
 

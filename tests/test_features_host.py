@@ -37,17 +37,6 @@ def _blob(rng, size):
     return mask
 
 
-def test_feat_dtype_is_the_c_struct():
-    import ctypes
-
-    from hover_net_amd import lib as L
-
-    assert F.FEAT_DTYPE.itemsize == ctypes.sizeof(L.hvn_inst_feat) == 88
-    for name in ("sxx", "syy", "sxy", "seen", "per", "csum", "csq"):
-        assert F.FEAT_DTYPE.fields[name][1] == getattr(L.hvn_inst_feat, name).offset
-    assert "hvn_instance_features" in L.EXPORTS and "hvn_features.hip" in L.SOURCES
-
-
 def test_oracle_convolution_classes_equal_the_pixel_loop():
     rng = np.random.default_rng(7)
     for k in range(200):

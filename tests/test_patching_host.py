@@ -4,7 +4,6 @@ tools/make_golden_patching.py with the reference's own extractor) everywhere; th
 files written into tmp_path; the table validation of `ImageStore`; the ABI of `hvn_augment_shape_images`.  `==` everywhere."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -263,14 +262,8 @@ def test_dataset_parsers_round_trip(tmp_path):
     assert st.c == 2 and st.n_patches == len(P.patch_origins(13, 17, (9, 8), (4, 3), "mirror"))
 
 
-def test_export_is_declared_listed_and_bound():
-    header = open(os.path.join(REPO, "include", "hvn.h")).read()
-    assert re.search(r"HVN_API\s+int\s+hvn_augment_shape_images\(", header)
-    assert "typedef struct hvn_image_rec" in header and "typedef struct hvn_patch_rec" in header
-    assert "hvn_augment_shape_images" in L.EXPORTS and len(set(L.EXPORTS)) == len(L.EXPORTS)
+def test_refusals_are_host_arithmetic():
     lib = L.lib()
-    assert len(lib.hvn_augment_shape_images.argtypes) == 18
-    assert lib.hvn_version() == 104
     # refusals are host arithmetic: no device is touched.  Dummy non-null, aligned "pointers" are never dereferenced.
     p = ctypes.c_void_p(4096)
 

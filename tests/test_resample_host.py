@@ -2,7 +2,6 @@
 and ranks agree with the whole-image resize, 1 grey level against the float64 evaluation of the same coefficients), the
 `ScaledSlide` backend and the manager's `base_mag` run argument."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -140,13 +139,3 @@ def test_manager_honours_base_mag(tmp_path):
     assert type(seen[0]) is infer_wsi.ArraySlide and tuple(seen[0].shape) == (40, 50, 3)
     assert type(im.open_slide(str(inp / "s1.npy"))) is infer_wsi.ArraySlide
     assert isinstance(im.open_slide(str(inp / "s1.npy"), 20, 40), infer_wsi.ScaledSlide)
-
-
-def test_abi_holds_the_resample_export():
-    from hover_net_amd import lib as L
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "hvn.h")).read()
-    assert re.search(r"HVN_API\s+int\s+hvn_resize_window\s*\(", hdr)
-    assert "hvn_resize_window" in L.EXPORTS and "hvn_resample.hip" in L.SOURCES
-    assert os.path.exists(os.path.join(L.CSRC, "hvn_resample.hip"))

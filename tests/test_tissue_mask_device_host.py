@@ -1,34 +1,18 @@
-"""The host side of the device tissue mask: the three exports are declared and bound, `otsu_from_hist` is `otsu_threshold` from
+"""The host side of the device tissue mask: the workspace size is host arithmetic, `otsu_from_hist` is `otsu_threshold` from
 the counters on, `select_valid_sat` keeps exactly the boxes `select_valid` keeps, and `simple_get_mask` without a device is the
 chain of its parts."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 from scipy import ndimage
 
 from hover_net_amd import infer_wsi, lib as L, tissue_mask as TM
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("hvn_tissue_gray_hist", "hvn_tissue_mask_workspace_bytes", "hvn_tissue_mask")
 
-
-def test_exports_are_declared_listed_and_bound():
-    header = open(os.path.join(REPO, "include", "hvn.h")).read()
-    for name in NAMES:
-        assert re.search(r"HVN_API\s+\w+\s+%s\(" % name, header), name
-        assert name in L.EXPORTS
-    assert "hvn_tissue.hip" in L.SOURCES and os.path.isfile(os.path.join(L.CSRC, "hvn_tissue.hip"))
+def test_workspace_size_is_host_arithmetic():
     lib = L.lib()
-    assert lib.hvn_tissue_mask_workspace_bytes.restype is ctypes.c_size_t
-    assert len(lib.hvn_tissue_gray_hist.argtypes) == 6 and len(lib.hvn_tissue_mask_workspace_bytes.argtypes) == 2
-    assert len(lib.hvn_tissue_mask.argtypes) == 13
     need = lib.hvn_tissue_mask_workspace_bytes(100, 130)                 # host arithmetic only: no device is touched
     assert need >= 100 * 130 * (2 * 4 + 3) and lib.hvn_tissue_mask_workspace_bytes(0, 130) == 0
     assert lib.hvn_tissue_mask_workspace_bytes(1 << 15, (1 << 15) + 1) == 0
-    assert lib.hvn_version() == 104
 
 
 @pytest.mark.parametrize("kind", ["random", "bimodal", "constant", "two-valued", "one pixel"])

@@ -4,7 +4,6 @@ own viz_step_output) and, where the reference tree exists, against the live refe
 bookkeeping of `run_engine.VisualizeOutput` and `ValidStats.plan_viz` on a CPU state.  `==` everywhere."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import types
@@ -197,14 +196,8 @@ def test_proc_valid_step_output_default_is_unchanged_and_selected_idx():
     assert np.array_equal(pic["image"]["output"], want) and want.shape == (4 * 12, 25, 3)
 
 
-def test_export_is_declared_listed_and_bound():
-    header = open(os.path.join(REPO, "include", "hvn.h")).read()
-    assert re.search(r"HVN_API\s+int\s+hvn_viz_strip\(", header)
-    assert "hvn_viz_strip" in L.EXPORTS
-    assert "hvn_viz.hip" in L.SOURCES and os.path.isfile(os.path.join(L.CSRC, "hvn_viz.hip"))
+def test_refusals_are_host_arithmetic():
     lib = L.lib()
-    assert len(lib.hvn_viz_strip.argtypes) == 18
-    assert lib.hvn_version() == 104
     # refusals are host arithmetic: no device is touched.  Dummy non-null, aligned "pointers" are never dereferenced.
     p = ctypes.c_void_p(4096)
 

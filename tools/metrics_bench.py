@@ -71,7 +71,7 @@ def device_legs(true, pred, reps):
         need = L.lib().hvn_pair_table_workspace_bytes(m, h, w)
         bufs.append((i0, m, need, torch.empty(need, dtype=torch.uint8, device=dev), torch.empty((m, h * w, 3), dtype=torch.int32, device=dev),
                      torch.empty(m, dtype=torch.int32, device=dev)))
-    stream = M._stream(dev)
+    stream = L.stream_ptr(dev)
 
     def kernels():
         for i0, m, need, ws, tri, cnt in bufs:
