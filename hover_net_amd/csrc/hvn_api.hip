@@ -319,6 +319,48 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         if (a.nr_types > 0 && !aligned16(a.y)) return fail(HVN_E_ARG, "predmap: output not 16-byte aligned%s", "");
         return hvn_launch_predmap(a, s);
     }
+    case HVN_OP_VIEW: {
+        ViewArgs a;
+        a.x = (const uint8_t *)op->x.base;
+        a.y = (uint8_t *)op->y.base;
+        a.N = batch; a.H = op->x.h; a.W = op->x.w; a.k = op->_rsv;
+        if (a.k < 0 || a.k > 7) return fail(HVN_E_ARG, "view: view id %s%ld outside 0..7", "", a.k);
+        if (op->x_dtype != 0) return fail(HVN_E_ARG, "view: uint8 patches only (x_dtype %s%ld)", "", op->x_dtype);
+        if (!a.x || !a.y || a.x == a.y) return fail(HVN_E_ARG, "view: null pointer, or x and y are the same buffer%s", "");
+        if (a.H < 1 || a.W < 1 || op->x.c != 3 || op->y.h != a.H || op->y.w != a.W || op->y.c != 3)
+            return fail(HVN_E_ARG, "view: x and y must have the same extents, three channels (x.h = %s%ld)", "", a.H);
+        if ((a.k & 1) && a.H != a.W) return fail(HVN_E_ARG, "view: a quarter turn needs square patches (view %s%ld)", "", a.k);
+        if (batch > 65535) return fail(HVN_E_ARG, "view: batch %s%ld above 65535", "", batch);
+        if ((op->x.sx && op->x.sx != 3) || (op->y.sx && op->y.sx != 3) || op->x.sc > 1 || op->y.sc > 1)
+            return fail(HVN_E_ARG, "view: pixels are three contiguous bytes%s", "");
+        // 0 = dense; a view's rows are x.h long for odd r, which is x.w there
+        a.xsy = op->x.sy ? op->x.sy : 3L * a.W; a.xsn = op->x.sn ? op->x.sn : a.xsy * a.H;
+        a.ysy = op->y.sy ? op->y.sy : 3L * a.W; a.ysn = op->y.sn ? op->y.sn : a.ysy * a.H;
+        if (a.xsy < 3L * a.W || a.ysy < 3L * a.W || a.xsn < a.xsy * a.H || a.ysn < a.ysy * a.H)
+            return fail(HVN_E_ARG, "view: a stride shorter than a row or a sample%s", "");
+        return hvn_launch_view(a, s);
+    }
+    case HVN_OP_TTA: {
+        TtaArgs a;
+        a.np = (const float *)op->x.base;
+        a.hv = (const float *)op->res.base;
+        a.tp = op->w;
+        a.acc = (float *)op->y2.base;
+        a.y = (float *)op->y.base;
+        a.N = batch; a.H = op->y.h; a.W = op->y.w; a.nr_types = op->cout;
+        a.k = op->_rsv; a.first = op->kh != 0; a.last = op->kw != 0; a.K = op->stride;
+        if (a.k < 0 || a.k > 7) return fail(HVN_E_ARG, "tta: view id %s%ld outside 0..7", "", a.k);
+        if (a.H < 1 || a.W < 1 || a.nr_types < 0) return fail(HVN_E_ARG, "tta: empty map or negative nr_types (y.h = %s%ld)", "", a.H);
+        if ((a.k & 1) && a.H != a.W) return fail(HVN_E_ARG, "tta: a quarter turn needs square maps (view %s%ld)", "", a.k);
+        if (!a.np || !a.hv || (a.nr_types > 0 && !a.tp)) return fail(HVN_E_ARG, "tta: null pointer%s", "");
+        if (!a.acc || ((uintptr_t)a.acc & 3)) return fail(HVN_E_ARG, "tta: null or misaligned accumulator (y2)%s", "");
+        if (a.last && !a.y) return fail(HVN_E_ARG, "tta: the last view needs an output (y)%s", "");
+        if (a.last && a.K < 1) return fail(HVN_E_ARG, "tta: the last view needs the number of views (stride = %s%ld)", "", a.K);
+        if (a.last && a.y == a.acc) return fail(HVN_E_ARG, "tta: y and the accumulator are the same buffer%s", "");
+        if (a.last && (a.nr_types > 0 ? !aligned16(a.y) : (((uintptr_t)a.y & 3) != 0))) return fail(HVN_E_ARG, "tta: output not 16-byte aligned%s", "");
+        if (batch > 65535) return fail(HVN_E_ARG, "tta: batch %s%ld above 65535", "", batch);
+        return hvn_launch_tta(a, s);
+    }
     default:
         return fail(HVN_E_ARG, "unknown op kind %s%ld", "", op->kind);
     }

@@ -166,6 +166,26 @@ struct PredMapArgs {
 };
 int hvn_launch_predmap(const PredMapArgs &a, hipStream_t stream);
 
+// hvn_tta.hip: test-time augmentation over the eight views k = r + 4 f of the square (flip left-right if f, then r quarter turns
+// counter-clockwise); arguments validated by the caller (hvn_api.hip); 0, -2 launch failure
+struct ViewArgs {
+    const uint8_t *x;           // [N][H][W][3]
+    long xsn, xsy;              // byte strides of a sample and a row (pixels are 3 contiguous bytes)
+    uint8_t *y;                 // view_k(x): [N][W][H][3] for odd r (H == W there), else [N][H][W][3]
+    long ysn, ysy;
+    int N, H, W, k;
+};
+int hvn_launch_view(const ViewArgs &a, hipStream_t stream);
+
+struct TtaArgs {
+    const float *tp, *np, *hv;  // NCHW logits of view k
+    float *acc;                 // [N][H][W][3 + nr_types] = (p_np, h, v, p_0 ..) in the original orientation
+    float *y;                   // last view: [N][H][W][3|4] as PREDMAP writes it
+    int N, H, W, nr_types;      // H x W: the original orientation (a transposing view's planes are [W][H], H == W)
+    int k, first, last, K;      // first: store the term instead of adding it; last: also write acc / K and the type to y
+};
+int hvn_launch_tta(const TtaArgs &a, hipStream_t stream);
+
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)
     long xsn, xsy, xsx;

@@ -1,0 +1,170 @@
+// hvn_tta.hip -- test-time augmentation over the dihedral group of the square (hover_net_amd/tta.py).
+//
+// View k = r + 4 f of an [H][W] map a is rot90(fliplr(a) if f else a, r): the left-right flip first, then r counter-clockwise
+// quarter turns.  Pixel (i, j) of a lands at (p, q) of the view, with jb = f ? W - 1 - j : j,
+//     r = 0: (i, jb)      r = 1: (W - 1 - jb, i)      r = 2: (H - 1 - i, W - 1 - jb)      r = 3: (jb, H - 1 - i),
+// and a field of (h, v) vectors transforms as the view with every vector multiplied by M_k = R^r F^f, F = diag(-1, 1),
+// R = [[0, 1], [-1, 0]]: a signed permutation, so that M_k and its transpose are exact in fp32.
+//
+//   hvn_view   y = view_k(x) on uint8 [n][H][W][3] patches.  grid (tiles_x, tiles_y, n); a workgroup owns one 32 x 32 tile of the
+//              OUTPUT, whose source is one (clipped) 32 x 32 rectangle of the input: its rows go to LDS as runs of up to 96
+//              consecutive bytes, and the output rows are written as runs of up to 96 consecutive bytes gathered from LDS, so the
+//              transposing views (odd r) keep both sides contiguous per wave.  LDS rows are 100 bytes (25 words): a column walk of
+//              the transposing views moves one bank per pixel row.
+//   hvn_tta    PREDMAP for one view, folded into an accumulator [n][H][W][3 + T] = (p_np, h, v, p_0 .. p_{T-1}) in the ORIGINAL
+//              orientation: one thread per original pixel reads the view's logits at (p, q), forms softmax(np)[1] in PREDMAP's own
+//              form, the type probabilities exp(l_t - m) / sum_j exp(l_j - m) (j ascending), (h, v) = M_k^T (h_k, v_k), and stores
+//              the term (first view) or acc + term.  The last view also writes acc / K (IEEE division) and the first maximum of
+//              the mean type probabilities in PREDMAP's layout.  No atomics, no cross-thread sum: the summation order is the call
+//              order.  Workgroups are 16 x 16 pixels, so that the strided reads of a transposing view use whole 64-byte runs of
+//              the logit planes per workgroup (the planes are 25 - 105 KB and stay in L2).
+// Every index is bounded by the extents the caller validated (hvn_api.hip); offsets are 64-bit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hvn_kernels.h"
+
+#define VW_TILE 32
+#define VW_ROW 100      // bytes per LDS row: 96 of pixels + 4 of padding
+
+// where pixel (i, j) of an [H][W] map lands in view k
+__device__ __forceinline__ void tta_forward(int k, int H, int W, int i, int j, int &p, int &q)
+{
+    const int jb = (k & 4) ? W - 1 - j : j;
+    switch (k & 3) {
+    case 0: p = i; q = jb; break;
+    case 1: p = W - 1 - jb; q = i; break;
+    case 2: p = H - 1 - i; q = W - 1 - jb; break;
+    default: p = jb; q = H - 1 - i; break;
+    }
+}
+
+// which pixel (sy, sx) of the [H][W] source pixel (i, j) of view k shows
+__device__ __forceinline__ void tta_source(int k, int H, int W, int i, int j, int &sy, int &sx)
+{
+    int xb;
+    switch (k & 3) {
+    case 0: sy = i; xb = j; break;
+    case 1: sy = j; xb = W - 1 - i; break;
+    case 2: sy = H - 1 - i; xb = W - 1 - j; break;
+    default: sy = H - 1 - j; xb = i; break;
+    }
+    sx = (k & 4) ? W - 1 - xb : xb;
+}
+
+__global__ __launch_bounds__(256) void hvn_view(const ViewArgs a)
+{
+    __shared__ uint8_t tile[VW_TILE * VW_ROW];
+    const int Ho = (a.k & 1) ? a.W : a.H, Wo = (a.k & 1) ? a.H : a.W;
+    const int oi0 = blockIdx.y * VW_TILE, oj0 = blockIdx.x * VW_TILE;
+    const int oh = min(VW_TILE, Ho - oi0), ow = min(VW_TILE, Wo - oj0);
+    // the source rectangle: the images of two opposite corners of the output tile
+    int ay, ax, by, bx;
+    tta_source(a.k, a.H, a.W, oi0, oj0, ay, ax);
+    tta_source(a.k, a.H, a.W, oi0 + oh - 1, oj0 + ow - 1, by, bx);
+    const int sy0 = min(ay, by), sx0 = min(ax, bx);
+    const int sh = (a.k & 1) ? ow : oh, sw = (a.k & 1) ? oh : ow;
+    const uint8_t *__restrict__ src = a.x + (long)blockIdx.z * a.xsn + (long)sy0 * a.xsy + (long)sx0 * 3;
+    const int in_row = sw * 3;
+    for (int t = threadIdx.x; t < sh * in_row; t += 256) {
+        const int r = t / in_row, b = t - r * in_row;
+        tile[r * VW_ROW + b] = src[(long)r * a.xsy + b];
+    }
+    __syncthreads();
+    uint8_t *__restrict__ dst = a.y + (long)blockIdx.z * a.ysn + (long)oi0 * a.ysy + (long)oj0 * 3;
+    const int out_row = ow * 3;
+    for (int t = threadIdx.x; t < oh * out_row; t += 256) {
+        const int r = t / out_row, b = t - r * out_row;
+        const int c = b / 3, ch = b - c * 3;
+        int sy, sx;
+        tta_source(a.k, a.H, a.W, oi0 + r, oj0 + c, sy, sx);
+        dst[(long)r * a.ysy + b] = tile[(sy - sy0) * VW_ROW + (sx - sx0) * 3 + ch];
+    }
+}
+
+int hvn_launch_view(const ViewArgs &a, hipStream_t stream)
+{
+    const int Ho = (a.k & 1) ? a.W : a.H, Wo = (a.k & 1) ? a.H : a.W;
+    const dim3 grid((unsigned)((Wo + VW_TILE - 1) / VW_TILE), (unsigned)((Ho + VW_TILE - 1) / VW_TILE), (unsigned)a.N);
+    hipLaunchKernelGGL(hvn_view, grid, dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hvn_tta(const TtaArgs a)
+{
+    const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (i >= a.H || j >= a.W) return;
+    const long n = blockIdx.z;
+    const long plane = (long)a.H * a.W;       // the view's planes hold as many pixels, [W][H] for a transposing view
+    const int Wv = (a.k & 1) ? a.H : a.W;
+    int p, q;
+    tta_forward(a.k, a.H, a.W, i, j, p, q);
+    const long pix = (long)p * Wv + q;
+    const float l0 = a.np[(n * 2) * plane + pix], l1 = a.np[(n * 2 + 1) * plane + pix];
+    // PREDMAP's form (torch softmax): exp(x - max) / sum
+    const float m = fmaxf(l0, l1);
+    const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+    const float prob = e1 / (e0 + e1);
+    const float hk = a.hv[(n * 2) * plane + pix], vk = a.hv[(n * 2 + 1) * plane + pix];
+    // (h, v) = M_k^T (h_k, v_k), M_k = R^r F^f: undo the quarter turns, then the flip
+    float h, v;
+    switch (a.k & 3) {
+    case 0: h = hk; v = vk; break;
+    case 1: h = -vk; v = hk; break;
+    case 2: h = -hk; v = -vk; break;
+    default: h = vk; v = -hk; break;
+    }
+    if (a.k & 4) h = -h;
+    const int C = 3 + a.nr_types;
+    const long o = n * plane + (long)i * a.W + j;
+    float *__restrict__ acc = a.acc + o * C;
+    const float fk = (float)a.K;
+    float s_np = prob, s_h = h, s_v = v;
+    if (!a.first) {
+        s_np = acc[0] + prob;
+        s_h = acc[1] + h;
+        s_v = acc[2] + v;
+    }
+    acc[0] = s_np;
+    acc[1] = s_h;
+    acc[2] = s_v;
+    int best = 0;
+    if (a.nr_types > 0) {
+        const float *__restrict__ tp = a.tp + (n * a.nr_types) * plane + pix;
+        float tm = tp[0];
+        for (int t = 1; t < a.nr_types; ++t) tm = fmaxf(tm, tp[t * plane]);
+        float sum = 0.f;
+        for (int t = 0; t < a.nr_types; ++t) sum = sum + expf(tp[t * plane] - tm);
+        float bv = 0.f;
+        for (int t = 0; t < a.nr_types; ++t) {
+            const float pt = expf(tp[t * plane] - tm) / sum;
+            const float st = a.first ? pt : acc[3 + t] + pt;
+            acc[3 + t] = st;
+            if (a.last) {       // first maximum of the mean probabilities
+                const float mean = __fdiv_rn(st, fk);
+                if (t == 0 || mean > bv) {
+                    bv = mean;
+                    best = t;
+                }
+            }
+        }
+    }
+    if (!a.last) return;
+    const float o_np = __fdiv_rn(s_np, fk), o_h = __fdiv_rn(s_h, fk), o_v = __fdiv_rn(s_v, fk);
+    if (a.nr_types > 0) {
+        *(float4 *)(a.y + o * 4) = make_float4((float)best, o_np, o_h, o_v);
+    } else {
+        float *y = a.y + o * 3;
+        y[0] = o_np;
+        y[1] = o_h;
+        y[2] = o_v;
+    }
+}
+
+int hvn_launch_tta(const TtaArgs &a, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((a.W + 15) / 16), (unsigned)((a.H + 15) / 16), (unsigned)a.N);
+    hipLaunchKernelGGL(hvn_tta, grid, dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}

@@ -480,6 +480,61 @@ class Engine:
         logits = {br: t[:n] for br, t in self.logits.items()}
         return logits, (None if self.pred_map is None else self.pred_map[:n])
 
+    def run_tta(self, imgs, views):
+        """Test-time augmentation (hover_net_amd/tta.py): for every view id of `views`, in order, HVN_OP_VIEW turns the uint8 patches into
+        an engine-owned scratch (view 0 reads `imgs` itself), `run` does the network pass exactly as for any other batch of bytes, and
+        HVN_OP_TTA folds that view's logits -- mapped back, the HV vectors through M_k^T -- into an fp32 accumulator; the last view
+        writes the mean and the type of the mean probabilities over `pred_map`.  -> (logits of the last view, pred_map) under `run`'s
+        aliasing contract.  The accumulator and the scratch are allocated on first use.  uint8 NHWC input only."""
+        from . import tta as TT
+
+        views = TT.views(views)
+        if views is None:
+            raise ValueError("run_tta needs a view set; Engine.run is the plain step")
+        if imgs.dtype != torch.uint8:
+            raise TypeError("test-time augmentation takes uint8 NHWC patches, got %s" % imgs.dtype)
+        if self.pred_map is None:
+            raise ValueError("test-time augmentation needs a plan with the infer_step epilogue (with_predmap=True)")
+        g = self.plan.geo["inp"]
+        n = imgs.shape[0]
+        if n > self.max_batch:
+            raise ValueError("batch %d exceeds the engine's max_batch %d" % (n, self.max_batch))
+        if tuple(imgs.shape[1:]) != (g, g, 3):
+            raise ValueError("expected uint8 [N,%d,%d,3] patches, got %s" % (g, g, tuple(imgs.shape)))
+        imgs = imgs.contiguous()
+        if imgs.device != self.device:
+            imgs = imgs.to(self.device, non_blocking=True)
+        pm = self.plan.pred_map
+        T_ = self.plan.nr_types or 0
+        if getattr(self, "_tta_acc", None) is None:
+            self._tta_acc = torch.empty((self.max_batch, pm.h, pm.w, 3 + T_), dtype=torch.float32, device=self.device)
+            self._tta_scratch = torch.empty((self.max_batch, g, g, 3), dtype=torch.uint8, device=self.device)
+        vo, to = L.hvn_op(), L.hvn_op()
+        vo.kind = PL.OP_VIEW
+        vo.x.base, vo.y.base = imgs.data_ptr(), self._tta_scratch.data_ptr()
+        for v in (vo.x, vo.y):
+            v.h, v.w, v.c = g, g, 3
+        to.kind = PL.OP_TTA
+        to.x.base, to.res.base = self.logits["np"].data_ptr(), self.logits["hv"].data_ptr()
+        to.w = self.logits["tp"].data_ptr() if "tp" in self.logits else None
+        to.cout = T_
+        to.y.base = self.pred_map.data_ptr()
+        to.y.h, to.y.w, to.y.c = pm.h, pm.w, pm.c
+        to.y2.base = self._tta_acc.data_ptr()
+        to.stride = len(views)
+        logits = None
+        for idx, k in enumerate(views):
+            src = imgs
+            if k:
+                vo._rsv = k
+                L.call("hvn_run_op", ctypes.addressof(vo), n, L.stream_ptr(self.device))
+                src = self._tta_scratch[:n]
+            logits, _ = self.run(src)
+            to._rsv, to.kh, to.kw = k, int(idx == 0), int(idx == len(views) - 1)
+            L.call("hvn_run_op", ctypes.addressof(to), n, L.stream_ptr(self.device))
+        self._keepalive = imgs
+        return logits, self.pred_map[:n]
+
     def buffer(self, view, n):
         """Test hook: the activation window `view` of the first n samples as a tensor view."""
         b = view.buf

@@ -148,11 +148,13 @@ class InferManager:
         patch_input_shape, patch_output_shape (+ nr_inference_workers, nr_post_proc_workers: ignored); device_overlay (default
         False): rank 0 draws `overlay/` on the GPU (`viz.visualize_instances_dict(device=...)`, the same pixels); save_features
         (default False): every nucleus of `json/` gains "features" (`features.derive`: shape and colour; `.mat`, overlay and
-        qupath are as without it).
+        qupath are as without it); tta (default None): a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids) --
+        every network step averages the views' outputs on the GPU (`Engine.run_tta`).
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
+        from . import tta as TT
 
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         batch_size = int(run_args.get("batch_size", 32))
@@ -162,6 +164,7 @@ class InferManager:
         save_qupath = bool(run_args.get("save_qupath", False))
         save_raw_map = bool(run_args.get("save_raw_map", False))
         save_features = bool(run_args.get("save_features", False))
+        tta = TT.views(run_args.get("tta"))                 # ValueError before any file is touched
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -174,7 +177,7 @@ class InferManager:
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
-            **({"return_features": True} if save_features else {})))
+            **({"return_features": True} if save_features else {}), **({"tta": tta} if tta is not None else {})))
         done = []
         self.rounds = []                                   # files per caching round (inspected by the tests)
         while pending:
@@ -270,11 +273,14 @@ class WsiManager(InferManager):
         {slide stem: number} mapping (a slide the mapping lacks is a "crash") -- a slide whose base_mag differs from proc_mag is resampled to proc_mag as it is read
         (`open_slide`); absent = the files are taken as they are; device_mask (default False): a slide without a mask file takes its
         tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`, the same bytes on every rank); save_features (default False): every nucleus of the json
-        gains "features" (`features.derive`, shape features only: colour features on slides are out of scope).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        gains "features" (`features.derive`, shape features only: colour features on slides are out of scope); tta (default None): a view set of
+        hover_net_amd.tta -- every stage-1 network step averages the views' outputs on the GPU (`Engine.run_tta`).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
+        from . import tta as TT
 
+        tta = TT.views(run_args.get("tta"))                 # ValueError before any slide is opened
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -318,7 +324,8 @@ class WsiManager(InferManager):
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
                                                  ambiguous_size=int(run_args.get("ambiguous_size", 128)),
-                                                 **({"features": True} if run_args.get("save_features", False) else {}))
+                                                 **({"features": True} if run_args.get("save_features", False) else {}),
+                                                 **({"tta": tta} if tta is not None else {}))
                     _inst_map, inst_info = wsi.run(slide, mask)
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)

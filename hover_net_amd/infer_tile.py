@@ -334,7 +334,7 @@ def run_sharded(items, step_fn, batch_size, gather=True):
 
 # --------------------------------------------------------------------------------------------
 def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384, *,
-                   return_features=False):
+                   return_features=False, tta=None):
     """images: list of uint8 [H,W,3] arrays (RGB).  Returns a list of (pred_inst int32 [H,W] numpy, inst_info_dict | None)
     in input order: complete on rank 0 (the writer); the other ranks hold their own images' results and None elsewhere.
     `return_raw=True` appends the stitched float32 prediction map [H,W,3|4] to each tuple (`--save_raw_map`,
@@ -342,9 +342,15 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     `return_features=True` (implies the instance dict) adds "features" to every dict entry: shape and colour features of the
     nucleus (`features.derive`) from one more pass over the instance map and the image this call uploaded anyway
     (`PostProc.features`); the feature bytes travel to rank 0 as one more array of the item.
+    `tta`: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every network step is the
+    test-time-augmented one (`Engine.run_tta`); the sharding is the same, the augmentation lives inside the step.
     The images are worked off in groups of at most `max_patches` network patches (3.6 GB of uint8 patches + 1.7 GB of maps at the
     default), so that a large cache round of `process_file_list` never has all its overlapping patches in HBM at once; every rank
     forms the same groups (the collectives inside stay matched)."""
+    if tta is not None:
+        from . import tta as TT
+
+        tta = TT.views(tta)
     win = 270 if (model.module if hasattr(model, "module") and not hasattr(model, "engine") else model).mode == "original" else 256
     msk = 80 if win == 270 else 164
     groups, cur, cur_n = [], [], 0
@@ -360,13 +366,15 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     out = [None] * len(images)
     for grp in groups:
         more = {"return_features": True} if return_features else {}
+        if tta is not None:
+            more["tta"] = tta
         for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
                                                     return_raw, **more)):
             out[i] = res
     return out
 
 
-def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False):
+def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False, tta=None):
     """One group of `process_images`.
 
     Pipeline per call: patch extraction -> sharded HIP network (`run_desc.infer_step_device`)
@@ -396,7 +404,8 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
     all_patches = torch.cat(patches, 0)
     # network: contiguous patch shards; then every per-patch map goes to the ONE rank that stitches its image (image i -> rank
     # i % world) with a single all_to_all -- not to every rank
-    local = run_sharded(all_patches, lambda b: run_desc.infer_step_device(b.to(dev), model), batch_size, gather=False)
+    step_more = {"tta": tta} if tta is not None else {}
+    local = run_sharded(all_patches, lambda b: run_desc.infer_step_device(b.to(dev), model, **step_more), batch_size, gather=False)
     counts = [info.shape[0] for info in infos]
     owner = np.repeat(np.arange(len(images)) % world, counts)
     _idx, pred = route_to_owners(local, all_patches.shape[0], owner)

@@ -509,8 +509,10 @@ class DeviceMerger:
 # --------------------------------------------------------------------------------------------
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
-                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False):
-        """features=True: every entry of the instance dict gains "features" (`features.derive`): the SHAPE features of the nucleus,
+                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None):
+        """tta: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every stage-1 network step is
+        the test-time-augmented one (`Engine.run_tta`); the stitching and stage 2 see its maps as they see the plain ones.
+        features=True: every entry of the instance dict gains "features" (`features.derive`): the SHAPE features of the nucleus,
         computed per post-processed tile right after its record table (`PostProc.features`, image=None) and carried wherever the
         record bytes go (pinned slot, remote ranks, merger entries).  They are translation-invariant, so the tile origin does not
         touch them.  Colour features on slides are out of scope: stage 2 holds the prediction map, not the slide's pixels.
@@ -524,6 +526,9 @@ class WsiInference:
         self.device_contours = bool(device_contours)
         self.device_mask = bool(device_mask)
         self.features = bool(features)
+        from . import tta as TT
+
+        self.tta = TT.views(tta)
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
@@ -632,7 +637,7 @@ class WsiInference:
         return local if (as_slab or world > 1) else local.t
 
     def _step(self, batch):
-        return run_desc.infer_step_device(batch.to(self.device), self.model)
+        return run_desc.infer_step_device(batch.to(self.device), self.model, **({"tta": self.tta} if self.tta is not None else {}))
 
     # -- stage 2: three-phase post-processing ------------------------------------------------------
     def _results_in_order(self, pred_map, tiles):

@@ -14,13 +14,17 @@ from . import post_proc, run_desc
 
 
 class TilePipeline:
-    def __init__(self, model, nr_types=None, return_centroids=True, device=None, contours=False, contour_max_pts=None):
-        """contours=True: every batch's contours are traced on the side stream too (`PostProc.contours`; the instance
+    def __init__(self, model, nr_types=None, return_centroids=True, device=None, contours=False, contour_max_pts=None, *, tta=None):
+        """tta: None, or a view set of hover_net_amd.tta: every `submit` then runs the test-time-augmented step (`Engine.run_tta`).
+        contours=True: every batch's contours are traced on the side stream too (`PostProc.contours`; the instance
         separation's labels are one piece each, which is what the device tracer needs) and `submit` returns
         (inst, records, counts, pts, offs, status).  contour_max_pts: capacity of `pts` per batch (default: a quarter of the
         batch's pixels); a batch that needs more is traced again with the exact size in `wait()`.  With to_host=True the whole
         `pts` buffer is copied at that capacity (2 bytes per pixel by default), whatever part of it the batch's points fill."""
+        from . import tta as TT
+
         self.model = model
+        self.tta = TT.views(tta)
         self.nr_types = nr_types
         self.return_centroids = return_centroids
         self.contours = bool(contours)
@@ -64,7 +68,7 @@ class TilePipeline:
         self._n += 1
         if not tiles_u8.is_cuda:
             tiles_u8 = self._upload(tiles_u8, k, main)
-        pred = run_desc.infer_step_device(tiles_u8, self.model)       # aliases the engine's buffer
+        pred = run_desc.infer_step_device(tiles_u8, self.model, **({"tta": self.tta} if self.tta is not None else {}))       # aliases the engine's buffer
         if self._in[k] is not None and tiles_u8 is self._in[k]:
             self._in_free[k] = torch.cuda.Event()
             self._in_free[k].record(main)

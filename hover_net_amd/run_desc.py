@@ -25,9 +25,15 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
 
 
-def infer_step_device(batch_data, model):
+def infer_step_device(batch_data, model, tta=None):
     """uint8 [N,H,W,3] (host or device) -> float32 device tensor [N,h,w,3|4]; aliases an
-    engine buffer that the next call overwrites."""
+    engine buffer that the next call overwrites.  tta: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of
+    view ids): the map is then the mean over the views' outputs mapped back, the type that of the mean probabilities
+    (`Engine.run_tta`)."""
+    if tta is not None:
+        from . import tta as TT
+
+        tta = TT.views(tta)         # ValueError before anything is launched
     net = _unwrap(model)
     net.eval()
     if batch_data.dtype != torch.uint8:
@@ -35,12 +41,12 @@ def infer_step_device(batch_data, model):
     dev = next(net.parameters()).device
     imgs = batch_data.to(dev, non_blocking=True)
     eng = net.engine(imgs.shape[0])
-    _, pred = eng.run(imgs)
+    _, pred = eng.run(imgs) if tta is None else eng.run_tta(imgs, tta)
     return pred
 
 
-def infer_step(batch_data, model):
-    pred = infer_step_device(batch_data, model)
+def infer_step(batch_data, model, tta=None):
+    pred = infer_step_device(batch_data, model, tta)
     return pred.cpu().numpy()
 
 

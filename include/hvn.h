@@ -38,7 +38,7 @@ typedef struct hvn_view {
     int32_t sc;          /* channel stride in elements (CONV0 input only, e.g. h*w for NCHW) */
 } hvn_view;
 
-enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8 };
+enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -81,6 +81,20 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *   PREDMAP y.base = [n][h][w][3|4] = [argmax(tp)?, softmax(np)[1], hv0, hv1]
  *           (run_desc.py:185-194); x.base = np logits, res.base = hv logits, w = tp logits or NULL,
  *           cout = nr_types (0 if none)
+ *   VIEW    test-time augmentation (hover_net_amd/tta.py): y = view_k(x) on uint8 [n][h][w][3] patches (x_dtype 0 only), k = `_rsv` =
+ *           r + 4 f in 0..7: view_k(a) = rot90(fliplr(a) if f else a, r) -- the left-right flip first, then r counter-clockwise quarter
+ *           turns.  x and y have the same extents (c = 3) and are different buffers; odd r needs x.h == x.w; strides in bytes,
+ *           sy / sn = 0: dense rows / samples; HVN_E_ARG otherwise
+ *   TTA     PREDMAP for the logits of ONE view, folded into an accumulator: operands as PREDMAP (x.base = np logits, res.base = hv
+ *           logits, w = tp logits or NULL, cout = nr_types, all in the view's orientation; y.h x y.w = the map in the ORIGINAL
+ *           orientation, needed on every view), `_rsv` = view id k, y2.base = fp32 accumulator [n][h][w][3 + nr_types] = (p_np, h, v,
+ *           p_0 ..), kh != 0: first view (the term is stored, else acc + term), kw != 0: last view, which also writes
+ *           y.base = [n][h][w][3|4] = [first maximum of the mean type probabilities?, acc / K] with K = `stride` >= 1 (IEEE division).
+ *           Per original pixel (i, j) the logits are read where view_k sends (i, j); p_np = softmax(np)[1] in PREDMAP's form,
+ *           p_t = exp(l_t - m) / sum_j exp(l_j - m) (j ascending), (h, v) = M_k^T (h_k, v_k) with M_k = R^r F^f, F = diag(-1, 1),
+ *           R = [[0, 1], [-1, 0]].  Sums run in call order, without atomics: the hv channels equal the same fp32 sum bit for bit, and
+ *           one view (k = 0, K = 1) gives PREDMAP's np and hv bits.  HVN_E_ARG: k outside 0..7, h != w with odd r, no accumulator, a
+ *           last view without y or with K < 1, y not 16-byte aligned (with types)
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
