@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/hvn.h"
+#include "hvn_env.h"
 
 namespace {
 
@@ -161,9 +162,8 @@ extern "C" HVN_API long hvn_trace_contours(const int32_t *inst, int h, int w, co
     // (threads only when there is enough to share: an 80 x 80 tile's handful of nuclei is traced faster than a thread starts)
     int n_thr = 1;
     if (n_rec >= 256 && crop_px >= 200000) {
-        const char *e = getenv("HVN_HOST_THREADS");
         const unsigned hc = std::thread::hardware_concurrency();
-        n_thr = e ? atoi(e) : (int)(hc ? (hc < 16 ? hc : 16) : 4);
+        n_thr = hvn_env_int("HVN_HOST_THREADS", (int)(hc ? (hc < 16 ? hc : 16) : 4));
         if (n_thr < 1) n_thr = 1;
         if (n_thr > n_rec / 64) n_thr = n_rec / 64;
     }

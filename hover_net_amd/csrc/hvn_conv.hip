@@ -39,16 +39,12 @@
 #include "hvn_conv_common.h"
 
 #define BK 32
-// LDS row layout of the staged A / B tiles (rows of BK = 32 floats = eight 16-byte chunks):
-//   HVN_SWZ=1  (default) unpadded rows of 32 floats, chunk c of row r stored at chunk c ^ ((r >> 1) & 7): the 16 lanes of one
-//              ds_read_b128 phase (16 consecutive rows, one logical chunk) cover all 64 banks -- rows 2k / 2k+1 share a chunk slot
-//              but lie in opposite bank halves.  The staging buffers are 1/9 smaller than with padding: a 128x64 tile needs 48 KB,
-//              so THREE workgroups fit a CU's 160 KB (128x32: four); measured in profiles/r02_experiments.md section 8.
-//   HVN_SWZ=0  rows padded to 36 floats (16-byte skew per row, the round-1 layout; 54 KB per 128x64 tile = two per CU).  Kept as
-//              the A/B build `libhvn_hip_pad.so` (lib.VARIANTS).
-#ifndef HVN_SWZ
-#define HVN_SWZ 1
-#endif
+// LDS row layout of the staged A / B tiles (rows of BK = 32 floats = eight 16-byte chunks): unpadded rows of 32 floats, chunk c of
+// row r stored at chunk c ^ ((r >> 1) & 7): the 16 lanes of one ds_read_b128 phase (16 consecutive rows, one logical chunk) cover
+// all 64 banks -- rows 2k / 2k+1 share a chunk slot but lie in opposite bank halves.  The staging buffers are 1/9 smaller than with
+// round 1's rows padded to 36 floats: a 128x64 tile needs 48 KB instead of 54, so THREE workgroups fit a CU's 160 KB (128x32: four);
+// measured in profiles/r02_experiments.md section 8.
+#define LDS_LD 32
 // Diagnosis build (lib.VARIANTS["trace"]):
 //   HVN_TRACE_FINE=1  (with HVN_CONV_TRACE) 8 instead of 4 words per workgroup: + the end of each epilogue phase (accumulators in LDS and
 //                     barrier passed, residual loads returned, values finished, stores issued); the phase waits it inserts perturb the timing
@@ -57,14 +53,9 @@
 #define HVN_TRACE_FINE 0
 #endif
 #define HVN_TRACE_WORDS (HVN_TRACE_FINE ? 8 : 4)
-#if HVN_SWZ
-#define LDS_LD 32
-#else
-#define LDS_LD 36  // padded row length in floats
-#endif
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool GROUPED = false, bool HAS_PRE = true, bool HAS_X2 = false>
-__global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) void hvn_conv_igemm_f32(ConvArgs p)
+__global__ __launch_bounds__(256, (BN <= 64 && BM <= 128) ? 3 : 2) void hvn_conv_igemm_f32(ConvArgs p)
 {
     unsigned long long t_start = 0, t_kend = 0;
     if (p.dbg) t_start = __builtin_readcyclecounter();
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
     // the k-loop then carries no vector address arithmetic at all.
     const int srow = tid >> 3;      // 0..31
     const int scol = (tid & 7) * 4; // float offset inside the 32-wide k chunk
-    const int lcol = HVN_SWZ ? (((tid & 7) ^ ((srow >> 1) & 7)) * 4) : scol;  // ... and where that chunk lives in the LDS row
+    const int lcol = ((tid & 7) ^ ((srow >> 1) & 7)) * 4;  // ... and where that chunk lives in the LDS row
     const unsigned HoWo = (unsigned)(p.Ho * p.Wo);
     const unsigned n_blk = m0 / HoWo;                                        // sample of the tile's first row
     const long padoff = (long)p.pad_t * p.xsy + (long)p.pad_l * p.xsx;       // keeps every thread offset >= 0
@@ -260,7 +251,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
         const int key = (l15 >> 1) & 7;             // rows +16 / +nt*16 leave bits 1..3 of the row alone
 #pragma unroll
         for (int c = Q0 / 2; c < (Q1 + 1) / 2; ++c) {  // chunks of 16 k (4 lane groups x 4)
-            const int off = HVN_SWZ ? (((l4 + 4 * c) ^ key) * 4) : (4 * l4 + c * 16);
+            const int off = ((l4 + 4 * c) ^ key) * 4;
             const f32x4 fb = *(const f32x4 *)(b + off);
             const f32x4 fa0 = *(const f32x4 *)(a + off);
             const f32x4 fa1 = *(const f32x4 *)(a + 16 * LDS_LD + off);
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(256, (HVN_SWZ && BN <= 64 && BM <= 128) ? 3 : 2) vo
 #pragma unroll
         for (int q = Q0; q < Q1; ++q) {
             f32x4 fa[TM], fb[TN];
-            const int off = HVN_SWZ ? (((2 * q + lh) ^ key) * 4) : (q * 8 + 4 * lh);
+            const int off = ((2 * q + lh) ^ key) * 4;
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[i] = *(const f32x4 *)(a + i * 32 * LDS_LD + off);
 #pragma unroll
@@ -534,8 +525,7 @@ static int launch_conv(const ConvArgs &a, hipStream_t stream)
     static unsigned long long *dbg_buf = nullptr;
     static int dbg_on = -1;
     if (dbg_on < 0) {
-        const char *e = getenv("HVN_CONV_TRACE");   // path of a file to dump per-workgroup timestamps of the LAST launch into
-        dbg_on = e ? 1 : 0;
+        dbg_on = hvn_env_str("HVN_CONV_TRACE") ? 1 : 0;   // path of a file to dump per-workgroup timestamps of the LAST launch into
         if (dbg_on) hipMalloc(&dbg_buf, HVN_TRACE_WORDS * 8 * (size_t)(1 << 20));
     }
     p.dbg = dbg_on ? dbg_buf : nullptr;
@@ -555,7 +545,7 @@ static int launch_conv(const ConvArgs &a, hipStream_t stream)
         const size_t n = (size_t)grid * (p.nbatch > 1 ? p.nbatch : 1);
         std::vector<unsigned long long> h(HVN_TRACE_WORDS * n);
         hipMemcpy(h.data(), dbg_buf, 8 * HVN_TRACE_WORDS * n, hipMemcpyDeviceToHost);
-        if (FILE *f = fopen(getenv("HVN_CONV_TRACE"), "wb")) {
+        if (FILE *f = fopen(hvn_env_str("HVN_CONV_TRACE"), "wb")) {
             fwrite(h.data(), 8, h.size(), f);
             fclose(f);
         }
@@ -970,24 +960,15 @@ static int launch_dense_grouped3(const ConvArgs &a, int run, hipStream_t stream)
 
 int hvn_launch_dense_grouped(const ConvArgs &a, hipStream_t stream)
 {
-    static int forced = -1;   // HVN_DENSE_FORM=1 | 2 forces a form (A/B runs); default: by the column-tile waste
-    if (forced < 0) {
-        const char *e = getenv("HVN_DENSE_FORM");
-        forced = e ? atoi(e) : 0;
-    }
+    // the form, by the column-tile waste and the height:
     // form 2 (two pixels per column block, 4 x 32 tiles) does 40 % fewer MFMAs but pads the width to a multiple of 32:
     // measured faster up to ~1.55x padding (widths 58..42 and 30 of the u3 / u2 dense blocks), slower beyond (38, 34)
     // form 3 (rolling patch, runs of 4 tiles) where it was measured faster than form 2: the tall units (58, 54, 50, 52 rows: 1.12 - 1.22x);
     // below that a run-per-workgroup grid no longer fills the chip (46 .. 34 rows: 0.96 - 1.04x, 30 rows: 0.58x) -- profiles/r04_dense_ab.txt
     const int wide = ((a.Wo + 31) / 32 * 32) * 100 <= a.Wo * 155;
-    const int form = forced ? forced : (wide ? (a.Ho >= 50 ? 3 : 2) : 1);
-    if (form == 3) {            // form 2's arithmetic on a rolling patch, `run` vertically consecutive tiles per workgroup (HVN_DENSE_RUN)
-        static int run = -1;
-        if (run < 0) {
-            const char *e = getenv("HVN_DENSE_RUN");
-            run = e ? atoi(e) : 4;
-            if (run < 1) run = 1;
-        }
+    const int form = wide ? (a.Ho >= 50 ? 3 : 2) : 1;
+    if (form == 3) {            // form 2's arithmetic on a rolling patch, `run` vertically consecutive tiles per workgroup
+        constexpr int run = 4;
         if (a.KH == 5) return launch_dense_grouped3<5>(a, run, stream);
         if (a.KH == 3) return launch_dense_grouped3<3>(a, run, stream);
         return -1;

@@ -25,10 +25,11 @@
 #define BKH 64      // reduction elements per k-step
 #define LDH 72      // LDS row pitch in bf16 elements (144 B: conflict-free ds_read_b128 / ds_write_b128)
 
-// WIDE = true (round 4, default): the loop structure of hvn_conv_x3.hip -- a k-step is TWO 64-channel chunks side by side in one LDS
+// WIDE = true (round 4; every reduction of two chunks or more): the loop structure of hvn_conv_x3.hip -- a k-step is TWO 64-channel chunks side by side in one LDS
 // buffer (row pitch 272 B = 68 banks = 4 x 17: conflict-free ds_read_b128), barrier, store the staged step, barrier, issue the next
 // step's global loads, 32 MFMAs per wave between barriers instead of 16; one register stage (two workgroups per CU cover each other's
-// store phases).  WIDE = false: round 2's loop (64-channel k-steps, double-buffered LDS, ring of four register stages); HVN_BF16_LOOP=0.
+// store phases).  WIDE = false: round 2's loop (64-channel k-steps, double-buffered LDS, ring of four register stages), the
+// path of a one-chunk reduction (launch_bf16).
 #define LDW 136     // WIDE: LDS row pitch in bf16 elements (2 x 64 + 8)
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2, bool WIDE>
 __global__ __launch_bounds__(256, 2) void hvn_conv_igemm_bf16(const ConvArgs p)
@@ -408,15 +409,10 @@ static int launch_bf16w(const ConvArgs &a, hipStream_t stream)
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2>
 static int launch_bf16(const ConvArgs &a, hipStream_t stream)
 {
-    static int wide = -1;
-    if (wide < 0) {
-        const char *e = getenv("HVN_BF16_LOOP");       // 0: round 2's loop (A/B runs); default: the wide-step loop
-        wide = e ? atoi(e) : 1;
-    }
-    // a reduction of ONE 64-channel chunk (d0's conv3: K = 64) would pair it with a chunk of zeros: the narrow loop keeps it
+    // the wide-step loop; a reduction of ONE 64-channel chunk (d0's conv3: K = 64) would pair it with a chunk of zeros: the narrow loop keeps it
     const long kt = (long)a.KH * a.KW * ((a.Cin + BKH - 1) / BKH) + (a.x2 ? a.Cin2 / BKH : 0);
-    return (wide && kt >= 2) ? launch_bf16w<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, true>(a, stream)
-                             : launch_bf16w<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, false>(a, stream);
+    return kt >= 2 ? launch_bf16w<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, true>(a, stream)
+                   : launch_bf16w<BM, BN, WAVES_M, WAVES_N, PADDED, HAS_PRE, HAS_X2, false>(a, stream);
 }
 
 int hvn_launch_conv_bf16(const ConvArgs &a, int tile_n, hipStream_t stream)

@@ -379,8 +379,7 @@ static int launch_chain(const ChainArgs &a, hipStream_t stream)
     static unsigned long long *dbg_buf = nullptr;
     static int dbg_on = -1;
     if (dbg_on < 0) {
-        const char *e = getenv("HVN_CHAIN_TRACE");   // path of a file to dump the per-workgroup stamps of the LAST launch into
-        dbg_on = e ? 1 : 0;
+        dbg_on = hvn_env_str("HVN_CHAIN_TRACE") ? 1 : 0;   // path of a file to dump the per-workgroup stamps of the LAST launch into
         if (dbg_on) hipMalloc(&dbg_buf, 10 * 8 * (size_t)(1 << 20));
     }
     ChainArgs p = a;
@@ -390,7 +389,7 @@ static int launch_chain(const ChainArgs &a, hipStream_t stream)
         hipStreamSynchronize(stream);
         std::vector<unsigned long long> h(10 * (size_t)grid);
         hipMemcpy(h.data(), dbg_buf, 8 * h.size(), hipMemcpyDeviceToHost);
-        if (FILE *f = fopen(getenv("HVN_CHAIN_TRACE"), "wb")) {
+        if (FILE *f = fopen(hvn_env_str("HVN_CHAIN_TRACE"), "wb")) {
             fwrite(h.data(), 8, h.size(), f);
             fclose(f);
         }

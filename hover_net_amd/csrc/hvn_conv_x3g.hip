@@ -38,13 +38,10 @@ __global__ __launch_bounds__(BM * 2, 2) void hvn_conv_igemm_x3g(ConvArgs p)
     constexpr int NTHR = BM * 2;                 // 256 | 512
     constexpr int NW = NTHR / 64;                // waves
     // Wave tile: 64 x 64 (TI = TJ = 2: two waves side by side read and split the same A fragment -- 88 VALU per slice and wave next to 24 MFMAs).
-    // Round 6 measured the alternative, 32 pixel rows x all 128 channels per wave (HVN_X3G_WN=1, lib.VARIANTS["wn1"]: the split done once, 44
+    // Round 6 measured the alternative, 32 pixel rows x all 128 channels per wave (WAVES_N = 1, a variant build since removed: the split done once, 44
     // VALU per slice, 14 instead of 10 fragment reads, 210 - 248 VGPRs, same per-accumulator MFMA order = same bits): conv launches of a step 42.03
     // vs 41.71 ms, bench 755.4 vs 754.8 tiles/s -- neutral, i.e. the split's VALU is NOT what holds the matrix pipe at 49 % (profiles/r06_x3g_wave_tile_ab.txt).
-#ifndef HVN_X3G_WN
-#define HVN_X3G_WN 2
-#endif
-    constexpr int WAVES_N = HVN_X3G_WN;
+    constexpr int WAVES_N = 2;
     constexpr int TI = BM / (NW / WAVES_N) / 32;      // 32-row tiles per wave: 1 | 2
     constexpr int TJ = GBN / WAVES_N / 32;            // 32-column tiles per wave: 4 | 2
     static_assert(TI * TJ == 4, "four accumulators per wave");

@@ -1,9 +1,8 @@
 // hvn_net_ops.hip -- the non-GEMM launches of the network plan (HBM-bound byte movers).
 //
 //   conv0    /root/reference/models/hovernet/net_desc.py:27-35,103 : uint8 image -> 7x7x3
-//            conv (1/255 and BN folded) + ReLU.  K = 147 is too thin for the matrix cores;
-//            done on the VALU with the taps streamed through the scalar cache (they are
-//            wave-uniform), the uint8 patch staged once in LDS.
+//            conv (1/255 and BN folded) + ReLU on the matrix cores (hvn_conv0_mfma), the
+//            uint8 patch and the taps staged once in LDS.
 //   upadd    net_utils.py:284-294 + net_desc.py:133,136,139 : nearest 2x upsample + skip add
 //   head     net_desc.py:62-68 u0.conv : 64 -> {2..} logits + bias, written NCHW
 //   predmap  run_desc.py:185-194 : softmax(np)[1], argmax(softmax(tp)), concat
@@ -16,61 +15,10 @@
 // ---------------------------------------------------------------------------------------
 #define C0_T 16              // output tile edge
 #define C0_P (C0_T + 6)      // patch edge
-template <typename T>
-__global__ __launch_bounds__(256) void hvn_conv0(const Conv0Args p)
-{
-    __shared__ float patch[C0_P][C0_P * 3 + 2];
-    const int tid = threadIdx.x;
-    const int n = blockIdx.z;
-    const int oy0 = blockIdx.y * C0_T, ox0 = blockIdx.x * C0_T;
-    const T *img = (const T *)p.img + (long)n * p.isn;
-    for (int i = tid; i < C0_P * C0_P * 3; i += 256) {
-        const int py = i / (C0_P * 3), pr = i - py * (C0_P * 3);
-        const int px = pr / 3, ch = pr - px * 3;
-        const int iy = oy0 + py - p.pad, ix = ox0 + px - p.pad;
-        float v = 0.f;
-        if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) v = (float)img[(long)iy * p.isy + (long)ix * p.isx + (long)ch * p.isc];
-        patch[py][pr] = v;
-    }
-    __syncthreads();
-    const int ty = tid >> 4, tx = tid & 15;
-    float acc[64];
-#pragma unroll
-    for (int c = 0; c < 64; ++c) acc[c] = p.bias[c];
-    for (int r = 0; r < 7; ++r) {
-        const float *prow = &patch[ty + r][tx * 3];
-        for (int s3 = 0; s3 < 21; ++s3) {
-            const float v = prow[s3];
-            const float *__restrict__ wp = p.w + (r * 21 + s3) * 64;  // wave-uniform -> s_load
-#pragma unroll
-            for (int c = 0; c < 64; ++c) acc[c] = fmaf(v, wp[c], acc[c]);
-        }
-    }
-    const int oy = oy0 + ty, ox = ox0 + tx;
-    const float lo = p.relu ? 0.f : -__builtin_inff();
-    if (oy < p.Ho && ox < p.Wo) {
-        const long yoff = (long)n * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx;
-        if (p.out_bf16) {   // bf16 activations (RNE)
-            uint16_t *y = (uint16_t *)p.y + yoff;
-#pragma unroll
-            for (int c = 0; c < 64; c += 4) {
-                bf16x2 h0 = {(__bf16)fmaxf(acc[c], lo), (__bf16)fmaxf(acc[c + 1], lo)};
-                bf16x2 h1 = {(__bf16)fmaxf(acc[c + 2], lo), (__bf16)fmaxf(acc[c + 3], lo)};
-                *(uint2 *)(y + c) = make_uint2(__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, h1));
-            }
-        } else {
-            float *y = p.y + yoff;
-#pragma unroll
-            for (int c = 0; c < 64; c += 4)
-                *(float4 *)(y + c) = make_float4(fmaxf(acc[c], lo), fmaxf(acc[c + 1], lo), fmaxf(acc[c + 2], lo), fmaxf(acc[c + 3], lo));
-        }
-    }
-}
-
 // conv0 on the matrix cores: 16x16 output pixels x 64 channels per workgroup, K = 7*7*3 = 147 (+1 zero) walked as 74
 // v_mfma_f32_32x32x2_f32 steps per block.  The A operand is gathered straight out of the staged image patch (lane = pixel,
 // k -> (tap row, tap col * 3 + ch) is a compile-time offset), B out of the [148][64] taps in LDS; 1.5 LDS reads per MFMA.
-// Replaces the VALU kernel above (1.46 ms -> see profiles; HVN_CONV0_VALU=1 keeps the old one for A/B runs).
+// Replaced the VALU kernel of round 1 (1.46 ms -> see profiles), which is gone.
 #define C0_PITCH (C0_P * 3 + 2)
 template <typename T>
 __global__ __launch_bounds__(256) void hvn_conv0_mfma(const Conv0Args p)
@@ -143,19 +91,10 @@ __global__ __launch_bounds__(256) void hvn_conv0_mfma(const Conv0Args p)
 int hvn_launch_conv0(const Conv0Args &a, hipStream_t stream)
 {
     dim3 grid((a.Wo + C0_T - 1) / C0_T, (a.Ho + C0_T - 1) / C0_T, a.N);
-    static int valu = -1;
-    if (valu < 0) valu = getenv("HVN_CONV0_VALU") ? 1 : 0;
-    if (!valu) {
-        if (a.is_f32)
-            hipLaunchKernelGGL(hvn_conv0_mfma<float>, grid, dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL(hvn_conv0_mfma<uint8_t>, grid, dim3(256), 0, stream, a);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
     if (a.is_f32)
-        hipLaunchKernelGGL(hvn_conv0<float>, grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(hvn_conv0_mfma<float>, grid, dim3(256), 0, stream, a);
     else
-        hipLaunchKernelGGL(hvn_conv0<uint8_t>, grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(hvn_conv0_mfma<uint8_t>, grid, dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -314,9 +253,6 @@ int hvn_launch_predmap(const PredMapArgs &a, hipStream_t stream)
 // n^2 multiplications per m^2 outputs instead of 25 m^2 (hover_net_amd/winograd.py derives the matrices).
 // Both kernels are HBM-bound byte movers: one thread = one tile x VW channels, consecutive threads on
 // consecutive channels.  VW = 4 (16-byte accesses) where the n^2 x VW register tile fits, 2 for the 8x8 input tile.
-#ifndef HVN_WINO_XCD
-#define HVN_WINO_XCD 1             // (lib.py VARIANTS "noxcd": 0, the A/B build)
-#endif
 template <int VW> struct WVec;
 template <> struct WVec<4> { typedef float T __attribute__((ext_vector_type(4))); };
 template <> struct WVec<2> { typedef float T __attribute__((ext_vector_type(2))); };
@@ -331,12 +267,10 @@ __global__ __launch_bounds__(256) void hvn_wino_in(const WinoArgs p, long total)
     // (blockIdx % 8), each with an L2 of its own: in launch order every XCD would fetch every halo from HBM for itself.  XCD k takes
     // the k-th CONTIGUOUS eighth of the (tile, channel slice) list instead, so a halo is re-read from the L2 that already holds it.
     unsigned bid = blockIdx.x;
-#if HVN_WINO_XCD
     {
         const unsigned per = gridDim.x >> 3;
         if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
     }
-#endif
     const long i = (long)bid * 256 + threadIdx.x;
     if (i >= total) return;
     const int cvn = p.C / VW;

@@ -1360,15 +1360,8 @@ static int postproc_impl(const float *pred, int n, int h, int w, int c, int c0, 
     hipLaunchKernelGGL(pp_marker_labels, grid, blk, 0, s, b);
     // taps first: the watershed stage recycles dead planes
     if (tap_marker) hipMemcpyAsync(tap_marker, b.mk, (size_t)n * b.P * 4, hipMemcpyDeviceToDevice, s);
-    static int ws_mode = -1, ws_wave = 1, ws_bitmap = 1;  // HVN_WS_GLOBAL=1 forces the whole-tile replay everywhere (tests)
-    if (ws_mode < 0) {
-        const char *e = getenv("HVN_WS_GLOBAL");
-        ws_mode = (e && atoi(e)) ? 1 : 0;
-        e = getenv("HVN_WS_WAVE");
-        ws_wave = e ? atoi(e) : 1;
-        e = getenv("HVN_WS_BITMAP");
-        ws_bitmap = e ? atoi(e) : 1;
-    }
+    static const int ws_mode = hvn_env_int("HVN_WS_GLOBAL", 0) ? 1 : 0;   // 1 forces the whole-tile replay everywhere (tests)
+    static const int ws_wave = hvn_env_int("HVN_WS_WAVE", 1), ws_bitmap = hvn_env_int("HVN_WS_BITMAP", 1);
     b.no_wave = ws_wave ? 0 : 1;
     b.no_bitmap = ws_bitmap ? 0 : 1;
     hipLaunchKernelGGL(ws_init, grid, blk, 0, s, b);
@@ -1384,7 +1377,7 @@ static int postproc_impl(const float *pred, int n, int h, int w, int c, int c0, 
         hipLaunchKernelGGL(ws_component, dim3((unsigned)maxc, n), dim3(64), WS_LDS_BYTES, s, b, 1, WS_LDS_BYTES);
     }
     hipLaunchKernelGGL(ws_fallback, dim3(n), dim3(64), WS_LDS_BYTES, s, b, ws_mode);
-    if (getenv("HVN_WS_STATS")) {   // diagnosis: which replay each component took (synchronous)
+    if (hvn_env_str("HVN_WS_STATS")) {   // diagnosis: which replay each component took (synchronous)
         hipStreamSynchronize(s);
         std::vector<TileStat> hs(n);
         hipMemcpy(hs.data(), b.stat, sizeof(TileStat) * (size_t)n, hipMemcpyDeviceToHost);

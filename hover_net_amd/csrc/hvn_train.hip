@@ -411,9 +411,8 @@ long hvn_wgrad_split(const WgradArgs &a, long tiles, unsigned *rows_per_split)
     // HVN_WGRAD_WGS / HVN_WGRAD_MIN_ROWS override (tools/wgrad_sweep.py; read per launch so that one process can sweep them).
     const long R = (long)a.N * a.Ho * a.Wo;
     const int nb = a.nbatch > 1 ? a.nbatch : 1;
-    const char *e_wgs = getenv("HVN_WGRAD_WGS"), *e_rows = getenv("HVN_WGRAD_MIN_ROWS");
-    const long want = e_wgs ? atol(e_wgs) : (a.want_wgs > 0 ? a.want_wgs : 1536);
-    const long min_rows = e_rows ? atol(e_rows) : 256;
+    const long want = hvn_env_int("HVN_WGRAD_WGS", a.want_wgs > 0 ? a.want_wgs : 1536);
+    const long min_rows = hvn_env_int("HVN_WGRAD_MIN_ROWS", 256);
     long ksplit = (want + tiles * nb - 1) / (tiles * nb);
     const long max_split = (R + min_rows - 1) / min_rows;
     if (ksplit > max_split) ksplit = max_split;
@@ -971,77 +970,15 @@ int hvn_launch_head_bwd(const HeadBwdArgs &a, hipStream_t stream)
 
 // =========================================================================================
 // conv0 weight gradient: dW[co][r][s][ch] += sum dz[n,oy,ox,co] * img[n, oy+r-pad, ox+s-pad, ch] / 255
-// One workgroup walks several 16x16 output tiles: image patch (22x22x3) and the dz tile (256 px x 64 co) in LDS;
-// thread = (co, tap phase): 37 of the 147 (r, s*3+ch) taps each, register accumulators across the tiles.
+// One workgroup walks several 16x16 output tiles: image patch (22x22x3) and the dz tile in LDS.
 // =========================================================================================
 #define W0_T 16
 #define W0_P (W0_T + 6)
-__global__ __launch_bounds__(256) void hvn_conv0_wgrad(const Conv0WgradArgs p, int tiles_x, int tiles_y, long tiles_total)
-{
-    __shared__ float patch[W0_P][W0_P * 3 + 2];
-    __shared__ float dz[W0_T * W0_T / 2][64];
-    const int tid = threadIdx.x;
-    const int co = tid & 63;
-    const int ph = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform tap phase
-    float acc[37];
-#pragma unroll
-    for (int k = 0; k < 37; ++k) acc[k] = 0.f;
-    for (long tile = blockIdx.x; tile < tiles_total; tile += gridDim.x) {
-        const int tx = (int)(tile % tiles_x);
-        const long t2 = tile / tiles_x;
-        const int ty = (int)(t2 % tiles_y);
-        const int n = (int)(t2 / tiles_y);
-        const int oy0 = ty * W0_T, ox0 = tx * W0_T;
-        __syncthreads();
-        const uint8_t *img = p.img + (long)n * p.isn;
-        for (int i = tid; i < W0_P * W0_P * 3; i += 256) {
-            const int py = i / (W0_P * 3), pr = i - py * (W0_P * 3);
-            const int px = pr / 3, ch = pr - px * 3;
-            const int iy = oy0 + py - p.pad, ix = ox0 + px - p.pad;
-            float v = 0.f;
-            if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) v = (float)img[(long)iy * p.isy + (long)ix * p.isx + ch];
-            patch[py][pr] = v * (1.0f / 255.0f);
-        }
-        for (int half = 0; half < 2; ++half) {      // the dz tile goes through LDS in two halves of 8 rows
-            if (half) __syncthreads();
-            for (int i = tid; i < (W0_T * W0_T / 2) * 16; i += 256) {
-                const int pix = i >> 4, c4 = i & 15;
-                const int oy = oy0 + half * 8 + (pix >> 4), ox = ox0 + (pix & 15);
-                f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (oy < p.Ho && ox < p.Wo) v = *(const f32x4 *)(p.dy + (long)n * p.ysn + (long)oy * p.ysy + (long)ox * p.ysx + c4 * 4);
-                *(f32x4 *)&dz[pix][c4 * 4] = v;
-            }
-            __syncthreads();
-            for (int pix = 0; pix < W0_T * W0_T / 2; ++pix) {
-                const float g = dz[pix][co];
-                const float *prow = &patch[half * 8 + (pix >> 4)][(pix & 15) * 3];
-#pragma unroll
-                for (int k = 0; k < 37; ++k) {
-                    const int tap = ph + 4 * k;  // 0..146 (the last phases have one tap less)
-                    if (tap < 147) {
-                        const int r = tap / 21, s3 = tap - r * 21;
-                        acc[k] = fmaf(g, prow[r * (W0_P * 3 + 2) + s3], acc[k]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 37; ++k) {
-        const int tap = ph + 4 * k;
-        if (tap >= 147) continue;
-        if (p.part)
-            p.part[(long)blockIdx.x * (64 * 147) + co * 147 + tap] = acc[k];
-        else
-            unsafeAtomicAdd(p.dw + (long)co * 147 + tap, acc[k]);
-    }
-}
-
 // conv0 weight gradient on the matrix cores: D[co][kidx] = sum_px dz[px][co] * P[px][kidx] with P gathered from the staged
 // image patch (kidx -> (tap row, tap col*3 + ch) is a per-lane constant offset), M = 64 channels (2 blocks), N = 147 (+13)
 // taps (5 blocks), K = pixels.  A wave reduces 32 pixels of each 8-row half tile (16 k-steps x 10 MFMAs) and keeps its
 // 64 x 160 partial in registers across all the tiles of the workgroup; the four waves' partials are summed through LDS and
-// leave with one atomic per weight.  ~10x the VALU kernel above (HVN_CONV0_WGRAD_VALU=1 keeps that one).
+// leave with one atomic per weight.  ~10x the VALU kernel (one thread per (co, tap phase)) it replaced.
 #define W0M_PITCH (W0_P * 3 + 2)
 __global__ __launch_bounds__(256) void hvn_conv0_wgrad_mfma(const Conv0WgradArgs p, int tiles_x, int tiles_y, long tiles_total)
 {
@@ -1138,16 +1075,10 @@ __global__ __launch_bounds__(256) void hvn_conv0_wgrad_mfma(const Conv0WgradArgs
     }
 }
 
-static inline bool conv0_wgrad_valu()
-{
-    static int valu = -1;
-    if (valu < 0) valu = getenv("HVN_CONV0_WGRAD_VALU") ? 1 : 0;
-    return valu != 0;
-}
 static inline long conv0_wgrad_wgs(const Conv0WgradArgs &a)
 {
     const int tx = (a.Wo + W0_T - 1) / W0_T, ty = (a.Ho + W0_T - 1) / W0_T;
-    const long total = (long)tx * ty * a.N, cap = conv0_wgrad_valu() ? 1024 : 512;
+    const long total = (long)tx * ty * a.N, cap = 512;
     return total < cap ? total : cap;
 }
 long hvn_conv0_wgrad_part_floats(const Conv0WgradArgs &a) { return conv0_wgrad_wgs(a) * 64 * 147; }
@@ -1158,13 +1089,10 @@ int hvn_launch_conv0_wgrad(const Conv0WgradArgs &a, hipStream_t stream)
     const long total = (long)tx * ty * a.N;
     const long blocks = conv0_wgrad_wgs(a);
     if (a.part && blocks * 64 * 147 > a.part_cap) return -4;
-    if (!conv0_wgrad_valu()) {
-        const size_t lds = (size_t)(W0_P * W0M_PITCH + 64 * 160) * sizeof(float);
-        static std::atomic<unsigned long long> attr{0};
-        if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv0_wgrad_mfma), (int)lds, attr)) return -2;
-        hipLaunchKernelGGL(hvn_conv0_wgrad_mfma, dim3((unsigned)blocks), dim3(256), lds, stream, a, tx, ty, total);
-    } else
-        hipLaunchKernelGGL(hvn_conv0_wgrad, dim3((unsigned)blocks), dim3(256), 0, stream, a, tx, ty, total);
+    const size_t lds = (size_t)(W0_P * W0M_PITCH + 64 * 160) * sizeof(float);
+    static std::atomic<unsigned long long> attr{0};
+    if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv0_wgrad_mfma), (int)lds, attr)) return -2;
+    hipLaunchKernelGGL(hvn_conv0_wgrad_mfma, dim3((unsigned)blocks), dim3(256), lds, stream, a, tx, ty, total);
     if (launch_ok()) return -2;
     return a.part ? hvn_launch_reduce_parts(a.dw, a.part, 64 * 147, blocks, 64 * 147, stream) : 0;
 }

@@ -15,6 +15,7 @@ import torch
 from . import lib as L
 from . import plan as PL
 from . import tune as T
+from .knobs import knob
 from .tune import X3G_128, X3G_256, X3R  # noqa: F401  (the form codes, importable from here as before)
 
 
@@ -113,11 +114,10 @@ class Engine:
         # Default launch schedule (round 4): fp32 = two encoder sub-batches on two streams + the decoder branches on three
         # (measured +2.6 .. +3.3 %, bit-equal outputs: tests/test_gpu_chain.py); `n_split=1, n_lanes=0` (or HVN_SPLIT=1 HVN_LANES=0)
         # is the single launch stream on which every launch can be timed alone (bench.py's roofline leg, the PMC runs).
-        import os
         dflt = ("2", "2") if dtype == "fp32" else ("1", "0")
-        self.n_split = int(os.environ.get("HVN_SPLIT", dflt[0])) if n_split is None else int(n_split)
-        self.n_lane_streams = int(os.environ.get("HVN_LANES", dflt[1])) if n_lanes is None else int(n_lanes)  # extra streams for the decoder branches (0: one launch stream)
-        self.split_decoder = os.environ.get("HVN_SPLIT_DECODER", "0") != "0"
+        self.n_split = int(knob("HVN_SPLIT") or dflt[0]) if n_split is None else int(n_split)
+        self.n_lane_streams = int(knob("HVN_LANES") or dflt[1]) if n_lanes is None else int(n_lanes)  # extra streams for the decoder branches (0: one launch stream)
+        self.split_decoder = knob("HVN_SPLIT_DECODER") != "0"
         self._streams = None
         self._stream_off = 0
         self._upload_params()

@@ -35,6 +35,7 @@ import torch
 
 from . import infer_tile, post_proc, run_desc
 from . import lib as L
+from .knobs import knob
 
 
 # --------------------------------------------------------------------------------------------
@@ -729,8 +730,7 @@ class WsiInference:
         # Mpixel leave most of the chip idle, two or three tiles in flight fill it
         lanes = self.__dict__.setdefault("_pp_lanes", [])
         if not lanes:
-            import os
-            for _ in range(max(1, int(os.environ.get("HVN_WSI_LANES", "3")))):
+            for _ in range(max(1, int(knob("HVN_WSI_LANES")))):
                 lanes.append((torch.cuda.Stream(self.device), post_proc.PostProc(self.device)))
             self._pp_next = 0
         stream, pp = lanes[self._pp_next % len(lanes)]
@@ -827,10 +827,9 @@ class WsiInference:
         self._shape = shape
         if mask is None:
             mask = np.ones((max(1, int(shape[0]) // 32), max(1, int(shape[1]) // 32)), np.uint8)
-        import os
 
         rank = infer_tile._dist()[1]
-        on_device = self.device.type == "cuda" and os.environ.get("HVN_WSI_HOST_MERGE", "0") == "0"
+        on_device = self.device.type == "cuda" and knob("HVN_WSI_HOST_MERGE") == "0"
         merger = None if rank != 0 else (DeviceMerger(shape, self.device) if on_device else WsiMerger(shape))
         for phase, tiles in enumerate(self.tile_lists(shape, mask)):
             # the merge is sequential by definition (wsi.py:569-677) and runs on rank 0, under the GPU work of later tiles

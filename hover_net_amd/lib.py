@@ -8,19 +8,19 @@ import os
 import re
 import subprocess
 
+from .knobs import knob
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhvn_hip.so")
 # Experiment builds of the same sources (`build_variant`), loaded INSTEAD of the default library when HVN_LIB_VARIANT names one:
 # kernel A/B runs on one box without rebuilding there.  Not used by the product path (unset = libhvn_hip.so).
 VARIANTS = {
-    "pad": ("-DHVN_SWZ=0",),                        # padded LDS rows (round-1 layout) instead of the XOR swizzle
-    "noxcd": ("-DHVN_WINO_XCD=0", "-DHVN_CONV_XCD_CONTIG=0"),   # A/B: round-robin tile order in the Winograd input transform and the multi-tap convolutions
-    "fullepi": ("-DHVN_X3G_FULL_EPI=1",),           # A/B (round 6): hvn_conv_igemm_x3g with the one full epilogue of rounds 1-5 instead of the 8 operand-set forms
-    "wn1": ("-DHVN_X3G_WN=1",),                      # A/B (round 6, neutral): hvn_conv_igemm_x3g with 32 x 128 wave tiles (every wave splits its A fragment once)
+    "fullepi": ("-DHVN_X3G_FULL_EPI=1",),           # hvn_conv_igemm_x3g with the one full epilogue of rounds 1-5: the reference tools/epilogue_forms_check.py holds the 8 operand-set forms to
     "prev": (),                                      # same-box A/B against ANOTHER CHECKOUT's library: built by hand into libhvn_hip_prev.so (never by build_variant)
     "trace": ("-DHVN_TRACE_FINE=1",),               # diagnosis: per-phase timestamps of the conv epilogue (with HVN_CONV_TRACE, tools/conv_trace.py --fine)
 }
 CSRC = os.path.join(_HERE, "csrc")
+HEADERS = ("hvn_conv_common.h", "hvn_env.h", "hvn_kernels.h")
 SOURCES = ("hvn_conv.hip", "hvn_conv_chain.hip", "hvn_conv_chain_x3.hip", "hvn_conv_chain_x3r.hip", "hvn_conv_bf16.hip", "hvn_conv_bf16g.hip", "hvn_conv_chain_bf16.hip", "hvn_conv_x3.hip", "hvn_conv_x3g.hip", "hvn_net_ops.hip", "hvn_postproc.hip", "hvn_api.hip", "hvn_train.hip", "hvn_wgrad_x3.hip", "hvn_targets.hip", "hvn_wsi_merge.hip",
            "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_contour_dev.hip", "hvn_metrics.hip", "hvn_valid.hip", "hvn_overlay.hip", "hvn_resample.hip", "hvn_tissue.hip", "hvn_viz.hip", "hvn_features.hip", "hvn_tta.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -87,7 +87,7 @@ def source_id():
     import hashlib
 
     h = hashlib.sha256()
-    for f in sorted(SOURCES) + ["hvn_conv_common.h", "hvn_kernels.h"]:
+    for f in sorted(SOURCES) + list(HEADERS):
         h.update(f.encode())
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read())
@@ -131,7 +131,7 @@ def _compile(out, extra, verbose):
     sid = source_id() + ("" if not extra else "+" + "".join(extra))
     objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
-    hdr = open(os.path.join(CSRC, "hvn_kernels.h"), "rb").read() + open(os.path.join(CSRC, "hvn_conv_common.h"), "rb").read() + open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read()
+    hdr = b"".join(open(os.path.join(CSRC, f), "rb").read() for f in HEADERS) + open(os.path.join(os.path.dirname(_HERE), "include", "hvn.h"), "rb").read()
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra)
     jobs, objs = [], []
     for src in SOURCES:
@@ -185,7 +185,7 @@ def build_variant(name, verbose=False):
 
 
 def lib_path():
-    v = os.environ.get("HVN_LIB_VARIANT", "")
+    v = knob("HVN_LIB_VARIANT")
     if not v:
         return LIB_PATH
     if v not in VARIANTS:
@@ -211,13 +211,13 @@ def lib():
         L = ctypes.CDLL(path)
         L.hvn_build_id.restype = ctypes.c_char_p
         built = L.hvn_build_id().decode()
-        if os.path.isdir(CSRC) and not os.environ.get("HVN_LIB_VARIANT") and built != source_id():
+        if os.path.isdir(CSRC) and not knob("HVN_LIB_VARIANT") and built != source_id():
             raise HvnError("%s was built from other sources (library %s, sources %s): run `python -c 'import __graft_entry__ as g; g.build()'`"
                            % (os.path.basename(path), built, source_id()))
         for name, (restype, argtypes) in PROTOS.items():
             fn = getattr(L, name, None)
             if fn is None:
-                if os.environ.get("HVN_LIB_VARIANT"):   # another checkout's library (variant "prev") may predate an entry point
+                if knob("HVN_LIB_VARIANT"):   # another checkout's library (variant "prev") may predate an entry point
                     continue
                 raise HvnError("%s does not export %s, which include/hvn.h declares" % (os.path.basename(path), name))
             fn.restype, fn.argtypes = restype, argtypes

@@ -15,13 +15,13 @@ computed on them in torch and `loss.backward()` hand the logit gradients to the 
 parameters' gradients -- so the module is "autograd-capable in train mode"  although no torch op computes a
 gradient.  `run_desc.train_step` does not take this detour: its losses and logit gradients are fused kernels.
 """
-import os
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from . import arch
+from .knobs import knob
 
 
 class _Node(nn.Module):
@@ -91,9 +91,6 @@ class _TrainForward(torch.autograd.Function):
         return (None, None) + out
 
 
-BF16_CHAIN_DEFAULT = "d0d1"      # which blocks' seams the bf16 plan chains by default (set from the measurement: DESIGN section 4.8)
-
-
 class HoVerNet(nn.Module):
     """Initialise HoVer-Net (interface of net_desc.py:14-99)."""
 
@@ -114,7 +111,7 @@ class HoVerNet(nn.Module):
         self.max_batch = 32
         # "fp32" (parity configuration, logits within 1e-3) or "bf16" (BASELINE cfg 3: bf16 weights / activations, fp32
         # accumulation; no reference bf16 exists, the declared tolerance is on the fp32 logits, tests/test_gpu_bf16.py)
-        self.compute_dtype = os.environ.get("HVN_DTYPE", "fp32")
+        self.compute_dtype = knob("HVN_DTYPE")
         # launch schedule of the inference engine: None = the engine's default (fp32: two encoder sub-batches + decoder branch
         # streams), or (n_split, n_lanes); (1, 0) = one launch stream (every launch can then be timed alone: bench.py's roofline leg)
         self.launch_schedule = None
@@ -145,14 +142,12 @@ class HoVerNet(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("HoVerNet runs on MI355X only: call .to('cuda') first (no CPU fallback)")
-        import os
-        key = (self._weights_version(), str(dev), self.compute_dtype, self.launch_schedule, self.lowering, os.environ.get("HVN_BF16_CHAIN", BF16_CHAIN_DEFAULT))
+        key = (self._weights_version(), str(dev), self.compute_dtype, self.launch_schedule, self.lowering, knob("HVN_BF16_CHAIN"))
         if self._engine is None or self._engine_key != key or batch > self._engine.max_batch:
             sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
             bf16 = self.compute_dtype == "bf16"
             # bf16: direct convolutions, no bf16x3; HVN_BF16_CHAIN = d0 | d0d1 chains those blocks' conv3 -> conv1 seams (csrc/hvn_conv_chain_bf16.hip, same bits), 0 none
-            import os
-            bchain = os.environ.get("HVN_BF16_CHAIN", BF16_CHAIN_DEFAULT)
+            bchain = knob("HVN_BF16_CHAIN")
             plan = PL.build_plan(sd, self.mode, self.nr_types, winograd=0 if bf16 else None,
                                  chain=(("bf16:" + bchain) if bchain not in ("0", "") else False) if bf16 else None, x3=0 if bf16 else None,
                                  lowering=self.lowering)

@@ -33,6 +33,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import arch
+from .knobs import knob
 
 OP_CONV0, OP_CONV, OP_UPADD, OP_HEAD, OP_PREDMAP, OP_WINO_IN, OP_WINO_OUT, OP_CHAIN = 1, 2, 3, 4, 5, 6, 7, 8
 OP_VIEW, OP_TTA = 9, 10     # test-time augmentation (tta.py): never part of a plan, issued around it by Engine.run_tta
@@ -151,7 +152,6 @@ _WINO_PACKED_BYTES = [0]
 
 def _wino_packed(wt, m, n2, cout, cin, cout_pad):
     """U = G g G^T of every (cout, cin) filter, packed [n2, cout_pad, cin / 32, 1, 32] fp32 (see `conv_winograd`)."""
-    import os
 
     from . import winograd as WG
     try:
@@ -168,7 +168,7 @@ def _wino_packed(wt, m, n2, cout, cin, cout_pad):
         hit[:, :cout] = u.reshape(n2, cout, cin // 32, 1, 32)
         _WINO_PACKED_BYTES[0] += hit.nbytes
     _WINO_PACKED[key] = hit                                                   # (re)inserted last = most recently used
-    limit = int(os.environ.get("HVN_WINO_CACHE_MB", "2048")) << 20
+    limit = int(knob("HVN_WINO_CACHE_MB")) << 20
     while _WINO_PACKED_BYTES[0] > limit and len(_WINO_PACKED) > 1:
         old_key = next(iter(_WINO_PACKED))
         _WINO_PACKED_BYTES[0] -= _WINO_PACKED.pop(old_key).nbytes
@@ -442,7 +442,6 @@ def build_plan(sd, mode="original", nr_types=None, with_predmap=True, winograd=N
     (env HVN_CHAIN=0 turns it off, HVN_CHAIN_MAXN2 = 64 | 128 bounds the second conv's width); fp32 only.
     x3: 0 = every fp32 conv on the fp32 matrix pipe; 9 | 6 = the MFMA-bound conv launches form their products on the bf16 matrix pipe
     from exact three-way bf16 splits of the fp32 operands (csrc/hvn_conv_x3.hip, `Plan.mark_x3`); default env HVN_X3; fp32 only."""
-    import os
     if lowering not in LOWERINGS:
         raise ValueError("lowering must be one of %s, got %r" % (LOWERINGS, lowering))
     conservative = lowering == "conservative"
@@ -451,19 +450,19 @@ def build_plan(sd, mode="original", nr_types=None, with_predmap=True, winograd=N
     # F(4x4, .) Winograd tiles everywhere (the smallest transform constants) and all NINE partial products of the bf16x3 convolution
     # (the fp32 dot product in another summation order, nothing dropped).  ~15 % slower.
     if chain is None:
-        chain = os.environ.get("HVN_CHAIN", "1") != "0"
+        chain = knob("HVN_CHAIN") != "0"
     if winograd is None:
-        winograd = 4 if conservative else int(os.environ.get("HVN_WINOGRAD", "4"))      # output tile m of F(m x m, 5x5); 0 = direct conv
+        winograd = 4 if conservative else int(knob("HVN_WINOGRAD"))      # output tile m of F(m x m, 5x5); 0 = direct conv
     wino_m = 4 if winograd is True else int(winograd)
     # per decoder stage override of the 5x5 output tile, e.g. HVN_WINOGRAD_STAGES="u3:6" (F(6x6,5x5) for u3.conva only, the rest as
     # HVN_WINOGRAD says): F(6x6,5x5) costs ~8x the fp32 error of F(4x4,5x5) (tests/test_gpu_trained_like.py), which stage carries it matters
     # Default since round 4: u3 (1024 -> 256 @62^2, the largest product) as F(6x6,5x5): 1.95e-4 on the trained-like checkpoint against
     # 1.70e-4 without and 1.95e-4 for direct convolutions; u2 (4.0e-4) and u1 (1.15e-3: it feeds the logits directly) keep F(4x4,5x5).
-    wino_stage = {kv.split(":")[0]: int(kv.split(":")[1]) for kv in os.environ.get("HVN_WINOGRAD_STAGES", "u3:6").split(",") if ":" in kv}
+    wino_stage = {kv.split(":")[0]: int(kv.split(":")[1]) for kv in knob("HVN_WINOGRAD_STAGES").split(",") if ":" in kv}
     if not winograd or conservative:
         wino_stage = {}
-    wino3 = int(os.environ.get("HVN_WINOGRAD3", "128"))      # minimum channel count for the Winograd form of the encoder's 3x3 convs; 0 = off
-    wino3_m = int(os.environ.get("HVN_WINOGRAD3_M", "6"))     # its output tile: F(6x6,3x3) (default since round 4: same logit error, 1.78 instead of 2.25 multiplies per output) or F(4x4,3x3)
+    wino3 = int(knob("HVN_WINOGRAD3"))      # minimum channel count for the Winograd form of the encoder's 3x3 convs; 0 = off
+    wino3_m = int(knob("HVN_WINOGRAD3_M"))     # its output tile: F(6x6,3x3) (default since round 4: same logit error, 1.78 instead of 2.25 multiplies per output) or F(4x4,3x3)
     if conservative:
         wino3_m = 4
     P = Plan(mode, nr_types)
@@ -574,10 +573,10 @@ def build_plan(sd, mode="original", nr_types=None, with_predmap=True, winograd=N
         P.pred_map = pm
         P.add(Op(OP_PREDMAP, "infer_step.epilogue", y=View(pm), extra={"branches": list(arch.branch_names(nr_types))}))
     if x3 is None:
-        x3 = 9 if conservative else int(os.environ.get("HVN_X3", "6"))       # default since round 4: six partial products (measured: the fp32-MFMA path's own error band)
+        x3 = 9 if conservative else int(knob("HVN_X3"))       # default since round 4: six partial products (measured: the fp32-MFMA path's own error band)
     if x3:
         # (which pipe a layer's products run on is a rule by LAYER, never by what the chain pass did: HVN_CHAIN=0 runs the same bits unchained)
-        P.mark_x3(int(x3), d1=os.environ.get("HVN_X3_D1", "1") != "0", chain=os.environ.get("HVN_X3_CHAIN", "d0"))
+        P.mark_x3(int(x3), d1=knob("HVN_X3_D1") != "0", chain=knob("HVN_X3_CHAIN"))
     if isinstance(chain, str) and chain.startswith("bf16"):
         # the bf16 path (csrc/hvn_conv_chain_bf16.hip): seams whose conv3 reduces over 64 or 128 channels in whole 64-channel slabs --
         # d0's three and d1's plain-residual ones; chain = "bf16:d0" | "bf16:d0d1" names the blocks whose seams are chained
@@ -589,8 +588,8 @@ def build_plan(sd, mode="original", nr_types=None, with_predmap=True, winograd=N
             return a.name.split(".")[0] in blocks and a.x.c % 64 == 0 and (x2 is None or x2.c % 64 == 0) and ka in (64, 128) and a.cout % 256 == 0
         P.fuse_chains(128, accept=bf16_seam)
     elif chain:
-        P.fuse_chains(int(os.environ.get("HVN_CHAIN_MAXN2", "128")))
-    if os.environ.get("HVN_FUSE_UPADD", "0") != "0":
+        P.fuse_chains(int(knob("HVN_CHAIN_MAXN2")))
+    if knob("HVN_FUSE_UPADD") != "0":
         # measured (profiles/r03_upadd_fusion_ab.txt): parity-green and bit-equal, one launch and one tensor less per decoder stage, but
         # SLOWER -- the transform (64 register-resident tile values per thread) pays more for the second, quarter-rate address stream
         # than the up-sampled tensor's write + re-read cost: 61.15 vs 60.54 ms per step.  Off by default.

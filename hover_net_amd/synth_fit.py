@@ -72,9 +72,8 @@ def fit(mode="fast", nr_types=None, steps=240, batch=8, lr=1e-3, seed=0, log=Non
     local=True: this process fits ALONE even when torch.distributed is initialised (bench.py --gpus N: every rank makes its own
     checkpoint; without this `train_step` would all-reduce the gradients of the N fits, i.e. run data-parallel training inside a
     benchmark's set-up)."""
-    import os
 
-    from . import net_desc, run_desc, targets
+    from . import net_desc, run_desc, targets, train_engine
     from .optim import FusedAdam
     from .synth import synth_state_dict
 
@@ -103,10 +102,10 @@ def fit(mode="fast", nr_types=None, steps=240, batch=8, lr=1e-3, seed=0, log=Non
         tp = torch.from_numpy(np.ascontiguousarray(painted[2][:, o:o + out, o:o + out]).astype(np.int64)).cuda()
     rng = np.random.default_rng(seed + 2)
     curve = []
-    saved_dist, saved_share = run_desc._dist, os.environ.get("HVN_TILE_SHARE")
+    saved_dist = run_desc._dist
     if local:
+        net._train_engine = train_engine.TrainEngine(net, batch, share_shapes=False)    # no launch-shape broadcast at engine build
         run_desc._dist = lambda: None                  # no gradient all-reduce
-        os.environ["HVN_TILE_SHARE"] = "0"             # no launch-shape broadcast at engine build
     try:
         for it in range(steps):
             idx = torch.from_numpy(rng.choice(pool_img.shape[0], batch, replace=False)).cuda()
@@ -119,9 +118,5 @@ def fit(mode="fast", nr_types=None, steps=240, batch=8, lr=1e-3, seed=0, log=Non
                 log("step %4d loss %.4f" % (it, curve[-1]))
     finally:
         run_desc._dist = saved_dist
-        if saved_share is None:
-            os.environ.pop("HVN_TILE_SHARE", None)
-        else:
-            os.environ["HVN_TILE_SHARE"] = saved_share
     net.eval()
     return net, curve

@@ -13,7 +13,6 @@ Memory (sized for 288 GB, nothing is recomputed):
 torch is used for allocation, streams and `torch.distributed` (RCCL) only.  There is no CPU fallback.
 """
 import ctypes
-import os
 
 import torch
 
@@ -22,6 +21,7 @@ from . import lib as L
 from . import train_plan as TP
 from . import tune as T
 from . import winograd as WG
+from .knobs import knob
 from .plan import OP_CONV, OP_CONV0, OP_HEAD, OP_UPADD, OP_WINO_IN, OP_WINO_OUT, _tile_n
 
 T_NET, T_PACK_W, T_BN_FWD, T_BN_BWD, T_WGRAD, T_CONV0_WGRAD, T_UPADD_BWD, T_HEAD_BWD, T_WINO_DY, T_WINO_DW = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
@@ -74,7 +74,7 @@ class TrainEngine:
         if deterministic is None:
             deterministic = getattr(net, "train_deterministic", None)
         if deterministic is None:
-            deterministic = os.environ.get("HVN_TRAIN_DETERMINISTIC", "1") != "0"
+            deterministic = knob("HVN_TRAIN_DETERMINISTIC") != "0"
         self.deterministic = bool(deterministic)
         self.n = int(batch)
         self.device = torch.device(device) if device is not None else next(net.parameters()).device
@@ -89,7 +89,7 @@ class TrainEngine:
         # 5x5 stride-1 convs (decoder conva, 51 % of the forward FLOPs) run as Winograd F(4x4,5x5) like the inference
         # plan (plan.py:conv_winograd) in all three passes: forward, data gradient, and the weight gradient in the
         # transform domain; HVN_TRAIN_WINOGRAD=0 keeps them direct
-        self.use_wino = os.environ.get("HVN_TRAIN_WINOGRAD", "1") != "0"
+        self.use_wino = knob("HVN_TRAIN_WINOGRAD") != "0"
         self._du_off, du_total = {}, 0
         for key, c in P.convs.items():
             if self._is_wino(c) and c["train"]:
@@ -99,7 +99,7 @@ class TrainEngine:
         # accumulates: the slab, the transform-domain gradients and the arena's first `gzero_elems` -- the rest of the arena are buffers
         # whose first writer of the step overwrites them completely (train_plan._first_writers; round 6: 73 % of the arena in phase 1).
         # HVN_TRAIN_FIRST_STORE=0: every backward launch accumulates and everything is cleared (rounds 3-5).
-        self.first_store = os.environ.get("HVN_TRAIN_FIRST_STORE", "1") != "0"
+        self.first_store = knob("HVN_TRAIN_FIRST_STORE") != "0"
         self._gtotal = self._slab_elems + garena_elems + du_total
         self.gmem = torch.zeros(self._gtotal, dtype=torch.float32, device=dev)
         self.gslab = self.gmem[:self._slab_elems]
@@ -125,7 +125,7 @@ class TrainEngine:
         # buffers (the skips' and conv_bot's output gradients, `upadd_bwd`) is deferred to after the join and runs in the single-stream
         # order: same sums in the same order, same bits (tests/test_gpu_train.py).  HVN_TRAIN_BRANCH_STREAMS=0: one stream.
         self.branches = arch.branch_names(net.nr_types)
-        self.branch_streams = os.environ.get("HVN_TRAIN_BRANCH_STREAMS", "1") != "0"
+        self.branch_streams = knob("HVN_TRAIN_BRANCH_STREAMS") != "0"
         self._nsets = len(self.branches) if self.branch_streams else 1
         self._side = _shared_streams(dev, "side", self._nsets - 1)
         # Weight-gradient streams (round 6): a conv's weight gradient and its data gradient are independent, and nothing in the backward
@@ -136,7 +136,7 @@ class TrainEngine:
         # layer trains) 42.8 -> 39.2 ms, phase 0 (batch 16, frozen encoder: launches that fill the chip alone) 61.3 -> 62.9 ms -- so the
         # default `HVN_TRAIN_WGRAD_STREAM=auto` times the backward list both ways once at engine build (`_choose_wgrad_stream`; the bits
         # do not depend on the answer); 1 / 0 force it on / in list order on the section's stream.
-        self._wgrad_mode = os.environ.get("HVN_TRAIN_WGRAD_STREAM", "auto")
+        self._wgrad_mode = knob("HVN_TRAIN_WGRAD_STREAM")
         self.wgrad_stream = self._wgrad_mode != "0"
         self._wside = _shared_streams(dev, "wgrad", self._nsets) if self.wgrad_stream else []
         self.bn_ws = [torch.zeros(256 * 2 * cmax, dtype=torch.float64, device=dev) for _ in range(self._nsets)]     # HVN_BN_MAX_PARTS partial sums
@@ -259,9 +259,9 @@ class TrainEngine:
         # bf16x3 (csrc/hvn_conv_x3.hip): the forward / data-gradient convs form their products on the bf16 matrix pipe from exact
         # three-way bf16 splits; the planes of the step's weight packings are made on the device right after the packing
         # (HVN_TRAIN_X3 = 6 (default) | 9 partial products per product, 0 = every conv on the fp32 pipe)
-        self.x3_terms = int(os.environ.get("HVN_TRAIN_X3", "6"))
+        self.x3_terms = int(knob("HVN_TRAIN_X3"))
         # round 5: the weight gradients too (csrc/hvn_wgrad_x3.hip: both operands split on the fly; HVN_TRAIN_WGRAD_X3=0 keeps the fp32 pipe)
-        wg = os.environ.get("HVN_TRAIN_WGRAD_X3", "1")            # 1: as the forward convs | 6 | 9 | 0: fp32 pipe
+        wg = knob("HVN_TRAIN_WGRAD_X3")            # 1: as the forward convs | 6 | 9 | 0: fp32 pipe
         self.wgrad_x3 = 0 if (wg == "0" or not self.x3_terms) else (int(wg) if wg in ("6", "9") else self.x3_terms)
         self.packs_x3 = torch.zeros(3 * total, dtype=torch.int16, device=self.device) if self.x3_terms else None
 
@@ -274,7 +274,7 @@ class TrainEngine:
         import numpy as np
 
         ops, table, blocks = [], [], [0]
-        multi = os.environ.get("HVN_TRAIN_PACK_MULTI", "1") != "0"
+        multi = knob("HVN_TRAIN_PACK_MULTI") != "0"
         for (key, mode), (off, lead) in self._pack_off.items():
             if mode == 2:
                 cout, cin_g, groups, kh, kw = 64, 3, 1, 7, 7

@@ -6,30 +6,12 @@ time, once per process and launch shape: `candidates` says which forms a bound l
 `choose` applies the one pick rule and keeps the answer in `CACHE`.  The engines own the rest: which ops they tune, at which
 batch, and how one launch is issued."""
 import math
-import os
 
 import torch
 
 from . import lib as L
+from .knobs import KNOBS, knob  # noqa: F401  (the table and its reader, importable from here as before)
 from .plan import OP_CHAIN, OP_CONV, _tile_n
-
-# The selection knobs (environment variables): default and meaning.  Read through `knob` at call time, never at import.
-KNOBS = {
-    "HVN_TILE_SELECT": ("auto", "auto: forms picked by time at engine build | model: inference CONV tiles by pick_tile_n's rounds model, nothing timed | 0: the plan's static tiles"),
-    "HVN_TUNE_REPS": ("", "timings per candidate after the warm-up launch (default 3; 2 for the weight-gradient stream pass)"),
-    "HVN_TUNE_SUB": ("1", "0: a split inference engine times its encoder launches at the full batch instead of the sub-batch"),
-    "HVN_FORCE_TILE_N": ("", "64 | 128: that column tile for every re-tileable fp32 inference CONV, nothing timed"),
-    "HVN_WG_SLOTS_64": ("768", "rounds model: resident 128x64 workgroups on the chip"),
-    "HVN_NARROW_COST": ("0.45", "rounds model: time of a round of 128x64 tiles relative to a round of 128x128 tiles"),
-    "HVN_X3G": ("1", "LDS-DMA forms of the bf16x3 CONV: 0 none | 896 | 640 that form only | 1 both"),
-    "HVN_X3G_FORCE": ("", "896 | 640: that bf16x3 LDS-DMA form wherever it is a candidate, nothing timed"),
-    "HVN_BF16G": ("1", "0: no LDS-DMA forms of the bf16 CONV"),
-    "HVN_BF16G_FORCE": ("", "896 | 640: that bf16 LDS-DMA form wherever it is a candidate, nothing timed"),
-    "HVN_CHAIN_X3R": ("1", "register-resident form of the bf16x3 CHAIN: 0 never | force wherever it is a candidate | 1 by time"),
-    "HVN_STREAM_SELECT": ("1", "0: the inference launch schedule keeps rotation 0 of the stream pool"),
-    "HVN_TILE_SHARE": ("1", "0: data-parallel ranks keep their own measured launch shapes (no broadcast from rank 0)"),
-    "HVN_TILE_FILE": ("", "path of a JSON list of per-op tile_n codes an fp32 inference engine binds instead of timing"),
-}
 
 MARGIN = 0.985              # a candidate replaces the baseline only when it is faster by more than 1.5 %
 X3G_256, X3G_128 = 128 + 0x300, 128 + 0x200     # hvn_op.tile_n of the LDS-DMA forms of the bf16x3 / bf16 convolution (include/hvn.h)
@@ -42,10 +24,6 @@ WG_SLOTS = 512              # resident 128x128 conv workgroups: 2 per CU (VGPRs)
 # (device, family, ...launch shape..., candidates) -> (choice, ms of the baseline, ms of the fastest other candidate, {candidate: ms}),
 # one per process; family: infer-conv | infer-chain | infer-chain-x3 | infer-bf16 | train-conv | train-wgrad | streams
 CACHE = {}
-
-
-def knob(name):
-    return os.environ.get(name, KNOBS[name][0])
 
 
 def tile_select():

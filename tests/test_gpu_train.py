@@ -747,7 +747,7 @@ def conv0_problem(n, H, W, pad, seed=4):
     t.x.base, t.x.sn, t.x.sy, t.x.sx, t.x.h, t.x.w, t.x.c, t.x.sc = imgc.data_ptr(), H * W * 3, W * 3, 3, H, W, 3, 1
     t.dy = view_of(dzc)
     t.p[0] = dw.data_ptr()
-    cap = 1024 if "HVN_CONV0_WGRAD_VALU" in os.environ else 512          # csrc/hvn_train.hip:conv0_wgrad_wgs (the VALU form keeps more workgroups)
+    cap = 512          # csrc/hvn_train.hip:conv0_wgrad_wgs
     return t, (imgc, dzc), dw, img, dz, min(-(-ho // 16) * -(-wo // 16) * n, cap)
 
 

@@ -50,11 +50,10 @@ case $T in
     Q="--steps 10 --no-cpu-baseline --no-variants --no-traffic --checkpoint random"
     for cfg in "HVN_X3_D1=0" "HVN_X3_D1=1"; do ENVV=($cfg); bench d1_$(echo $cfg | tr -d ' =A-Z_') $Q; done
     ;;
-  bf16)       # the bf16 conv loop A/B (HVN_BF16_LOOP=0: round 2's loop) + launch schedule, cfg 3, one box; then its parity tests
+  bf16)       # the bf16 launch schedule A/B, cfg 3, one box; then its parity tests
     Q="--dtype bf16 --mode fast --nr-types 6 --batch 64 --steps 10 --warmup 2 --no-cpu-baseline --no-variants --no-traffic --checkpoint random"
-    for cfg in "HVN_BF16_LOOP=0" "HVN_BF16_LOOP=1" "HVN_BF16_LOOP=1 HVN_SPLIT=2 HVN_LANES=2"; do ENVV=($cfg); bench bf16_$(echo $cfg | tr -d ' =A-Z_') $Q; done
-    grep -E "^== bench|^value|^roofline" $O > gpurun_out/${R}_bf16_loop_ab.txt
-    for x in 0 1; do HVN_BF16_LOOP=$x timeout 200 python tools/layer_ms.py --dtype bf16 --mode fast --nr-types 6 --batch 64 2>/dev/null | grep -v amdgpu.ids > gpurun_out/${R}_layers_cfg3_bf16_loop$x.txt; done
+    for cfg in "HVN_SPLIT=1 HVN_LANES=0" "HVN_SPLIT=2 HVN_LANES=2"; do ENVV=($cfg); bench bf16_$(echo $cfg | tr -d ' =A-Z_') $Q; done
+    grep -E "^== bench|^value|^roofline" $O > $D/${R}_bf16_sched_ab.txt
     timeout 900 python -m pytest tests/test_gpu_bf16.py tests/test_gpu_bench_shapes.py -x -q 2>&1 | tail -5 >> $O
     ;;
   train)      # training step: fp32 pipe vs bf16x3 forward / data-gradient products on one box, then the training tests
@@ -66,13 +65,6 @@ for l in open("gpurun_out/r04_train_bench.jsonl"):
     print(tag, "phase", d.get("phase"), "batch", d.get("batch"), "ms/step %.2f" % d.get("ms_per_step", 0), {k: round(v, 2) for k, v in d.items() if k.endswith("_ms")})
 PY
     timeout 1500 python -m pytest tests/test_gpu_train.py -x -q -s 2>&1 | grep -E "passed|failed|Error|assert|bf16x3|direct vs" | tail -14 >> $O
-    ;;
-  dense)      # dense-unit grouped conv: form 2 (whole patch per tile) vs form 3 (rolling patch, runs of tiles), one box; parity tests first
-    timeout 900 python -m pytest tests/test_gpu_conv.py tests/test_gpu_net.py -x -q 2>&1 | tail -3 >> $O
-    Q="--steps 10 --no-cpu-baseline --no-variants --no-traffic --checkpoint random"
-    for cfg in "HVN_DENSE_FORM=2" "HVN_DENSE_RUN=4" "HVN_DENSE_RUN=3" "HVN_DENSE_RUN=5" "HVN_DENSE_RUN=8"; do ENVV=($cfg); bench dense_$(echo $cfg | tr -d ' =A-Z_') $Q; done
-    grep -E "^== bench|^value|^roofline" $O > gpurun_out/${R}_dense_ab.txt
-    for cfg in "HVN_DENSE_FORM=2" "HVN_DENSE_RUN=4"; do env $cfg timeout 200 python tools/layer_ms.py 2>/dev/null | grep "dense.units.*conv2" | head -12 > gpurun_out/${R}_dense_layers_$(echo $cfg | tr -d ' =A-Z_').txt; done
     ;;
   trainprof)  # rocprofv3 kernel summary of the training step, per phase
     for ph in 0 1; do
@@ -115,16 +107,6 @@ PY
       grep -E "\+" $f | head -6 >> $O
     done
     for c in 0 1; do ENVV=(HVN_CHAIN_X3R=$c); bench x3r_$c $Q; done
-    ;;
-  winoxcd)    # round 5: XCD-contiguous tile ranges in the Winograd input transform (csrc/hvn_net_ops.hip); A/B against the "noxcd" build
-    timeout 600 python -m pytest tests/test_gpu_net.py tests/test_gpu_conv.py -q --tb=short -x -k "not slow" 2>&1 | tail -5 >> $O
-    for v in noxcd ""; do
-      f=gpurun_out/${R}_layers_winoxcd_${v:-default}.txt
-      HVN_LIB_VARIANT=$v timeout 300 python tools/layer_ms.py > $f 2>&1; echo "== HVN_LIB_VARIANT=$v: $(tail -1 $f)" >> $O
-      grep "wino_in" $f | awk '{s+=$(NF)} END {print "   wino_in total us:", s}' >> $O
-    done
-    Q="--steps 10 --no-cpu-baseline --no-variants --no-traffic --checkpoint random"
-    for v in noxcd ""; do ENVV=(HVN_LIB_VARIANT=$v); bench winoxcd_${v:-default} $Q; done
     ;;
   wgradx3)    # round 5: weight gradients on the bf16 pipe (csrc/hvn_wgrad_x3.hip) + the LDS-DMA conv forms in the training step: kernel tests,
               # then the training step with / without them on one box
