@@ -104,8 +104,8 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         a.y = (float *)op->y.base;
         a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx;
         a.N = batch; a.Ho = op->y.h; a.Wo = op->y.w; a.pad = op->pad_t; a.relu = op->relu; a.out_bf16 = op->act_dtype == 1;
-        if (op->kh != 7 || op->kw != 7 || op->x.c != 3 || op->y.c != 64 || !op->w || !op->bias)
-            return fail(HVN_E_ARG, "conv0: expects 7x7x3->64 with bias%s", "");
+        if (op->kh != 7 || op->kw != 7 || op->x.c != 3 || op->y.c != 64 || !op->w || !op->bias || !op->x.base || !op->y.base)
+            return fail(HVN_E_ARG, "conv0: expects 7x7x3->64 with bias, a non-null image and output%s", "");
         if (!aligned16(a.y) || (a.ysx & 3) || (a.ysy & 3) || (a.ysn & 3)) return fail(HVN_E_ARG, "conv0: output view not 16-byte aligned%s", "");
         return hvn_launch_conv0(a, s);
     }
@@ -292,6 +292,8 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         if (!a.lo || !a.skip || !a.y) return fail(HVN_E_ARG, "upadd: null pointer%s", "");
         if (op->x.h * 2 != a.H || op->x.w * 2 != a.W || op->res.h != a.H || op->res.w != a.W || op->x.c != a.C || op->res.c != a.C)
             return fail(HVN_E_ARG, "upadd: shape mismatch%s", "");
+        if (a.C <= 0 || a.C % (a.bf16 ? 8 : 4))     // one thread moves 16 bytes: the launcher would refuse without a text of its own
+            return fail(HVN_E_ARG, "upadd: channels must be a multiple of 4 (fp32) or 8 (bf16) (got %s%ld)", "", a.C);
         if (!aligned16(a.lo) || !aligned16(a.skip) || !aligned16(a.y) || ((a.lsx | a.lsy | a.lsn | a.ssx | a.ssy | a.ssn | a.ysx | a.ysy | a.ysn) & 3))
             return fail(HVN_E_ARG, "upadd: views not 16-byte aligned%s", "");
         return hvn_launch_upadd(a, s);
