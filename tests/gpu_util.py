@@ -80,6 +80,66 @@ def run_conv_case(n, xbuf_shape, xview, ybuf_shape, yview, wt, *, stride=1, pad=
     return got, want
 
 
+def conv_bits_plan(*, n, x, xbuf, xview, ybuf, yview, wt, stride=1, pad=(0, 0), groups=1, bias=None, relu=0, pre=None, res=None, inplace_res=False,
+                   post=None, x2=None, wt2=None, stride2=1):
+    """The one-CONV plan of a case given as explicit arrays (tests/bf16_model.py's `spec`): weights with bn=None, bias=..., so the fold
+    preserves every value.  -> (plan, op, views = dict(x, y, res | None, x2 | None)).  Host only."""
+    P = MiniPlan()
+    xv = PL.View(P.buf("x", *xbuf), *xview)
+    yv = PL.View(P.buf("y", *ybuf), *yview)
+    assert tuple(x.shape) == (n, xv.h, xv.w, xv.c)
+    kw, views = {}, dict(x=xv, y=yv, res=None, x2=None)
+    if res is not None:
+        views["res"] = kw["res"] = yv if inplace_res else PL.View(P.buf("r", *ybuf), *yview)
+    if x2 is not None:
+        views["x2"] = PL.View(P.buf("x2", *x2.shape[1:]))
+        kw.update(x2=views["x2"], wt2=np.asarray(wt2, np.float64), stride2=stride2)
+    op = P.conv("case", xv, yv, np.asarray(wt, np.float64), stride=stride, pad=pad, groups=groups, bn=None, bias=bias, relu=relu, pre=pre,
+                post=post, **kw)
+    P.pack()
+    return P, op, views
+
+
+def run_conv_bits(force_tile, **spec):
+    """One bf16 CONV launch on exactly the values given: x, res [n, h, w, c] (the views' contents) and x2 (its whole buffer; NaN where
+    nothing may be read) float32 arrays of bf16-exact values, weights [cout, cin_g, k, k] bf16-exact, bias / pre / post fp32.  The
+    rest of the arena -- the buffers around the views, the output, the alignment gaps -- holds the NaN pattern 0x7FC0.
+    -> (the output view's raw bf16 bits, uint16 [n, ho, wo, cout]; the number of arena elements outside the output view whose bits
+    changed -- a write outside the view, or an unwritten NaN that is no longer the fill pattern)."""
+    from hover_net_amd.engine import Engine
+    from net_ops_ref import bf16_bits
+
+    P, op, views = conv_bits_plan(**spec)
+    n = spec["n"]
+    eng = Engine(P, max_batch=n, n_split=1, n_lanes=0, dtype="bf16")
+    eng.ops[0].tile_n = force_tile
+    eng.arena.fill_(0x7FC0)
+
+    def put(view, a):
+        bits = bf16_bits(a).view(np.int16).reshape(a.shape)
+        eng.buffer(view, n).copy_(torch.from_numpy(bits).view(torch.bfloat16))
+
+    put(views["x"], spec["x"])
+    if views["res"] is not None:
+        put(views["res"], spec["res"])
+    if views["x2"] is not None:
+        put(views["x2"], spec["x2"])
+    before = eng.arena.cpu().numpy().view(np.uint16).copy()
+    eng.run_raw(n)
+    torch.cuda.synchronize()
+    assert eng.ops[0].act_dtype == 1 and eng.ops[0].tile_n == force_tile
+    after = eng.arena.cpu().numpy().view(np.uint16)
+
+    def window(arena):
+        v, b = views["y"], views["y"].buf
+        return arena[:, b.offset:b.offset + b.size].reshape(n, b.h, b.w, b.c)[:, v.y0:v.y0 + v.h, v.x0:v.x0 + v.w, v.c0:v.c0 + v.c]
+
+    got = window(after).copy()
+    rest = after.copy()
+    window(rest)[...] = window(before)
+    return got, int((rest != before).sum())
+
+
 def run_dot_conv(n, x, wt, *, stride=1, pad=(0, 0), x3=0, force_tile=None, x2=None, wt2=None, stride2=1, winograd=0):
     """One BARE convolution -- no bn, bias, relu, prologue or residual: every output element is a dot product -- on exactly the values
     given (tests/test_gpu_x3_budget.py).  x [n, h, w, cin] (and x2 [n, h2, w2, cin2], the fused shortcut's second K source) go into the
