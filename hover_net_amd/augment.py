@@ -89,10 +89,8 @@ def augment_shape(img_dev, ann_dev, prm, out_hw):
     prm_dev = _upload(prm, img_dev.device)
     oimg = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=img_dev.device)
     oann = torch.empty((n, oh, ow, c), dtype=torch.int32, device=img_dev.device)
-    rc = L.lib().hvn_augment_shape(img_dev.data_ptr(), ann_dev.data_ptr(), p, h, w, c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
-                                   L.stream_ptr(img_dev.device))
-    if rc:
-        raise L.HvnError("hvn_augment_shape failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
+    L.call("hvn_augment_shape", img_dev.data_ptr(), ann_dev.data_ptr(), p, h, w, c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
+           L.stream_ptr(img_dev.device))
     return oimg, oann
 
 
@@ -109,10 +107,8 @@ def augment_input(img_dev, prm, noise=None):
         assert noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n, h, w, 3) and noise.is_contiguous()
     prm_dev = _upload(prm, img_dev.device)
     out = torch.empty_like(img_dev)
-    rc = L.lib().hvn_augment_input(img_dev.data_ptr(), prm_dev.data_ptr(), noise.data_ptr() if noise is not None else None, n, h, w, out.data_ptr(),
-                                   L.stream_ptr(img_dev.device))
-    if rc:
-        raise L.HvnError("hvn_augment_input failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
+    L.call("hvn_augment_input", img_dev.data_ptr(), prm_dev.data_ptr(), noise.data_ptr() if noise is not None else None, n, h, w, out.data_ptr(),
+           L.stream_ptr(img_dev.device))
     return out
 
 

@@ -1,20 +1,41 @@
 // hvn_api.hip -- the C ABI (include/hvn.h) over the kernels: descriptor validation,
-// plan execution, error text, optional per-launch timing of the conv kernel.
+// plan execution, the error text of the whole library (hvn_error.h), optional per-launch timing of the conv kernel.
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
-#include "../../include/hvn.h"
 #include "hvn_kernels.h"
 
-static thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";   // the library's one error text (hvn_error.h)
 
-static int fail(int code, const char *fmt, const char *a = "", long b = 0)
+int hvn_fail(int code, const char *fmt, ...)
 {
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
     return code;
+}
+
+int hvn_launch_status(int rc, const char *what)
+{
+    return rc ? hvn_fail(rc, "%s: %s", what, rc == HVN_E_LAUNCH ? "launch failed" : "the launcher refused these arguments") : HVN_OK;
+}
+
+int hvn_fail_in_op(int code, const char *plan, int i)
+{
+    char text[sizeof(g_err)];
+    snprintf(text, sizeof(text), "%s", g_err);
+    return hvn_fail(code, "%s op %d: %s", plan, i, text);
+}
+
+int hvn_launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? HVN_OK : hvn_fail(HVN_E_LAUNCH, "%s: launch failed: %s", what, hipGetErrorString(e));
 }
 
 extern "C" {
@@ -88,69 +109,70 @@ int hvn_profile_conv_ms_list(double *out, int cap)
     return n;
 }
 
-// ---- one op ---------------------------------------------------------------------------------
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+}  // extern "C"
 
-static int run_one(const hvn_op *op, int batch, hipStream_t s)
+// ---- one op (also a HVN_T_NET op of a training plan: hvn_train_api.hip) ---------------------
+static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// base and strides of a view into a launcher's argument struct
+template <class T> static inline void set_view(const hvn_view &v, T *&p, long &sn, long &sy, long &sx) { p = (T *)v.base; sn = v.sn; sy = v.sy; sx = v.sx; }
+// every stride a multiple of mask + 1 elements (3: 16 bytes of fp32, 7: 16 bytes of bf16)
+static inline bool strides_ok(const hvn_view &v, long mask) { return ((v.sn | v.sy | v.sx) & mask) == 0; }
+
+int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
 {
     switch (op->kind) {
     case HVN_OP_CONV0: {
         Conv0Args a;
-        a.img = op->x.base;
-        a.isn = op->x.sn; a.isy = op->x.sy; a.isx = op->x.sx; a.isc = op->x.sc ? op->x.sc : 1;
+        set_view(op->x, a.img, a.isn, a.isy, a.isx);
+        a.isc = op->x.sc ? op->x.sc : 1;
         a.is_f32 = op->x_dtype;
         a.H = op->x.h; a.W = op->x.w;
         a.w = op->w; a.bias = op->bias;
-        a.y = (float *)op->y.base;
-        a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx;
+        set_view(op->y, a.y, a.ysn, a.ysy, a.ysx);
         a.N = batch; a.Ho = op->y.h; a.Wo = op->y.w; a.pad = op->pad_t; a.relu = op->relu; a.out_bf16 = op->act_dtype == 1;
         if (op->kh != 7 || op->kw != 7 || op->x.c != 3 || op->y.c != 64 || !op->w || !op->bias || !op->x.base || !op->y.base)
-            return fail(HVN_E_ARG, "conv0: expects 7x7x3->64 with bias, a non-null image and output%s", "");
-        if (!aligned16(a.y) || (a.ysx & 3) || (a.ysy & 3) || (a.ysn & 3)) return fail(HVN_E_ARG, "conv0: output view not 16-byte aligned%s", "");
-        return hvn_launch_conv0(a, s);
+            return hvn_fail(HVN_E_ARG, "conv0: expects 7x7x3->64 with bias, a non-null image and output");
+        if (!aligned16(a.y) || !strides_ok(op->y, 3)) return hvn_fail(HVN_E_ARG, "conv0: output view not 16-byte aligned");
+        return hvn_launch_status(hvn_launch_conv0(a, s), "conv0");
     }
     case HVN_OP_CONV: {
         ConvArgs a;
         memset(&a, 0, sizeof(a));
-        a.x = (const float *)op->x.base;
-        a.xsn = op->x.sn; a.xsy = op->x.sy; a.xsx = op->x.sx;
+        set_view(op->x, a.x, a.xsn, a.xsy, a.xsx);
         a.H = op->x.h; a.W = op->x.w; a.Cin = op->x.c;
         a.w = op->w; a.bias = op->bias;
         a.pre_s = op->pre_scale; a.pre_b = op->pre_shift;
         a.post_s = op->post_scale; a.post_b = op->post_shift;
-        a.res = (const float *)op->res.base;
-        a.rsn = op->res.sn; a.rsy = op->res.sy; a.rsx = op->res.sx;
-        a.y = (float *)op->y.base;
-        a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx;
+        set_view(op->res, a.res, a.rsn, a.rsy, a.rsx);
+        set_view(op->y, a.y, a.ysn, a.ysy, a.ysx);
         a.N = batch; a.Ho = op->y.h; a.Wo = op->y.w; a.Cout = op->cout;
         a.KH = op->kh; a.KW = op->kw; a.stride = op->stride; a.pad_t = op->pad_t; a.pad_l = op->pad_l;
         a.relu = op->relu;
         a.groups = op->groups > 1 ? op->groups : 1;
-        a.x2 = (const float *)op->x2.base;
-        a.x2sn = op->x2.sn; a.x2sy = op->x2.sy; a.x2sx = op->x2.sx;
+        set_view(op->x2, a.x2, a.x2sn, a.x2sy, a.x2sx);
         a.Cin2 = a.x2 ? op->x2.c : 0;
         a.stride2 = op->_rsv > 0 ? op->_rsv : 1;
-        if (a.x2 && (op->kh != 1 || op->kw != 1 || a.stride != 1 || a.Cin2 % 32 || !aligned16(a.x2) || ((a.x2sn | a.x2sy | a.x2sx) & 3) ||
+        if (a.x2 && (op->kh != 1 || op->kw != 1 || a.stride != 1 || a.Cin2 % 32 || !aligned16(a.x2) || !strides_ok(op->x2, 3) ||
                      a.pre_s || (long)(a.Ho - 1) * a.stride2 >= op->x2.h || (long)(a.Wo - 1) * a.stride2 >= op->x2.w))
-            return fail(HVN_E_ARG, "conv: second input needs a 1x1 stride-1 op without prologue and a view that covers the output grid%s", "");
+            return hvn_fail(HVN_E_ARG, "conv: second input needs a 1x1 stride-1 op without prologue and a view that covers the output grid");
         a.M = (long)batch * a.Ho * a.Wo;
-        if (!a.x || !a.w || !a.y) return fail(HVN_E_ARG, "conv: null pointer%s", "");
-        if (a.Cin % 32) return fail(HVN_E_ARG, "conv: input channels must be a multiple of 32 (got %s%ld)", "", a.Cin);
-        if (!aligned16(a.x) || !aligned16(a.w) || (a.xsx & 3) || (a.xsy & 3) || (a.xsn & 3))
-            return fail(HVN_E_ARG, "conv: input view / weights not 16-byte aligned%s", "");
+        if (!a.x || !a.w || !a.y) return hvn_fail(HVN_E_ARG, "conv: null pointer");
+        if (a.Cin % 32) return hvn_fail(HVN_E_ARG, "conv: input channels must be a multiple of 32 (got %d)", a.Cin);
+        if (!aligned16(a.x) || !aligned16(a.w) || !strides_ok(op->x, 3))
+            return hvn_fail(HVN_E_ARG, "conv: input view / weights not 16-byte aligned");
         if ((a.pre_s && !aligned16(a.pre_s)) || (a.pre_b && !aligned16(a.pre_b)) || (!a.pre_s != !a.pre_b))
-            return fail(HVN_E_ARG, "conv: prologue vectors must be 16-byte aligned and come in pairs%s", "");
-        if (!a.post_s != !a.post_b) return fail(HVN_E_ARG, "conv: epilogue affine must come in pairs%s", "");
-        if (op->y.c != op->cout) return fail(HVN_E_ARG, "conv: output view channels != cout%s", "");
+            return hvn_fail(HVN_E_ARG, "conv: prologue vectors must be 16-byte aligned and come in pairs");
+        if (!a.post_s != !a.post_b) return hvn_fail(HVN_E_ARG, "conv: epilogue affine must come in pairs");
+        if (op->y.c != op->cout) return hvn_fail(HVN_E_ARG, "conv: output view channels != cout");
         a.nbatch = op->nbatch > 1 ? op->nbatch : 1;
         a.xb = op->batch_stride[0]; a.wb = op->batch_stride[1]; a.yb = op->batch_stride[2];
-        if (a.nbatch > 1 && ((a.xb | a.wb | a.yb) & 3)) return fail(HVN_E_ARG, "conv: batch strides must keep 16-byte alignment%s", "");
+        if (a.nbatch > 1 && ((a.xb | a.wb | a.yb) & 3)) return hvn_fail(HVN_E_ARG, "conv: batch strides must keep 16-byte alignment");
         const bool bf16 = op->act_dtype == 1;
-        if (bf16 && (((a.xsx | a.xsy | a.xsn) & 7) || (a.x2 && ((a.x2sx | a.x2sy | a.x2sn) & 7)) || a.nbatch > 1))
-            return fail(HVN_E_ARG, "conv(bf16): input strides must be multiples of 8 elements; no batched launch%s", "");
+        if (bf16 && (!strides_ok(op->x, 7) || (a.x2 && !strides_ok(op->x2, 7)) || a.nbatch > 1))
+            return hvn_fail(HVN_E_ARG, "conv(bf16): input strides must be multiples of 8 elements; no batched launch");
         if (g_prof) prof_mark(s);
         const bool x3 = op->act_dtype == 2 || op->act_dtype == 3;
-        if (x3 && (a.groups > 1 || (a.nbatch > 1 && (a.wb & 7)))) return fail(HVN_E_ARG, "conv(bf16x3): no grouped convs; batch stride of the planes must keep 16-byte alignment%s", "");
+        if (x3 && (a.groups > 1 || (a.nbatch > 1 && (a.wb & 7)))) return hvn_fail(HVN_E_ARG, "conv(bf16x3): no grouped convs; batch stride of the planes must keep 16-byte alignment");
         int rc;
         if (bf16 && (op->tile_n == 896 || op->tile_n == 640))            // LDS-DMA form of the bf16 convolution (hvn_conv_bf16g.hip)
             rc = hvn_launch_conv_bf16g(a, op->tile_n == 896 ? 256 : 128, s);
@@ -161,103 +183,84 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         else
             rc = x3 ? hvn_launch_conv_x3(a, op->tile_n, op->act_dtype == 3 ? 6 : 9, s) : hvn_launch_conv(a, op->tile_n, s);
         if (g_prof) prof_mark(s);
-        if (rc) return fail(rc == -1 ? HVN_E_ARG : HVN_E_LAUNCH, "conv: launch failed (tile_n=%s%ld)", "", op->tile_n);
-        return 0;
+        if (rc) return hvn_fail(rc, "conv: launch failed (tile_n=%d)", op->tile_n);
+        return HVN_OK;
     }
     case HVN_OP_CHAIN: {
         ChainArgs a;
         memset(&a, 0, sizeof(a));
-        a.x = (const float *)op->x.base;
-        a.xsn = op->x.sn; a.xsy = op->x.sy; a.xsx = op->x.sx; a.K1 = op->x.c;
-        a.x2 = (const float *)op->x2.base;
-        a.x2sn = op->x2.sn; a.x2sy = op->x2.sy; a.x2sx = op->x2.sx;
+        set_view(op->x, a.x, a.xsn, a.xsy, a.xsx);
+        a.K1 = op->x.c;
+        set_view(op->x2, a.x2, a.x2sn, a.x2sy, a.x2sx);
         a.K1b = a.x2 ? op->x2.c : 0;
         a.stride2 = op->_rsv > 0 ? op->_rsv : 1;
         a.w1 = op->w;
-        a.res = (const float *)op->res.base;
-        a.rsn = op->res.sn; a.rsy = op->res.sy; a.rsx = op->res.sx;
-        a.y = (float *)op->y.base;
-        a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx; a.C = op->cout;
+        set_view(op->res, a.res, a.rsn, a.rsy, a.rsx);
+        set_view(op->y, a.y, a.ysn, a.ysy, a.ysx);
+        a.C = op->cout;
         a.post_s = op->post_scale; a.post_b = op->post_shift;
         a.pre_s = op->pre_scale; a.pre_b = op->pre_shift;
         a.w2 = op->w2; a.bias2 = op->bias2; a.relu2 = 1;
-        a.y2 = (float *)op->y2.base;
-        a.y2sn = op->y2.sn; a.y2sy = op->y2.sy; a.y2sx = op->y2.sx; a.N2 = op->cout2;
+        set_view(op->y2, a.y2, a.y2sn, a.y2sy, a.y2sx);
+        a.N2 = op->cout2;
         a.N = batch; a.Ho = op->y.h; a.Wo = op->y.w;
         a.M = (long)batch * a.Ho * a.Wo;
         a.bm = op->tile_n == 64 ? 64 : 128;      // CHAIN: tile_n = pixels per workgroup (0 / 128: 128)
         const bool cx3 = op->act_dtype == 2 || op->act_dtype == 3;       // products on the bf16 pipe from bf16x3 splits: w / w2 = plane packings
         const bool cbf = op->act_dtype == 1;                             // bf16 activations and weights (hvn_conv_chain_bf16.hip)
-        if (op->act_dtype != 0 && !cx3 && !cbf) return fail(HVN_E_ARG, "chain: act_dtype 0 (fp32), 1 (bf16) or 2 | 3 (fp32 with bf16x3 products)%s", "");
-        if (cbf) {
-            if (!a.x || !a.w1 || !a.y || !a.w2 || !a.y2) return fail(HVN_E_ARG, "chain: null pointer%s", "");
-            if (op->kh != 1 || op->kw != 1 || op->stride != 1 || op->pad_t || op->pad_l || op->relu || op->bias)
-                return fail(HVN_E_ARG, "chain: the first conv is a plain 1x1 (no bias / relu of its own)%s", "");
-            if (!hvn_chain_bf16_supported(a.K1, a.K1b, a.C, a.N2) || op->y.c != a.C || op->y2.c != a.N2)
-                return fail(HVN_E_ARG, "chain (bf16): needs input channels in slabs of 64 (64 or 128 in all), cout %% 256 == 0, cout2 in {64, 128} (cout2 = %s%ld)", "", a.N2);
-            if (op->x.h != a.Ho || op->x.w != a.Wo || op->y2.h != a.Ho || op->y2.w != a.Wo ||
-                (a.x2 && ((long)(a.Ho - 1) * a.stride2 >= op->x2.h || (long)(a.Wo - 1) * a.stride2 >= op->x2.w)))
-                return fail(HVN_E_ARG, "chain: views do not cover the output grid%s", "");
-            if (a.res && (a.rsn != a.ysn || a.rsy != a.ysy || a.rsx != a.ysx || op->res.c != a.C))
-                return fail(HVN_E_ARG, "chain: the residual view must have the output's strides%s", "");
-            if (!aligned16(a.x) || !aligned16(a.w1) || !aligned16(a.w2) || !aligned16(a.y) || !aligned16(a.y2) || (a.res && !aligned16(a.res)) ||
-                (a.x2 && !aligned16(a.x2)) || ((a.xsn | a.xsy | a.xsx | a.ysn | a.ysy | a.ysx | a.y2sn | a.y2sy | a.y2sx | a.x2sn | a.x2sy | a.x2sx) & 7))
-                return fail(HVN_E_ARG, "chain (bf16): views / weights not 16-byte aligned%s", "");
-            if ((!a.pre_s != !a.pre_b) || (!a.post_s != !a.post_b) || (a.pre_s && (!aligned16(a.pre_s) || !aligned16(a.pre_b))) ||
-                (a.post_s && (!aligned16(a.post_s) || !aligned16(a.post_b))) || (a.bias2 && !aligned16(a.bias2)))
-                return fail(HVN_E_ARG, "chain: per-channel vectors must be 16-byte aligned and come in pairs%s", "");
-            if (g_prof) prof_mark(s);
-            const int rcb = hvn_launch_conv_chain_bf16(a, s);
-            if (g_prof) prof_mark(s);
-            if (rcb) return fail(rcb == -1 ? HVN_E_ARG : HVN_E_LAUNCH, "chain (bf16): launch failed (cout2=%s%ld)", "", a.N2);
-            return 0;
-        }
-        if (!a.x || !a.w1 || !a.y || !a.w2 || !a.y2) return fail(HVN_E_ARG, "chain: null pointer%s", "");
+        if (op->act_dtype != 0 && !cx3 && !cbf) return hvn_fail(HVN_E_ARG, "chain: act_dtype 0 (fp32), 1 (bf16) or 2 | 3 (fp32 with bf16x3 products)");
+        // the bf16 form differs from the fp32 / bf16x3 forms in three things: the channel counts it exists for, the stride multiple, the launcher
+        const char *form = cbf ? " (bf16)" : "";
+        const bool channels_ok = cbf ? hvn_chain_bf16_supported(a.K1, a.K1b, a.C, a.N2) != 0
+                                     : hvn_chain_supported(a.C, a.N2) && !(a.K1 % 32 || a.K1b % 32 || a.K1 + a.K1b < 64);
+        const long stride_mask = cbf ? 7 : 3;
+        if (!a.x || !a.w1 || !a.y || !a.w2 || !a.y2) return hvn_fail(HVN_E_ARG, "chain: null pointer");
         if (op->kh != 1 || op->kw != 1 || op->stride != 1 || op->pad_t || op->pad_l || op->relu || op->bias)
-            return fail(HVN_E_ARG, "chain: the first conv is a plain 1x1 (no bias / relu of its own)%s", "");
-        if (!hvn_chain_supported(a.C, a.N2) || op->y.c != a.C || op->y2.c != a.N2 || a.K1 % 32 || a.K1b % 32 || a.K1 + a.K1b < 64)
-            return fail(HVN_E_ARG, "chain: needs cout %% 64 == 0, cout2 in {64, 128}, input channels in slabs of 32 (>= 64) (cout2 = %s%ld)", "", a.N2);
+            return hvn_fail(HVN_E_ARG, "chain: the first conv is a plain 1x1 (no bias / relu of its own)");
+        if (!channels_ok || op->y.c != a.C || op->y2.c != a.N2)
+            return hvn_fail(HVN_E_ARG, "chain%s: needs %s, cout2 in {64, 128} (cout2 = %d)", form,
+                            cbf ? "input channels in slabs of 64 (64 or 128 in all), cout % 256 == 0" : "input channels in slabs of 32 (>= 64), cout % 64 == 0", a.N2);
         if (op->x.h != a.Ho || op->x.w != a.Wo || op->y2.h != a.Ho || op->y2.w != a.Wo ||
             (a.x2 && ((long)(a.Ho - 1) * a.stride2 >= op->x2.h || (long)(a.Wo - 1) * a.stride2 >= op->x2.w)))
-            return fail(HVN_E_ARG, "chain: views do not cover the output grid%s", "");
+            return hvn_fail(HVN_E_ARG, "chain: views do not cover the output grid");
         if (a.res && (a.rsn != a.ysn || a.rsy != a.ysy || a.rsx != a.ysx || op->res.c != a.C))
-            return fail(HVN_E_ARG, "chain: the residual view must have the output's strides%s", "");
+            return hvn_fail(HVN_E_ARG, "chain: the residual view must have the output's strides");
         if (!aligned16(a.x) || !aligned16(a.w1) || !aligned16(a.w2) || !aligned16(a.y) || !aligned16(a.y2) || (a.res && !aligned16(a.res)) ||
-            (a.x2 && !aligned16(a.x2)) || ((a.xsn | a.xsy | a.xsx | a.ysn | a.ysy | a.ysx | a.y2sn | a.y2sy | a.y2sx | a.x2sn | a.x2sy | a.x2sx) & 3))
-            return fail(HVN_E_ARG, "chain: views / weights not 16-byte aligned%s", "");
+            (a.x2 && !aligned16(a.x2)) || !strides_ok(op->x, stride_mask) || !strides_ok(op->y, stride_mask) || !strides_ok(op->y2, stride_mask) ||
+            !strides_ok(op->x2, stride_mask))
+            return hvn_fail(HVN_E_ARG, "chain%s: views / weights not 16-byte aligned", form);
         if ((!a.pre_s != !a.pre_b) || (!a.post_s != !a.post_b) || (a.pre_s && (!aligned16(a.pre_s) || !aligned16(a.pre_b))) ||
             (a.post_s && (!aligned16(a.post_s) || !aligned16(a.post_b))) || (a.bias2 && !aligned16(a.bias2)))
-            return fail(HVN_E_ARG, "chain: per-channel vectors must be 16-byte aligned and come in pairs%s", "");
+            return hvn_fail(HVN_E_ARG, "chain: per-channel vectors must be 16-byte aligned and come in pairs");
         if (g_prof) prof_mark(s);
         int rc;
-        if (cx3 && op->tile_n == 1152)           // input tile resident in registers, operands a chunk ahead (hvn_conv_chain_x3r.hip)
+        if (cbf)
+            rc = hvn_launch_conv_chain_bf16(a, s);
+        else if (cx3 && op->tile_n == 1152)      // input tile resident in registers, operands a chunk ahead (hvn_conv_chain_x3r.hip)
             rc = hvn_launch_conv_chain_x3r(a, op->act_dtype == 3 ? 6 : 9, s);
         else
             rc = cx3 ? hvn_launch_conv_chain_x3(a, op->act_dtype == 3 ? 6 : 9, s) : hvn_launch_conv_chain(a, s);
         if (g_prof) prof_mark(s);
-        if (rc) return fail(rc == -1 ? HVN_E_ARG : HVN_E_LAUNCH, "chain: launch failed (cout2=%s%ld)", "", a.N2);
-        return 0;
+        if (rc) return hvn_fail(rc, "chain%s: launch failed (cout2=%d)", form, a.N2);
+        return HVN_OK;
     }
     case HVN_OP_WINO_IN:
     case HVN_OP_WINO_OUT: {
         WinoArgs a;
         const bool in = op->kind == HVN_OP_WINO_IN;
-        a.x = (const float *)op->x.base;
-        a.xsn = op->x.sn; a.xsy = op->x.sy; a.xsx = op->x.sx;
-        a.y = (float *)op->y.base;
-        a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx;
+        set_view(op->x, a.x, a.xsn, a.xsy, a.xsx);
+        set_view(op->y, a.y, a.ysn, a.ysy, a.ysx);
         a.mat = op->w; a.bias = op->bias;
         a.N = batch; a.H = in ? op->x.h : op->y.h; a.W = in ? op->x.w : op->y.w; a.C = in ? op->x.c : op->y.c;
         a.ty = op->kh; a.tx = op->kw; a.pad = op->pad_t; a.relu = op->relu;
         a.accum = (!in && op->res.base != nullptr) ? 1 : 0;
         a.lo = nullptr; a.lsn = a.lsy = a.lsx = 0;
         if (in && op->res.base) {       // WINO_IN with res: the input is nearest2x(res) + x, formed on the fly (UPADD fused into the transform)
-            a.lo = (const float *)op->res.base;
-            a.lsn = op->res.sn; a.lsy = op->res.sy; a.lsx = op->res.sx;
-            if (op->res.h * 2 != op->x.h || op->res.w * 2 != op->x.w || op->res.c != op->x.c || !aligned16(a.lo) || ((a.lsn | a.lsy | a.lsx) & 3))
-                return fail(HVN_E_ARG, "wino_in: the half-resolution input must be x.h/2 x x.w/2 x x.c and 16-byte aligned%s", "");
+            set_view(op->res, a.lo, a.lsn, a.lsy, a.lsx);
+            if (op->res.h * 2 != op->x.h || op->res.w * 2 != op->x.w || op->res.c != op->x.c || !aligned16(a.lo) || !strides_ok(op->res, 3))
+                return hvn_fail(HVN_E_ARG, "wino_in: the half-resolution input must be x.h/2 x x.w/2 x x.c and 16-byte aligned");
         }
-        if (a.accum && op->res.base != op->y.base) return fail(HVN_E_ARG, "wino_out: res must alias y (accumulate in place)%s", "");
+        if (a.accum && op->res.base != op->y.base) return hvn_fail(HVN_E_ARG, "wino_out: res must alias y (accumulate in place)");
         const int n2 = in ? op->y.h : op->x.h;       // transform positions (m + r - 1)^2
         if (op->stride > 1 && op->_rsv > 1) {         // explicit F(m x m, r x r): stride = m, _rsv = r
             a.m = op->stride; a.r = op->_rsv;
@@ -265,50 +268,46 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
             a.m = n2 == 36 ? 2 : n2 == 64 ? 4 : n2 == 100 ? 6 : 0; a.r = 5;
         }
         if (!a.m || (a.m + a.r - 1) * (a.m + a.r - 1) != n2 || !((a.m == 2 && a.r == 5) || ((a.m == 4 || a.m == 6) && (a.r == 5 || a.r == 3))))
-            return fail(HVN_E_ARG, "winograd transform: %s%ld transform positions do not match F(2,5) / F(4,5) / F(4,3) / F(6,3) / F(6,5)", "", (long)n2);
-        if (!a.x || !a.y || !a.mat || a.ty <= 0 || a.tx <= 0 || (a.C & 3)) return fail(HVN_E_ARG, "winograd transform: bad descriptor%s", "");
-        if (!aligned16(a.x) || !aligned16(a.y) || ((a.xsn | a.xsy | a.xsx | a.ysn | a.ysy | a.ysx) & 3))
-            return fail(HVN_E_ARG, "winograd transform: views not 16-byte aligned%s", "");
-        if (in && (op->y.w != a.ty * a.tx || op->y.c != a.C)) return fail(HVN_E_ARG, "wino_in: V must be [n*n][tiles][c]%s", "");
+            return hvn_fail(HVN_E_ARG, "winograd transform: %d transform positions do not match F(2,5) / F(4,5) / F(4,3) / F(6,3) / F(6,5)", n2);
+        if (!a.x || !a.y || !a.mat || a.ty <= 0 || a.tx <= 0 || (a.C & 3)) return hvn_fail(HVN_E_ARG, "winograd transform: bad descriptor");
+        if (!aligned16(a.x) || !aligned16(a.y) || !strides_ok(op->x, 3) || !strides_ok(op->y, 3))
+            return hvn_fail(HVN_E_ARG, "winograd transform: views not 16-byte aligned");
+        if (in && (op->y.w != a.ty * a.tx || op->y.c != a.C)) return hvn_fail(HVN_E_ARG, "wino_in: V must be [n*n][tiles][c]");
         if (!in && (op->x.w != a.ty * a.tx || op->y.h > a.m * a.ty || op->y.h <= a.m * (a.ty - 1) || op->y.w > a.m * a.tx ||
                     op->y.w <= a.m * (a.tx - 1) || op->x.c != a.C))
-            return fail(HVN_E_ARG, "wino_out: M must be [n*n][tiles][cout] and the tiles must cover y%s", "");
+            return hvn_fail(HVN_E_ARG, "wino_out: M must be [n*n][tiles][cout] and the tiles must cover y");
         if (g_prof) prof_mark(s);
         int rc = in ? hvn_launch_wino_in(a, s) : hvn_launch_wino_out(a, s);
         if (g_prof) prof_mark(s);
-        return rc;
+        return hvn_launch_status(rc, in ? "wino_in" : "wino_out");
     }
     case HVN_OP_UPADD: {
         UpAddArgs a;
-        a.lo = (const float *)op->x.base;
-        a.lsn = op->x.sn; a.lsy = op->x.sy; a.lsx = op->x.sx;
-        a.skip = (const float *)op->res.base;
-        a.ssn = op->res.sn; a.ssy = op->res.sy; a.ssx = op->res.sx;
-        a.y = (float *)op->y.base;
-        a.ysn = op->y.sn; a.ysy = op->y.sy; a.ysx = op->y.sx;
+        set_view(op->x, a.lo, a.lsn, a.lsy, a.lsx);
+        set_view(op->res, a.skip, a.ssn, a.ssy, a.ssx);
+        set_view(op->y, a.y, a.ysn, a.ysy, a.ysx);
         a.N = batch; a.H = op->y.h; a.W = op->y.w; a.C = op->y.c; a.bf16 = op->act_dtype == 1;
-        if (a.bf16 && ((a.lsx | a.lsy | a.lsn | a.ssx | a.ssy | a.ssn | a.ysx | a.ysy | a.ysn) & 7))
-            return fail(HVN_E_ARG, "upadd(bf16): strides must be multiples of 8 elements%s", "");
-        if (!a.lo || !a.skip || !a.y) return fail(HVN_E_ARG, "upadd: null pointer%s", "");
+        if (a.bf16 && !(strides_ok(op->x, 7) && strides_ok(op->res, 7) && strides_ok(op->y, 7)))
+            return hvn_fail(HVN_E_ARG, "upadd(bf16): strides must be multiples of 8 elements");
+        if (!a.lo || !a.skip || !a.y) return hvn_fail(HVN_E_ARG, "upadd: null pointer");
         if (op->x.h * 2 != a.H || op->x.w * 2 != a.W || op->res.h != a.H || op->res.w != a.W || op->x.c != a.C || op->res.c != a.C)
-            return fail(HVN_E_ARG, "upadd: shape mismatch%s", "");
+            return hvn_fail(HVN_E_ARG, "upadd: shape mismatch");
         if (a.C <= 0 || a.C % (a.bf16 ? 8 : 4))     // one thread moves 16 bytes: the launcher would refuse without a text of its own
-            return fail(HVN_E_ARG, "upadd: channels must be a multiple of 4 (fp32) or 8 (bf16) (got %s%ld)", "", a.C);
-        if (!aligned16(a.lo) || !aligned16(a.skip) || !aligned16(a.y) || ((a.lsx | a.lsy | a.lsn | a.ssx | a.ssy | a.ssn | a.ysx | a.ysy | a.ysn) & 3))
-            return fail(HVN_E_ARG, "upadd: views not 16-byte aligned%s", "");
-        return hvn_launch_upadd(a, s);
+            return hvn_fail(HVN_E_ARG, "upadd: channels must be a multiple of 4 (fp32) or 8 (bf16) (got %d)", a.C);
+        if (!aligned16(a.lo) || !aligned16(a.skip) || !aligned16(a.y) || !(strides_ok(op->x, 3) && strides_ok(op->res, 3) && strides_ok(op->y, 3)))
+            return hvn_fail(HVN_E_ARG, "upadd: views not 16-byte aligned");
+        return hvn_launch_status(hvn_launch_upadd(a, s), "upadd");
     }
     case HVN_OP_HEAD: {
         HeadArgs a;
-        a.x = (const float *)op->x.base;
-        a.xsn = op->x.sn; a.xsy = op->x.sy; a.xsx = op->x.sx;
+        set_view(op->x, a.x, a.xsn, a.xsy, a.xsx);
         a.w = op->w; a.bias = op->bias;
         a.y = (float *)op->y.base;
         a.N = batch; a.H = op->x.h; a.W = op->x.w; a.Cout = op->cout; a.in_bf16 = op->act_dtype == 1;
-        if (a.in_bf16 && ((a.xsx | a.xsy | a.xsn) & 7)) return fail(HVN_E_ARG, "head(bf16): strides must be multiples of 8 elements%s", "");
-        if (op->x.c != 64 || !a.w || !a.bias || !a.x || !a.y) return fail(HVN_E_ARG, "head: expects 64 input channels, weights and bias%s", "");
-        if (!aligned16(a.x) || ((a.xsx | a.xsy | a.xsn) & 3)) return fail(HVN_E_ARG, "head: input view not 16-byte aligned%s", "");
-        return hvn_launch_head(a, s);
+        if (a.in_bf16 && !strides_ok(op->x, 7)) return hvn_fail(HVN_E_ARG, "head(bf16): strides must be multiples of 8 elements");
+        if (op->x.c != 64 || !a.w || !a.bias || !a.x || !a.y) return hvn_fail(HVN_E_ARG, "head: expects 64 input channels, weights and bias");
+        if (!aligned16(a.x) || !strides_ok(op->x, 3)) return hvn_fail(HVN_E_ARG, "head: input view not 16-byte aligned");
+        return hvn_launch_status(hvn_launch_head(a, s), "head");
     }
     case HVN_OP_PREDMAP: {
         PredMapArgs a;
@@ -317,30 +316,30 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         a.tp = op->w;
         a.y = (float *)op->y.base;
         a.N = batch; a.H = op->y.h; a.W = op->y.w; a.nr_types = op->cout;
-        if (!a.np || !a.hv || !a.y || (a.nr_types > 0 && !a.tp)) return fail(HVN_E_ARG, "predmap: null pointer%s", "");
-        if (a.nr_types > 0 && !aligned16(a.y)) return fail(HVN_E_ARG, "predmap: output not 16-byte aligned%s", "");
-        return hvn_launch_predmap(a, s);
+        if (!a.np || !a.hv || !a.y || (a.nr_types > 0 && !a.tp)) return hvn_fail(HVN_E_ARG, "predmap: null pointer");
+        if (a.nr_types > 0 && !aligned16(a.y)) return hvn_fail(HVN_E_ARG, "predmap: output not 16-byte aligned");
+        return hvn_launch_status(hvn_launch_predmap(a, s), "predmap");
     }
     case HVN_OP_VIEW: {
         ViewArgs a;
         a.x = (const uint8_t *)op->x.base;
         a.y = (uint8_t *)op->y.base;
         a.N = batch; a.H = op->x.h; a.W = op->x.w; a.k = op->_rsv;
-        if (a.k < 0 || a.k > 7) return fail(HVN_E_ARG, "view: view id %s%ld outside 0..7", "", a.k);
-        if (op->x_dtype != 0) return fail(HVN_E_ARG, "view: uint8 patches only (x_dtype %s%ld)", "", op->x_dtype);
-        if (!a.x || !a.y || a.x == a.y) return fail(HVN_E_ARG, "view: null pointer, or x and y are the same buffer%s", "");
+        if (a.k < 0 || a.k > 7) return hvn_fail(HVN_E_ARG, "view: view id %d outside 0..7", a.k);
+        if (op->x_dtype != 0) return hvn_fail(HVN_E_ARG, "view: uint8 patches only (x_dtype %d)", op->x_dtype);
+        if (!a.x || !a.y || a.x == a.y) return hvn_fail(HVN_E_ARG, "view: null pointer, or x and y are the same buffer");
         if (a.H < 1 || a.W < 1 || op->x.c != 3 || op->y.h != a.H || op->y.w != a.W || op->y.c != 3)
-            return fail(HVN_E_ARG, "view: x and y must have the same extents, three channels (x.h = %s%ld)", "", a.H);
-        if ((a.k & 1) && a.H != a.W) return fail(HVN_E_ARG, "view: a quarter turn needs square patches (view %s%ld)", "", a.k);
-        if (batch > 65535) return fail(HVN_E_ARG, "view: batch %s%ld above 65535", "", batch);
+            return hvn_fail(HVN_E_ARG, "view: x and y must have the same extents, three channels (x.h = %d)", a.H);
+        if ((a.k & 1) && a.H != a.W) return hvn_fail(HVN_E_ARG, "view: a quarter turn needs square patches (view %d)", a.k);
+        if (batch > 65535) return hvn_fail(HVN_E_ARG, "view: batch %d above 65535", batch);
         if ((op->x.sx && op->x.sx != 3) || (op->y.sx && op->y.sx != 3) || op->x.sc > 1 || op->y.sc > 1)
-            return fail(HVN_E_ARG, "view: pixels are three contiguous bytes%s", "");
+            return hvn_fail(HVN_E_ARG, "view: pixels are three contiguous bytes");
         // 0 = dense; a view's rows are x.h long for odd r, which is x.w there
         a.xsy = op->x.sy ? op->x.sy : 3L * a.W; a.xsn = op->x.sn ? op->x.sn : a.xsy * a.H;
         a.ysy = op->y.sy ? op->y.sy : 3L * a.W; a.ysn = op->y.sn ? op->y.sn : a.ysy * a.H;
         if (a.xsy < 3L * a.W || a.ysy < 3L * a.W || a.xsn < a.xsy * a.H || a.ysn < a.ysy * a.H)
-            return fail(HVN_E_ARG, "view: a stride shorter than a row or a sample%s", "");
-        return hvn_launch_view(a, s);
+            return hvn_fail(HVN_E_ARG, "view: a stride shorter than a row or a sample");
+        return hvn_launch_status(hvn_launch_view(a, s), "view");
     }
     case HVN_OP_TTA: {
         TtaArgs a;
@@ -351,42 +350,38 @@ static int run_one(const hvn_op *op, int batch, hipStream_t s)
         a.y = (float *)op->y.base;
         a.N = batch; a.H = op->y.h; a.W = op->y.w; a.nr_types = op->cout;
         a.k = op->_rsv; a.first = op->kh != 0; a.last = op->kw != 0; a.K = op->stride;
-        if (a.k < 0 || a.k > 7) return fail(HVN_E_ARG, "tta: view id %s%ld outside 0..7", "", a.k);
-        if (a.H < 1 || a.W < 1 || a.nr_types < 0) return fail(HVN_E_ARG, "tta: empty map or negative nr_types (y.h = %s%ld)", "", a.H);
-        if ((a.k & 1) && a.H != a.W) return fail(HVN_E_ARG, "tta: a quarter turn needs square maps (view %s%ld)", "", a.k);
-        if (!a.np || !a.hv || (a.nr_types > 0 && !a.tp)) return fail(HVN_E_ARG, "tta: null pointer%s", "");
-        if (!a.acc || ((uintptr_t)a.acc & 3)) return fail(HVN_E_ARG, "tta: null or misaligned accumulator (y2)%s", "");
-        if (a.last && !a.y) return fail(HVN_E_ARG, "tta: the last view needs an output (y)%s", "");
-        if (a.last && a.K < 1) return fail(HVN_E_ARG, "tta: the last view needs the number of views (stride = %s%ld)", "", a.K);
-        if (a.last && a.y == a.acc) return fail(HVN_E_ARG, "tta: y and the accumulator are the same buffer%s", "");
-        if (a.last && (a.nr_types > 0 ? !aligned16(a.y) : (((uintptr_t)a.y & 3) != 0))) return fail(HVN_E_ARG, "tta: output not 16-byte aligned%s", "");
-        if (batch > 65535) return fail(HVN_E_ARG, "tta: batch %s%ld above 65535", "", batch);
-        return hvn_launch_tta(a, s);
+        if (a.k < 0 || a.k > 7) return hvn_fail(HVN_E_ARG, "tta: view id %d outside 0..7", a.k);
+        if (a.H < 1 || a.W < 1 || a.nr_types < 0) return hvn_fail(HVN_E_ARG, "tta: empty map or negative nr_types (y.h = %d)", a.H);
+        if ((a.k & 1) && a.H != a.W) return hvn_fail(HVN_E_ARG, "tta: a quarter turn needs square maps (view %d)", a.k);
+        if (!a.np || !a.hv || (a.nr_types > 0 && !a.tp)) return hvn_fail(HVN_E_ARG, "tta: null pointer");
+        if (!a.acc || ((uintptr_t)a.acc & 3)) return hvn_fail(HVN_E_ARG, "tta: null or misaligned accumulator (y2)");
+        if (a.last && !a.y) return hvn_fail(HVN_E_ARG, "tta: the last view needs an output (y)");
+        if (a.last && a.K < 1) return hvn_fail(HVN_E_ARG, "tta: the last view needs the number of views (stride = %d)", a.K);
+        if (a.last && a.y == a.acc) return hvn_fail(HVN_E_ARG, "tta: y and the accumulator are the same buffer");
+        if (a.last && (a.nr_types > 0 ? !aligned16(a.y) : (((uintptr_t)a.y & 3) != 0))) return hvn_fail(HVN_E_ARG, "tta: output not 16-byte aligned");
+        if (batch > 65535) return hvn_fail(HVN_E_ARG, "tta: batch %d above 65535", batch);
+        return hvn_launch_status(hvn_launch_tta(a, s), "tta");
     }
     default:
-        return fail(HVN_E_ARG, "unknown op kind %s%ld", "", op->kind);
+        return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }
 }
 
-}  // extern "C"
-int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s) { return run_one(op, batch, s); }
 extern "C" {
 
 int hvn_run_op(const hvn_op *op, int batch, void *stream)
 {
-    if (!op || batch <= 0) return fail(HVN_E_ARG, "run_op: bad arguments%s", "");
-    int rc = run_one(op, batch, (hipStream_t)stream);
-    if (rc == -2) return fail(HVN_E_LAUNCH, "launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    if (!op || batch <= 0) return hvn_fail(HVN_E_ARG, "run_op: bad arguments");
+    return hvn_internal_run_one(op, batch, (hipStream_t)stream);     // its refusals lead with the op's name ("conv: ...")
 }
 
 int hvn_extract_patches(const uint8_t *img, int h, int w, const int32_t *coords, int n_patches, int win, int pad_t, int pad_l,
                         uint8_t *out, void *stream)
 {
     if (!img || !coords || !out || h <= 0 || w <= 0 || n_patches <= 0 || win <= 0 || pad_t < 0 || pad_l < 0)
-        return fail(HVN_E_ARG, "extract_patches: bad arguments%s", "");
+        return hvn_fail(HVN_E_ARG, "extract_patches: bad arguments");
     int rc = hvn_launch_extract_patches(img, h, w, coords, n_patches, win, pad_t, pad_l, out, (hipStream_t)stream);
-    if (rc) return fail(HVN_E_LAUNCH, "extract_patches: launch failed%s", "");
+    if (rc) return hvn_fail(HVN_E_LAUNCH, "extract_patches: launch failed");
     return 0;
 }
 
@@ -394,39 +389,39 @@ int hvn_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitc
                       const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps, uint8_t *dst, int dst_h,
                       int dst_w, void *stream)
 {
-    if (!src || !xofs || !xcoef || !yofs || !ycoef || !dst) return fail(HVN_E_ARG, "resize_window: null pointer%s", "");
-    if (taps != 2 && taps != 4) return fail(HVN_E_ARG, "resize_window: taps = %s%ld (2 = linear, 4 = cubic)", "", taps);
+    if (!src || !xofs || !xcoef || !yofs || !ycoef || !dst) return hvn_fail(HVN_E_ARG, "resize_window: null pointer");
+    if (taps != 2 && taps != 4) return hvn_fail(HVN_E_ARG, "resize_window: taps = %d (2 = linear, 4 = cubic)", taps);
     if (((uintptr_t)xofs & 3) || ((uintptr_t)yofs & 3) || ((uintptr_t)xcoef & 1) || ((uintptr_t)ycoef & 1))
-        return fail(HVN_E_ARG, "resize_window: misaligned table%s", "");
+        return hvn_fail(HVN_E_ARG, "resize_window: misaligned table");
     if (src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0 || full_h <= 0 || full_w <= 0)
-        return fail(HVN_E_ARG, "resize_window: empty source, window or destination%s", "");
+        return hvn_fail(HVN_E_ARG, "resize_window: empty source, window or destination");
     // offsets within a row are 32-bit: 3 * width (and taps * width, the coefficient index) must fit
-    if (src_w > (1 << 29) || dst_w > (1 << 29) || dst_h > (1 << 29)) return fail(HVN_E_ARG, "resize_window: a row longer than 2^29 pixels%s", "");
-    if (src_pitch < 3 * (int64_t)src_w) return fail(HVN_E_ARG, "resize_window: src_pitch %s%ld is shorter than a source row", "", (long)src_pitch);
+    if (src_w > (1 << 29) || dst_w > (1 << 29) || dst_h > (1 << 29)) return hvn_fail(HVN_E_ARG, "resize_window: a row longer than 2^29 pixels");
+    if (src_pitch < 3 * (int64_t)src_w) return hvn_fail(HVN_E_ARG, "resize_window: src_pitch %ld is shorter than a source row", (long)src_pitch);
     // the uploaded box must lie in the full source: taps are clamped against the full source, then translated into the box
     if (src_y0 < 0 || src_x0 < 0 || (int64_t)src_y0 + src_h > full_h || (int64_t)src_x0 + src_w > full_w)
-        return fail(HVN_E_ARG, "resize_window: the uploaded source box leaves the full source%s", "");
+        return hvn_fail(HVN_E_ARG, "resize_window: the uploaded source box leaves the full source");
     int rc = hvn_launch_resize_window(src, src_h, src_w, src_pitch, src_y0, src_x0, full_h, full_w, xofs, xcoef, yofs, ycoef, taps, dst, dst_h,
                                       dst_w, (hipStream_t)stream);
-    if (rc == -4) return fail(HVN_E_SIZE, "resize_window: %s%ld output rows are more than one launch takes (16 * 65535)", "", dst_h);
-    if (rc) return fail(HVN_E_LAUNCH, "resize_window: launch failed%s", "");
+    if (rc == HVN_E_SIZE) return hvn_fail(HVN_E_SIZE, "resize_window: %d output rows are more than one launch takes (16 * 65535)", dst_h);
+    if (rc) return hvn_fail(HVN_E_LAUNCH, "resize_window: launch failed");
     return 0;
 }
 
 // the tissue mask's common refusals: 0 = the extent is one the kernels index with int32
 static int tissue_extent(const char *what, int h, int w)
 {
-    if (h < 1 || w < 1) return fail(HVN_E_ARG, "%s: h or w < 1 (h = %ld)", what, h);
-    if ((int64_t)h * w > ((int64_t)1 << 30)) return fail(HVN_E_SIZE, "%s: h * w > 2^30 (h = %ld)", what, h);
+    if (h < 1 || w < 1) return hvn_fail(HVN_E_ARG, "%s: h or w < 1 (h = %d)", what, h);
+    if ((int64_t)h * w > ((int64_t)1 << 30)) return hvn_fail(HVN_E_SIZE, "%s: h * w > 2^30 (h = %d)", what, h);
     return 0;
 }
 
 int hvn_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, void *stream)
 {
-    if (!rgb || !gray || !hist256) return fail(HVN_E_ARG, "%s: null pointer", "tissue_gray_hist");
-    if ((uintptr_t)hist256 & 3) return fail(HVN_E_ARG, "%s: misaligned hist256", "tissue_gray_hist");
+    if (!rgb || !gray || !hist256) return hvn_fail(HVN_E_ARG, "tissue_gray_hist: null pointer");
+    if ((uintptr_t)hist256 & 3) return hvn_fail(HVN_E_ARG, "tissue_gray_hist: misaligned hist256");
     if (int rc = tissue_extent("tissue_gray_hist", h, w)) return rc;
-    if (hvn_launch_tissue_gray_hist(rgb, h, w, gray, hist256, (hipStream_t)stream)) return fail(HVN_E_LAUNCH, "%s: launch failed", "tissue_gray_hist");
+    if (hvn_launch_tissue_gray_hist(rgb, h, w, gray, hist256, (hipStream_t)stream)) return hvn_fail(HVN_E_LAUNCH, "tissue_gray_hist: launch failed");
     return 0;
 }
 
@@ -439,14 +434,14 @@ size_t hvn_tissue_mask_workspace_bytes(int h, int w)
 int hvn_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
                     uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!gray || !mask || !workspace) return fail(HVN_E_ARG, "%s: null pointer", "tissue_mask");
+    if (!gray || !mask || !workspace) return hvn_fail(HVN_E_ARG, "tissue_mask: null pointer");
     if (int rc = tissue_extent("tissue_mask", h, w)) return rc;
-    if (radius < 0 || radius > 32) return fail(HVN_E_ARG, "tissue_mask: radius %s%ld outside [0, 32]", "", radius);
-    if ((uintptr_t)workspace & 15) return fail(HVN_E_ARG, "%s: workspace is not 16-byte aligned", "tissue_mask");
+    if (radius < 0 || radius > 32) return hvn_fail(HVN_E_ARG, "tissue_mask: radius %d outside [0, 32]", radius);
+    if ((uintptr_t)workspace & 15) return hvn_fail(HVN_E_ARG, "tissue_mask: workspace is not 16-byte aligned");
     if (workspace_bytes < hvn_tissue_workspace_bytes(h, w))
-        return fail(HVN_E_SIZE, "tissue_mask: workspace smaller than hvn_tissue_mask_workspace_bytes%s (%ld bytes given)", "", (long)workspace_bytes);
+        return hvn_fail(HVN_E_SIZE, "tissue_mask: workspace smaller than hvn_tissue_mask_workspace_bytes (%zu bytes given)", workspace_bytes);
     if (hvn_launch_tissue_mask(gray, h, w, threshold, min_obj, max_hole, radius, mask, tap_objects, tap_holes, workspace, (hipStream_t)stream))
-        return fail(HVN_E_LAUNCH, "%s: launch failed", "tissue_mask");
+        return hvn_fail(HVN_E_LAUNCH, "tissue_mask: launch failed");
     return 0;
 }
 
@@ -454,29 +449,28 @@ int hvn_viz_strip(const uint8_t *img, int n, int ih, int iw, const float *pred, 
                   const int32_t *tp_map, int h, int w, int nr_types, const int32_t *sel, int n_sel, const uint8_t *lut, uint8_t *out,
                   int n_blocks, void *stream)
 {
-    if (!img || !pred || !np_map || !hv_map || !lut || !out || (n_sel > 0 && !sel)) return fail(HVN_E_ARG, "%s: null pointer", "viz_strip");
-    if (n < 1 || h < 1 || w < 1 || n_blocks < 1) return fail(HVN_E_ARG, "viz_strip: n, h, w or n_blocks < 1 (h = %s%ld)", "", h);
-    if (n_sel < 0 || n_sel > 65535) return fail(HVN_E_ARG, "viz_strip: n_sel %s%ld outside [0, 65535]", "", n_sel);
-    if (ih < h || iw < w) return fail(HVN_E_ARG, "viz_strip: the image is smaller than the maps (ih = %s%ld)", "", ih);
-    if (c != 3 && c != 4) return fail(HVN_E_ARG, "viz_strip: c = %s%ld, not 3 or 4", "", c);
-    if (nr_types < 0 || nr_types > 16) return fail(HVN_E_ARG, "viz_strip: nr_types %s%ld outside [0, 16]", "", nr_types);
-    if ((nr_types > 0) != (c == 4)) return fail(HVN_E_ARG, "viz_strip: nr_types > 0 goes with c == 4 and nr_types == 0 with c == 3 (c = %s%ld)", "", c);
+    if (!img || !pred || !np_map || !hv_map || !lut || !out || (n_sel > 0 && !sel)) return hvn_fail(HVN_E_ARG, "viz_strip: null pointer");
+    if (n < 1 || h < 1 || w < 1 || n_blocks < 1) return hvn_fail(HVN_E_ARG, "viz_strip: n, h, w or n_blocks < 1 (h = %d)", h);
+    if (n_sel < 0 || n_sel > 65535) return hvn_fail(HVN_E_ARG, "viz_strip: n_sel %d outside [0, 65535]", n_sel);
+    if (ih < h || iw < w) return hvn_fail(HVN_E_ARG, "viz_strip: the image is smaller than the maps (ih = %d)", ih);
+    if (c != 3 && c != 4) return hvn_fail(HVN_E_ARG, "viz_strip: c = %d, not 3 or 4", c);
+    if (nr_types < 0 || nr_types > 16) return hvn_fail(HVN_E_ARG, "viz_strip: nr_types %d outside [0, 16]", nr_types);
+    if ((nr_types > 0) != (c == 4)) return hvn_fail(HVN_E_ARG, "viz_strip: nr_types > 0 goes with c == 4 and nr_types == 0 with c == 3 (c = %d)", c);
     if (((uintptr_t)pred | (uintptr_t)np_map | (uintptr_t)hv_map | (uintptr_t)tp_map | (uintptr_t)sel) & 3)
-        return fail(HVN_E_ARG, "%s: misaligned pred, map or sel", "viz_strip");
-    if ((int64_t)2 * h * 5 * w > ((int64_t)1 << 30)) return fail(HVN_E_SIZE, "viz_strip: 2h * 5w > 2^30 (h = %s%ld)", "", h);
+        return hvn_fail(HVN_E_ARG, "viz_strip: misaligned pred, map or sel");
+    if ((int64_t)2 * h * 5 * w > ((int64_t)1 << 30)) return hvn_fail(HVN_E_SIZE, "viz_strip: 2h * 5w > 2^30 (h = %d)", h);
     if (n_sel == 0) return 0;
     if (hvn_launch_viz_strip(img, n, ih, iw, pred, c, np_map, hv_map, tp_map, h, w, nr_types, sel, n_sel, lut, out, n_blocks, (hipStream_t)stream))
-        return fail(HVN_E_LAUNCH, "%s: launch failed", "viz_strip");
+        return hvn_fail(HVN_E_LAUNCH, "viz_strip: launch failed");
     return 0;
 }
 
 int hvn_run_plan(const hvn_op *ops, int n_ops, int batch, void *stream)
 {
-    if (!ops || n_ops <= 0 || batch <= 0) return fail(HVN_E_ARG, "run_plan: bad arguments%s", "");
+    if (!ops || n_ops <= 0 || batch <= 0) return hvn_fail(HVN_E_ARG, "run_plan: bad arguments");
     for (int i = 0; i < n_ops; ++i) {
-        int rc = run_one(&ops[i], batch, (hipStream_t)stream);
-        if (rc == -2) return fail(HVN_E_LAUNCH, "launch failed at op %s%ld", "", i);
-        if (rc) return rc;
+        int rc = hvn_internal_run_one(&ops[i], batch, (hipStream_t)stream);
+        if (rc) return hvn_fail_in_op(rc, "run_plan", i);
     }
     return 0;
 }

@@ -269,7 +269,7 @@ int hvn_launch_aug_shape(const uint8_t *img, const int32_t *ann, int h, int w, i
     const int y0 = (int)((h - oh) * 0.5), x0 = (int)((w - ow) * 0.5);   // cropping_center / CropToFixedSize(position="center")
     hipLaunchKernelGGL(hvn_aug_shape_k, dim3((unsigned)((total + AUG_T - 1) / AUG_T)), dim3(AUG_T), 0, stream, img, ann, h, w, c, prm, oh, ow, y0, x0,
                        oimg, oann, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_launch_aug_shape_images(const uint8_t *pix, const int32_t *ann, const hvn_image_rec *images, const hvn_patch_rec *patches, int n_images,
@@ -280,12 +280,12 @@ int hvn_launch_aug_shape_images(const uint8_t *pix, const int32_t *ann, const hv
     const int y0 = (int)((win_h - oh) * 0.5), x0 = (int)((win_w - ow) * 0.5);   // the crop of hvn_launch_aug_shape, in the patch frame
     hipLaunchKernelGGL(hvn_aug_shape_images_k, dim3((unsigned)((total + AUG_T - 1) / AUG_T)), dim3(AUG_T), 0, stream, pix, ann, images, patches,
                        n_images, n_patches, total_pixels, win_h, win_w, c, prm, oh, ow, y0, x0, oimg, oann, status, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_launch_aug_input(const uint8_t *src, const hvn_aug_sample *prm, const float *noise, int n, int h, int w, uint8_t *dst, hipStream_t stream)
 {
     const long total = (long)n * h * w;
     hipLaunchKernelGGL(hvn_aug_input_k, dim3((unsigned)((total + AUG_T - 1) / AUG_T)), dim3(AUG_T), 0, stream, src, prm, noise, h, w, dst, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

@@ -24,8 +24,8 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/hvn.h"
 #include "hvn_env.h"
+#include "hvn_error.h"
 
 namespace {
 
@@ -149,12 +149,14 @@ struct Tracer {
 extern "C" HVN_API long hvn_trace_contours(const int32_t *inst, int h, int w, const hvn_inst_rec *recs, int n_rec,
                                            int32_t *pts, long max_pts, int64_t *offs)
 {
-    if (!inst || !recs || !pts || !offs || h <= 0 || w <= 0 || n_rec < 0) return HVN_E_ARG;
+    if (!inst || !recs || !pts || !offs) return hvn_fail(HVN_E_ARG, "trace_contours: null pointer");
+    if (h <= 0 || w <= 0 || n_rec < 0) return hvn_fail(HVN_E_ARG, "trace_contours: h or w < 1, or n_rec < 0 (h = %d)", h);
     long crop_px = 0;  // crop pixels to scan
     for (int i = 0; i < n_rec; ++i) {
         const hvn_inst_rec &r = recs[i];
         if (r.area <= 0) continue;
-        if (r.rmin < 0 || r.cmin < 0 || r.rmax > h || r.cmax > w || r.rmax <= r.rmin || r.cmax <= r.cmin) return HVN_E_ARG;
+        if (r.rmin < 0 || r.cmin < 0 || r.rmax > h || r.cmax > w || r.rmax <= r.rmin || r.cmax <= r.cmin)
+            return hvn_fail(HVN_E_ARG, "trace_contours: the bounding box of record %d is empty or leaves the map", i);
         crop_px += (long)(r.rmax - r.rmin) * (r.cmax - r.cmin);
     }
     // Instances are independent: contiguous record ranges go to worker threads (a 2048^2 WSI tile holds ~3000 instances,
@@ -197,7 +199,7 @@ extern "C" HVN_API long hvn_trace_contours(const int32_t *inst, int h, int w, co
         total += cnt[i];
     }
     offs[n_rec] = total;
-    if (total > max_pts) return HVN_E_SIZE;
+    if (total > max_pts) return hvn_fail(HVN_E_SIZE, "trace_contours: %ld points, pts holds max_pts = %ld", total, max_pts);
     long pos = 0;
     for (int t = 0; t < n_thr; ++t) {
         for (size_t k = 0; k < out[t].size(); ++k) pts[2 * pos + (long)k] = out[t][k];

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hvn.h"
+#include "hvn_error.h"   // include/hvn.h and hvn_fail
 
 #define CT_T 64          // one wave per workgroup: a few thousand live lanes, spread over as many CUs as possible
 #define CT_SCAN_T 256
@@ -204,23 +204,27 @@ size_t hvn_contours_workspace_bytes(int n, int max_inst)
 int hvn_trace_contours_device(const int32_t *inst, int n, int h, int w, const hvn_inst_rec *records, int max_inst, int32_t *pts,
                               int64_t max_pts, int64_t *offs, int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!inst || !records || !offs || !status || n <= 0 || h <= 0 || w <= 0 || max_inst <= 0 || max_pts < 0) return HVN_E_ARG;
-    if (max_pts > 0 && (!pts || ((uintptr_t)pts & 7))) return HVN_E_ARG;  // points are stored as (x, y) pairs
-    if ((long)h * w >= (1L << 31)) return HVN_E_ARG;
+    if (!inst || !records || !offs || !status) return hvn_fail(HVN_E_ARG, "trace_contours_device: null inst, records, offs or status");
+    if (n <= 0 || h <= 0 || w <= 0 || max_inst <= 0 || max_pts < 0)
+        return hvn_fail(HVN_E_ARG, "trace_contours_device: n, h, w or max_inst < 1, or max_pts < 0 (max_inst = %d)", max_inst);
+    if (max_pts > 0 && (!pts || ((uintptr_t)pts & 7)))   // points are stored as (x, y) pairs
+        return hvn_fail(HVN_E_ARG, "trace_contours_device: pts NULL or not 8-byte aligned");
+    if ((long)h * w >= (1L << 31)) return hvn_fail(HVN_E_ARG, "trace_contours_device: h * w >= 2^31 (h = %d)", h);
     const long M = (long)n * max_inst;
-    if (M >= 0x7fffffffL) return HVN_E_ARG;  // status[2] holds a slot index
-    if (!workspace || workspace_bytes < hvn_contours_workspace_bytes(n, max_inst)) return HVN_E_SIZE;
+    if (M >= 0x7fffffffL) return hvn_fail(HVN_E_ARG, "trace_contours_device: n * max_inst >= 2^31 - 1 (%ld slots)", M);  // status[2] holds a slot index
+    if (!workspace || workspace_bytes < hvn_contours_workspace_bytes(n, max_inst))
+        return hvn_fail(HVN_E_SIZE, "trace_contours_device: workspace NULL or smaller than hvn_contours_workspace_bytes (%zu bytes given)", workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     int32_t *cnt = (int32_t *)workspace;
     const unsigned blocks = (unsigned)((M + CT_T - 1) / CT_T);
-    if (hipMemsetAsync(status, 0, 4 * sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
-    if (hipMemsetAsync(status + 2, 0xff, sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemsetAsync(status, 0, 4 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status + 2, 0xff, sizeof(int32_t), s) != hipSuccess)
+        return hvn_fail(HVN_E_LAUNCH, "trace_contours_device: hipMemsetAsync failed");
     hipLaunchKernelGGL(ct_trace<false>, dim3(blocks), dim3(CT_T), 0, s, inst, h, w, records, max_inst, M, cnt, (const int64_t *)nullptr,
                        (int2 *)nullptr, (int64_t)0, status);
     hipLaunchKernelGGL(ct_scan, dim3(1), dim3(CT_SCAN_T), 0, s, (const int32_t *)cnt, M, offs, max_pts, status);
     hipLaunchKernelGGL(ct_trace<true>, dim3(blocks), dim3(CT_T), 0, s, inst, h, w, records, max_inst, M, cnt, (const int64_t *)offs,
                        (int2 *)pts, max_pts, status);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("trace_contours_device");
 }
 
 }  // extern "C"

@@ -535,10 +535,10 @@ static int launch_conv(const ConvArgs &a, hipStream_t stream)
     const size_t lds = (stage_fl > ep_fl ? stage_fl : ep_fl) * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, PADDED, GROUPED, HAS_PRE, HAS_X2>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long groups = (p.m_tiles + 7) / 8;
     const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, p.nbatch > 1 ? p.nbatch : 1), dim3(256), lds, stream, p);
     if (dbg_on && grid * (p.nbatch > 1 ? p.nbatch : 1) <= (1 << 20)) {   // experiment mode only: synchronous dump
         hipStreamSynchronize(stream);
@@ -550,25 +550,25 @@ static int launch_conv(const ConvArgs &a, hipStream_t stream)
             fclose(f);
         }
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_launch_dense_grouped(const ConvArgs &a, hipStream_t stream);
 
 int hvn_launch_conv(const ConvArgs &a, int tile_n, hipStream_t stream)
 {
-    if (a.Cin % BK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return -1;
+    if (a.Cin % BK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return HVN_E_ARG;
     // 32-bit pixel indices and per-thread byte offsets into x / x2 (the epilogue addresses y and res with 64 bits)
     const int bm = tile_n == 320 ? 256 : 128;
-    if (!hvn_conv_reach_ok(a, bm, 4, 256, true, false)) return -1;
-    if ((long)(a.Cout + 128) * a.KH * a.KW * a.Cin * 4 >= (1L << 32)) return -1;
+    if (!hvn_conv_reach_ok(a, bm, 4, 256, true, false)) return HVN_E_ARG;
+    if ((long)(a.Cout + 128) * a.KH * a.KW * a.Cin * 4 >= (1L << 32)) return HVN_E_ARG;
     const bool padded = hvn_conv_padded(a);
-    if (padded && a.pre_s) return -1;  // zero padding is produced by the load, before a prologue could run
+    if (padded && a.pre_s) return HVN_E_ARG;  // zero padding is produced by the load, before a prologue could run
     if (a.x2) {  // fused shortcut: 1x1, no prologue, no padding (validated by the caller)
-        if (padded || a.Cin2 % BK) return -1;
+        if (padded || a.Cin2 % BK) return HVN_E_ARG;
         if (tile_n == 128) return launch_conv<128, 128, 2, 2, false, false, false, true>(a, stream);
         if (tile_n == 64) return launch_conv<128, 64, 4, 1, false, false, false, true>(a, stream);
-        return -1;
+        return HVN_E_ARG;
     }
     switch (tile_n) {
     case 128:
@@ -593,9 +593,9 @@ int hvn_launch_conv(const ConvArgs &a, int tile_n, hipStream_t stream)
             return hvn_launch_dense_grouped(a, stream);
         if (a.groups == 4 && a.Cin == 128 && a.Cout == 32)
             return padded ? launch_conv<128, 32, 4, 1, true, true>(a, stream) : launch_conv<128, 32, 4, 1, false, true>(a, stream);
-        if (a.groups != 1 && !(a.groups == 4 && a.Cin == 128 && a.Cout == 32)) return -1;
+        if (a.groups != 1 && !(a.groups == 4 && a.Cin == 128 && a.Cout == 32)) return HVN_E_ARG;
         return padded ? launch_conv<128, 32, 4, 1, true>(a, stream) : launch_conv<128, 32, 4, 1, false>(a, stream);
-    default: return -1;
+    default: return HVN_E_ARG;
     }
 }
 
@@ -710,11 +710,11 @@ static int launch_dense_grouped(const ConvArgs &a, hipStream_t stream)
     const size_t lds = (size_t)(DG_TH + KS - 1) * (DG_TW + KS - 1) * DG_PP * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_dense_grouped_f32<KS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = 2L * tiles_x * tiles_y * a.N;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a, tiles_x, tiles_y);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 
@@ -814,11 +814,11 @@ static int launch_dense_grouped2(const ConvArgs &a, hipStream_t stream)
     const size_t lds = (size_t)(DG2_TH + KS - 1) * (DG2_TW + KS - 1) * DG_PP * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_dense_grouped2_f32<KS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = 2L * tiles_x * tiles_y * a.N;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a, tiles_x, tiles_y);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 
@@ -951,11 +951,11 @@ static int launch_dense_grouped3(const ConvArgs &a, int run, hipStream_t stream)
     const size_t lds = (size_t)8 * (DG2_TW + KS - 1) * DG_PP * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_dense_grouped3_f32<KS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = 2L * tiles_x * runs * a.N;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a, tiles_x, tiles_y, run, runs);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_launch_dense_grouped(const ConvArgs &a, hipStream_t stream)
@@ -971,14 +971,14 @@ int hvn_launch_dense_grouped(const ConvArgs &a, hipStream_t stream)
         constexpr int run = 4;
         if (a.KH == 5) return launch_dense_grouped3<5>(a, run, stream);
         if (a.KH == 3) return launch_dense_grouped3<3>(a, run, stream);
-        return -1;
+        return HVN_E_ARG;
     }
     if (form == 2) {
         if (a.KH == 5) return launch_dense_grouped2<5>(a, stream);
         if (a.KH == 3) return launch_dense_grouped2<3>(a, stream);
-        return -1;
+        return HVN_E_ARG;
     }
     if (a.KH == 5) return launch_dense_grouped<5>(a, stream);
     if (a.KH == 3) return launch_dense_grouped<3>(a, stream);
-    return -1;
+    return HVN_E_ARG;
 }

@@ -417,18 +417,18 @@ static int launch_bf16(const ConvArgs &a, hipStream_t stream)
 
 int hvn_launch_conv_bf16(const ConvArgs &a, int tile_n, hipStream_t stream)
 {
-    if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0 || a.nbatch > 1) return -1;
-    if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return -1;   // 16-byte epilogue accesses
-    if (!hvn_conv_reach_ok(a, 128, 2, 256, false, true)) return -1;      // (this launcher never checked the reach of x2)
+    if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0 || a.nbatch > 1) return HVN_E_ARG;
+    if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return HVN_E_ARG;   // 16-byte epilogue accesses
+    if (!hvn_conv_reach_ok(a, 128, 2, 256, false, true)) return HVN_E_ARG;      // (this launcher never checked the reach of x2)
     const long kt = (long)a.KH * a.KW * ((a.Cin + BKH - 1) / BKH) + (a.x2 ? a.Cin2 / BKH : 0);
-    if ((long)(a.Cout + 128) * kt * BKH * 2 >= (1L << 31)) return -1;
+    if ((long)(a.Cout + 128) * kt * BKH * 2 >= (1L << 31)) return HVN_E_ARG;
     const bool padded = hvn_conv_padded(a);
-    if (padded && a.pre_s) return -1;
+    if (padded && a.pre_s) return HVN_E_ARG;
     if (a.x2) {
-        if (padded || a.Cin2 % BKH || a.Cin % BKH || a.pre_s) return -1;
+        if (padded || a.Cin2 % BKH || a.Cin % BKH || a.pre_s) return HVN_E_ARG;
         if (tile_n == 128) return launch_bf16<128, 128, 2, 2, false, false, true>(a, stream);
         if (tile_n == 64) return launch_bf16<128, 64, 4, 1, false, false, true>(a, stream);
-        return -1;
+        return HVN_E_ARG;
     }
     switch (tile_n) {
     case 128:
@@ -440,6 +440,6 @@ int hvn_launch_conv_bf16(const ConvArgs &a, int tile_n, hipStream_t stream)
     case 32:
         if (a.pre_s) return launch_bf16<128, 32, 4, 1, false, true, false>(a, stream);
         return padded ? launch_bf16<128, 32, 4, 1, true, false, false>(a, stream) : launch_bf16<128, 32, 4, 1, false, false, false>(a, stream);
-    default: return -1;
+    default: return HVN_E_ARG;
     }
 }

@@ -364,15 +364,15 @@ static int launch_bf16g(const ConvArgs &a, hipStream_t stream)
 // no batched launch, cout >= 128.
 int hvn_launch_conv_bf16g(const ConvArgs &a, int bm, hipStream_t stream)
 {
-    if ((bm != 256 && bm != 128) || a.Cout < 128 || a.pre_s || a.nbatch > 1) return -1;
-    if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0) return -1;
-    if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return -1;
-    if (!hvn_conv_reach_ok(a, bm, 2, 512, true, true)) return -1;
+    if ((bm != 256 && bm != 128) || a.Cout < 128 || a.pre_s || a.nbatch > 1) return HVN_E_ARG;
+    if (a.Cin % 32 != 0 || a.Cin <= 0 || a.Cout % 8 != 0) return HVN_E_ARG;
+    if ((((uintptr_t)a.y) & 15) || ((a.ysn | a.ysy | a.ysx) & 7) || (a.res && ((((uintptr_t)a.res) & 15) || ((a.rsn | a.rsy | a.rsx) & 7)))) return HVN_E_ARG;
+    if (!hvn_conv_reach_ok(a, bm, 2, 512, true, true)) return HVN_E_ARG;
     const long kt = (long)a.KH * a.KW * ((a.Cin + HK - 1) / HK) + (a.x2 ? a.Cin2 / HK : 0);
-    if ((long)(a.Cout + 128) * kt * HK * 2 >= (1L << 31)) return -1;
+    if ((long)(a.Cout + 128) * kt * HK * 2 >= (1L << 31)) return HVN_E_ARG;
     const bool padded = hvn_conv_padded(a);
     if (a.x2) {
-        if (padded || a.Cin2 % HK || a.Cin % HK) return -1;
+        if (padded || a.Cin2 % HK || a.Cin % HK) return HVN_E_ARG;
         return bm == 256 ? launch_bf16g<256, false, true>(a, stream) : launch_bf16g<128, false, true>(a, stream);
     }
     if (bm == 256) return padded ? launch_bf16g<256, true, false>(a, stream) : launch_bf16g<256, false, false>(a, stream);

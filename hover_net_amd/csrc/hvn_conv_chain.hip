@@ -373,9 +373,9 @@ static int launch_chain(const ChainArgs &a, hipStream_t stream)
     static_assert((size_t)BM * CH_EP <= (size_t)2 * (BM + CH_BN) * 32, "the epilogue tile must fit the staging buffers it aliases");
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_conv_chain_f32<BM, N2, HAS_X2>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = (a.M + BM - 1) / BM;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     static unsigned long long *dbg_buf = nullptr;
     static int dbg_on = -1;
     if (dbg_on < 0) {
@@ -394,24 +394,24 @@ static int launch_chain(const ChainArgs &a, hipStream_t stream)
             fclose(f);
         }
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_chain_supported(int c, int n2) { return c > 0 && c % CH_BN == 0 && (n2 == 64 || n2 == 128); }
 
 int hvn_launch_conv_chain(const ChainArgs &a, hipStream_t stream)
 {
-    if (!hvn_chain_supported(a.C, a.N2) || a.K1 <= 0 || a.K1 % 32 || a.K1 + a.K1b < 64 || (a.x2 && (a.K1b <= 0 || a.K1b % 32))) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
+    if (!hvn_chain_supported(a.C, a.N2) || a.K1 <= 0 || a.K1 % 32 || a.K1 + a.K1b < 64 || (a.x2 && (a.K1b <= 0 || a.K1b % 32))) return HVN_E_ARG;
+    if (a.M <= 0 || a.M >= (1L << 31) - 256) return HVN_E_ARG;
     // 32-bit per-thread byte offsets below 2^31 (the top bit marks rows past the end): a tile of `bm` pixels spans at most
     // bm / (Ho * Wo) + 2 samples (two when a sample holds at least a tile's worth of pixels, as in every HoVer-Net plan)
     const long px = (long)a.Ho * a.Wo;
-    if (px <= 0) return -1;
+    if (px <= 0) return HVN_E_ARG;
     const long ns = (a.bm == 64 ? 64 : 128) / px + 2;
     const long spans[5] = {ns * a.xsn, a.x2 ? ns * a.x2sn : 0, ns * a.ysn, a.res ? ns * a.rsn : 0, ns * a.y2sn};
     for (long s : spans)
-        if (s < 0 || s * 4 >= (1L << 31)) return -1;
-    if ((long)(a.C + 64) * (a.K1 + a.K1b) * 4 >= (1L << 31) || (long)(a.N2 + 64) * a.C * 4 >= (1L << 31)) return -1;
+        if (s < 0 || s * 4 >= (1L << 31)) return HVN_E_ARG;
+    if ((long)(a.C + 64) * (a.K1 + a.K1b) * 4 >= (1L << 31) || (long)(a.N2 + 64) * a.C * 4 >= (1L << 31)) return HVN_E_ARG;
     const bool small = a.bm == 64;          // pixels per workgroup: 128 (default) or 64
     if (a.N2 == 64) {
         if (small) return a.x2 ? launch_chain<64, 64, true>(a, stream) : launch_chain<64, 64, false>(a, stream);

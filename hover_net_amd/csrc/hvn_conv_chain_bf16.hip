@@ -341,11 +341,11 @@ static int launch_chain_bf16(const ChainArgs &a, hipStream_t stream)
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_conv_chain_bf16<N2, KA, HAS_X2, FL>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = (a.M + CB_BM - 1) / CB_BM;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // Which chains have this form: conv3's reduction (K1 + K1b) is 64 or 128 channels in whole 64-channel slabs (the bf16 packing's k-step),
@@ -360,15 +360,15 @@ int hvn_chain_bf16_supported(int k1, int k1b, int c, int n2)
 // packing ([rows][ceil(k / 64)][1][64] bf16); fp32 per-channel vectors.
 int hvn_launch_conv_chain_bf16(const ChainArgs &a, hipStream_t stream)
 {
-    if (!hvn_chain_bf16_supported(a.K1, a.x2 ? a.K1b : 0, a.C, a.N2) || (a.x2 != nullptr) != (a.K1b > 0)) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
+    if (!hvn_chain_bf16_supported(a.K1, a.x2 ? a.K1b : 0, a.C, a.N2) || (a.x2 != nullptr) != (a.K1b > 0)) return HVN_E_ARG;
+    if (a.M <= 0 || a.M >= (1L << 31) - 256) return HVN_E_ARG;
     const long px = (long)a.Ho * a.Wo;
-    if (px <= 0) return -1;
+    if (px <= 0) return HVN_E_ARG;
     const long ns = CB_BM / px + 2;
     const long spans[5] = {ns * a.xsn, a.x2 ? ns * a.x2sn : 0, ns * a.ysn, a.res ? ns * a.rsn : 0, ns * a.y2sn};
     for (long s : spans)
-        if (s < 0 || s * 2 >= (1L << 31)) return -1;
-    if ((long)(a.C + 64) * (a.K1 + a.K1b) * 2 >= (1L << 31) || (long)(a.N2 + 64) * a.C * 2 >= (1L << 31)) return -1;
+        if (s < 0 || s * 2 >= (1L << 31)) return HVN_E_ARG;
+    if ((long)(a.C + 64) * (a.K1 + a.K1b) * 2 >= (1L << 31) || (long)(a.N2 + 64) * a.C * 2 >= (1L << 31)) return HVN_E_ARG;
     const int ka = a.K1 + a.K1b;
     const int fl = (a.res ? 1 : 0) | (a.pre_s ? 2 : 0) | (a.post_s ? 4 : 0);
     // the four seams of a HoVer-Net encoder, with their operand set compiled in
@@ -377,9 +377,9 @@ int hvn_launch_conv_chain_bf16(const ChainArgs &a, hipStream_t stream)
     if (a.N2 == 128 && ka == 64 && !a.x2 && fl == 5) return launch_chain_bf16<128, 64, false, 5>(a, stream);     // d0's last unit (block BN-ReLU) -> d1 unit 0
     if (a.N2 == 128 && ka == 128 && !a.x2 && fl == 3) return launch_chain_bf16<128, 128, false, 3>(a, stream);   // d1 unit i -> unit i + 1
     if (a.N2 == 64) {
-        if (a.x2) return ka == 128 ? launch_chain_bf16<64, 128, true>(a, stream) : -1;
+        if (a.x2) return ka == 128 ? launch_chain_bf16<64, 128, true>(a, stream) : HVN_E_ARG;
         return ka == 128 ? launch_chain_bf16<64, 128, false>(a, stream) : launch_chain_bf16<64, 64, false>(a, stream);
     }
-    if (a.x2) return -1;       // (a fused shortcut in front of a 128-wide conv1 does not occur in HoVer-Net)
+    if (a.x2) return HVN_E_ARG;       // (a fused shortcut in front of a 128-wide conv1 does not occur in HoVer-Net)
     return ka == 128 ? launch_chain_bf16<128, 128, false>(a, stream) : launch_chain_bf16<128, 64, false>(a, stream);
 }

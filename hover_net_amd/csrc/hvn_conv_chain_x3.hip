@@ -379,26 +379,26 @@ static int launch_chain_x3(const ChainArgs &a, hipStream_t stream)
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_conv_chain_x3<N2, HAS_X2, NTERMS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = (a.M + CX_BM - 1) / CX_BM;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ChainArgs as hvn_launch_conv_chain, except: w1 / w2 = the bf16 planes of the fp32 packings ([rows][k-step][3][32] bf16: hvn_conv_x3.hip),
 // 128 pixels per workgroup, terms = 9 | 6 partial products per product.
 int hvn_launch_conv_chain_x3(const ChainArgs &a, int terms, hipStream_t stream)
 {
-    if (!hvn_chain_supported(a.C, a.N2) || a.K1 <= 0 || a.K1 % 32 || a.K1 + a.K1b < 64 || (a.x2 && (a.K1b <= 0 || a.K1b % 32))) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
+    if (!hvn_chain_supported(a.C, a.N2) || a.K1 <= 0 || a.K1 % 32 || a.K1 + a.K1b < 64 || (a.x2 && (a.K1b <= 0 || a.K1b % 32))) return HVN_E_ARG;
+    if (a.M <= 0 || a.M >= (1L << 31) - 256) return HVN_E_ARG;
     const long px = (long)a.Ho * a.Wo;
-    if (px <= 0) return -1;
+    if (px <= 0) return HVN_E_ARG;
     const long ns = 128 / px + 2;
     const long spans[5] = {ns * a.xsn, a.x2 ? ns * a.x2sn : 0, ns * a.ysn, a.res ? ns * a.rsn : 0, ns * a.y2sn};
     for (long s : spans)
-        if (s < 0 || s * 4 >= (1L << 31)) return -1;
-    if ((long)(a.C + 64) * ((a.K1 + a.K1b) / 32) * 192 >= (1L << 31) || (long)(a.N2 + 64) * (a.C / 32) * 192 >= (1L << 31)) return -1;
+        if (s < 0 || s * 4 >= (1L << 31)) return HVN_E_ARG;
+    if ((long)(a.C + 64) * ((a.K1 + a.K1b) / 32) * 192 >= (1L << 31) || (long)(a.N2 + 64) * (a.C / 32) * 192 >= (1L << 31)) return HVN_E_ARG;
     const bool nine = terms != 6;
     if (a.N2 == 64) {
         if (a.x2) return nine ? launch_chain_x3<64, true, 9>(a, stream) : launch_chain_x3<64, true, 6>(a, stream);

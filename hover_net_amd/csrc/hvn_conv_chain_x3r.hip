@@ -363,11 +363,11 @@ static int launch_chain_x3r(const ChainArgs &a, hipStream_t stream)
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = hvn_conv_chain_x3r<N2, HAS_X2, NTERMS>;
-    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, (int)lds, attr_done)) return HVN_E_LAUNCH;
     const long grid = (a.M + CR_BM - 1) / CR_BM;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // Does the op have this form?  conv3 with 64 input channels (+ 64 of a fused shortcut, then without a residual view and with cout2 = 64):
@@ -383,15 +383,15 @@ int hvn_chain_x3r_supported(const ChainArgs &a)
 // ChainArgs as hvn_launch_conv_chain_x3 (same operands, same packings, same bits).
 int hvn_launch_conv_chain_x3r(const ChainArgs &a, int terms, hipStream_t stream)
 {
-    if (!hvn_chain_x3r_supported(a)) return -1;
-    if (a.M <= 0 || a.M >= (1L << 31) - 256) return -1;
+    if (!hvn_chain_x3r_supported(a)) return HVN_E_ARG;
+    if (a.M <= 0 || a.M >= (1L << 31) - 256) return HVN_E_ARG;
     const long px = (long)a.Ho * a.Wo;
-    if (px <= 0) return -1;
+    if (px <= 0) return HVN_E_ARG;
     const long ns = 128 / px + 2;
     const long spans[5] = {ns * a.xsn, a.x2 ? ns * a.x2sn : 0, ns * a.ysn, a.res ? ns * a.rsn : 0, ns * a.y2sn};
     for (long s : spans)
-        if (s < 0 || s * 4 >= (1L << 31)) return -1;
-    if ((long)(a.C + 64) * ((a.K1 + a.K1b) / 32) * 192 >= (1L << 31) || (long)(a.N2 + 64) * (a.C / 32) * 192 >= (1L << 31)) return -1;
+        if (s < 0 || s * 4 >= (1L << 31)) return HVN_E_ARG;
+    if ((long)(a.C + 64) * ((a.K1 + a.K1b) / 32) * 192 >= (1L << 31) || (long)(a.N2 + 64) * (a.C / 32) * 192 >= (1L << 31)) return HVN_E_ARG;
     const bool nine = terms != 6;
     if (a.x2) return nine ? launch_chain_x3r<64, true, 9>(a, stream) : launch_chain_x3r<64, true, 6>(a, stream);
     if (a.N2 == 64) return nine ? launch_chain_x3r<64, false, 9>(a, stream) : launch_chain_x3r<64, false, 6>(a, stream);

@@ -112,10 +112,10 @@ static inline int hvn_conv_launch(Kern kern, ConvArgs p, int bm, int bn, int thr
 {
     p.m_tiles = (p.M + bm - 1) / bm;
     p.n_tiles = (p.Cout + bn - 1) / bn;
-    if (hvn_max_lds_once((const void *)kern, attr_lds, attr_done)) return -2;
+    if (hvn_max_lds_once((const void *)kern, attr_lds, attr_done)) return HVN_E_LAUNCH;
     const long groups = (p.m_tiles + 7) / 8;
     const long grid = groups * 8 * p.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffL) return -1;
+    if (grid <= 0 || grid > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, p.nbatch > 1 ? p.nbatch : 1), dim3(threads), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

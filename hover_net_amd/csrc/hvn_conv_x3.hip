@@ -387,11 +387,11 @@ __global__ __launch_bounds__(256) void hvn_split_x3(const float *src, uint16_t *
 
 int hvn_launch_split_x3(const float *src, uint16_t *dst, long granules, hipStream_t stream)
 {
-    if (!src || !dst || granules <= 0 || (((uintptr_t)src | (uintptr_t)dst) & 15)) return -1;
+    if (!src || !dst || granules <= 0 || (((uintptr_t)src | (uintptr_t)dst) & 15)) return HVN_E_ARG;
     const long blocks = (granules * 8 + 255) / 256;
-    if (blocks > 0x7fffffffL) return -1;
+    if (blocks > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(hvn_split_x3, dim3((unsigned)blocks), dim3(256), 0, stream, src, dst, granules);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool PADDED, bool HAS_PRE, bool HAS_X2, int NTERMS>
@@ -409,7 +409,7 @@ static int dispatch_x3(const ConvArgs &a, int tile_n, bool padded, hipStream_t s
     if (a.x2) {
         if (tile_n == 128) return launch_x3<128, 128, 2, 2, false, false, true, NTERMS>(a, stream);
         if (tile_n == 64) return launch_x3<128, 64, 4, 1, false, false, true, NTERMS>(a, stream);
-        return -1;
+        return HVN_E_ARG;
     }
     switch (tile_n) {
     case 128:
@@ -418,7 +418,7 @@ static int dispatch_x3(const ConvArgs &a, int tile_n, bool padded, hipStream_t s
     case 64:
         if (a.pre_s) return launch_x3<128, 64, 4, 1, false, true, false, NTERMS>(a, stream);
         return padded ? launch_x3<128, 64, 4, 1, true, false, false, NTERMS>(a, stream) : launch_x3<128, 64, 4, 1, false, false, false, NTERMS>(a, stream);
-    default: return -1;
+    default: return HVN_E_ARG;
     }
 }
 
@@ -426,12 +426,12 @@ static int dispatch_x3(const ConvArgs &a, int tile_n, bool padded, hipStream_t s
 // terms: 9 (every partial product: the fp32 dot product in another summation order) or 6.
 int hvn_launch_conv_x3(const ConvArgs &a, int tile_n, int terms, hipStream_t stream)
 {
-    if (a.Cin % XK != 0 || a.Cin <= 0 || a.Cout % 4 != 0 || a.groups > 1) return -1;
-    if (!hvn_conv_reach_ok(a, 128, 4, 256, true, true)) return -1;
+    if (a.Cin % XK != 0 || a.Cin <= 0 || a.Cout % 4 != 0 || a.groups > 1) return HVN_E_ARG;
+    if (!hvn_conv_reach_ok(a, 128, 4, 256, true, true)) return HVN_E_ARG;
     const long kt = (long)a.KH * a.KW * (a.Cin / XK) + (a.x2 ? a.Cin2 / XK : 0);
-    if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return -1;
+    if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return HVN_E_ARG;
     const bool padded = hvn_conv_padded(a);
-    if (padded && a.pre_s) return -1;
-    if (a.x2 && (padded || a.Cin2 % XK || a.pre_s)) return -1;
+    if (padded && a.pre_s) return HVN_E_ARG;
+    if (a.x2 && (padded || a.Cin2 % XK || a.pre_s)) return HVN_E_ARG;
     return terms == 6 ? dispatch_x3<6>(a, tile_n, padded, stream) : dispatch_x3<9>(a, tile_n, padded, stream);
 }

@@ -498,7 +498,7 @@ static int launch_x3g(const ConvArgs &a, hipStream_t stream)
     constexpr int NA = BM == 256 ? 3 : 2;
     const size_t stage_b = (size_t)NA * BM * 128 + 2 * G_BSTAGE + (HAS_PRE && BM == 256 ? (size_t)2 * a.Cin * 4 : 0), ep_b = (size_t)BM * (GBN + 4) * 4;
     const size_t lds = stage_b > ep_b ? stage_b : ep_b;
-    if (lds > 160 * 1024) return -1;
+    if (lds > 160 * 1024) return HVN_E_ARG;
     static std::atomic<unsigned long long> attr_done{0};
     return hvn_conv_launch(hvn_conv_igemm_x3g<BM, PADDED, HAS_PRE, HAS_X2, NTERMS>, a, BM, GBN, BM * 2, lds, 160 * 1024, attr_done, stream);
 }
@@ -523,15 +523,15 @@ int hvn_conv_x3g_supported(const ConvArgs &a, int bm)
 // As hvn_launch_conv_x3 (same operands, same packing, same bits), 256 | 128 pixels x 128 channels per workgroup.
 int hvn_launch_conv_x3g(const ConvArgs &a, int bm, int terms, hipStream_t stream)
 {
-    if (!hvn_conv_x3g_supported(a, bm)) return -1;
-    if (a.Cin % GK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return -1;
-    if (!hvn_conv_reach_ok(a, bm, 4, 512, true, true)) return -1;
+    if (!hvn_conv_x3g_supported(a, bm)) return HVN_E_ARG;
+    if (a.Cin % GK != 0 || a.Cin <= 0 || a.Cout % 4 != 0) return HVN_E_ARG;
+    if (!hvn_conv_reach_ok(a, bm, 4, 512, true, true)) return HVN_E_ARG;
     const long kt = (long)a.KH * a.KW * (a.Cin / GK) + (a.x2 ? a.Cin2 / GK : 0);
-    if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return -1;
+    if ((long)(a.Cout + 128) * kt * 192 >= (1L << 31)) return HVN_E_ARG;
     const bool padded = hvn_conv_padded(a);
-    if (padded && a.pre_s) return -1;
-    if (a.x2 && (padded || a.Cin2 % GK || a.pre_s)) return -1;
-    if (a.pre_s && (((uintptr_t)a.pre_s | (uintptr_t)a.pre_b) & 15)) return -1;
+    if (padded && a.pre_s) return HVN_E_ARG;
+    if (a.x2 && (padded || a.Cin2 % GK || a.pre_s)) return HVN_E_ARG;
+    if (a.pre_s && (((uintptr_t)a.pre_s | (uintptr_t)a.pre_b) & 15)) return HVN_E_ARG;
     if (bm == 256) return terms == 6 ? dispatch_x3g<256, 6>(a, padded, stream) : dispatch_x3g<256, 9>(a, padded, stream);
     return terms == 6 ? dispatch_x3g<128, 6>(a, padded, stream) : dispatch_x3g<128, 9>(a, padded, stream);
 }

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hvn.h"
+#include "hvn_error.h"   // include/hvn.h and hvn_fail
 
 #define FT_T 256            // four waves = four record slots per workgroup (no LDS, no barrier: an empty slot's wave just leaves)
 #define FT_OWN 60           // owned columns of a strip (64 lanes - 2 halo columns on either side)
@@ -130,15 +130,17 @@ int hvn_instance_features(const int32_t *inst, const uint8_t *image, int n, int 
                           hvn_inst_feat *feats, void *workspace, size_t workspace_bytes, void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    if (!inst || !records || !feats || n <= 0 || h <= 0 || w <= 0 || max_inst <= 0) return HVN_E_ARG;
-    if ((long)h * w >= (1L << 31)) return HVN_E_ARG;
-    if (((uintptr_t)feats & 7) || ((uintptr_t)records & 7) || ((uintptr_t)inst & 3)) return HVN_E_ARG;
+    if (!inst || !records || !feats) return hvn_fail(HVN_E_ARG, "instance_features: null inst, records or feats");
+    if (n <= 0 || h <= 0 || w <= 0 || max_inst <= 0) return hvn_fail(HVN_E_ARG, "instance_features: n, h, w or max_inst < 1 (max_inst = %d)", max_inst);
+    if ((long)h * w >= (1L << 31)) return hvn_fail(HVN_E_ARG, "instance_features: h * w >= 2^31 (h = %d)", h);
+    if (((uintptr_t)feats & 7) || ((uintptr_t)records & 7) || ((uintptr_t)inst & 3))
+        return hvn_fail(HVN_E_ARG, "instance_features: feats and records must be 8-byte, inst 4-byte aligned");
     const long n_slots = (long)n * max_inst;
-    if (n_slots >= (1L << 31)) return HVN_E_SIZE;
+    if (n_slots >= (1L << 31)) return hvn_fail(HVN_E_SIZE, "instance_features: n * max_inst >= 2^31 (%ld slots)", n_slots);
     const long blocks = (n_slots + FT_T / 64 - 1) / (FT_T / 64);
     hipLaunchKernelGGL(ft_features, dim3((unsigned)blocks), dim3(FT_T), 0, (hipStream_t)stream, inst, image, h, w, records, max_inst,
                        n_slots, feats);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("instance_features");
 }
 
 }  // extern "C"

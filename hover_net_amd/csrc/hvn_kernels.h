@@ -6,18 +6,19 @@
 #include <atomic>
 
 #include "hvn_env.h"
+#include "hvn_error.h"   // the status enum of include/hvn.h and hvn_fail
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per (kernel instantiation, device), from any
-// host thread.  `done` = one bit per device ordinal (function-local static of the launcher).  Returns 0, or -2 when the runtime refuses.
+// host thread.  `done` = one bit per device ordinal (function-local static of the launcher).  Returns HVN_OK, or HVN_E_LAUNCH when the runtime refuses.
 static inline int hvn_max_lds_once(const void *kern, int bytes, std::atomic<unsigned long long> &done)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
+    if (hipGetDevice(&dev) != hipSuccess) return HVN_E_LAUNCH;
     const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return 0;
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -2;
+    if (done.load(std::memory_order_acquire) & bit) return HVN_OK;
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return HVN_E_LAUNCH;
     done.fetch_or(bit, std::memory_order_release);
-    return 0;
+    return HVN_OK;
 }
 
 struct ConvArgs {
@@ -142,18 +143,18 @@ int hvn_launch_head(const HeadArgs &a, hipStream_t stream);
 int hvn_launch_extract_patches(const uint8_t *img, int H, int W, const int32_t *coords, int P, int win, int pad_t, int pad_l, uint8_t *out,
                                hipStream_t stream);
 
-// hvn_resample.hip: arguments as hvn_resize_window (include/hvn.h), validated by the caller; 0, -2 launch failure, -4 too many tile rows
+// hvn_resample.hip: arguments as hvn_resize_window (include/hvn.h), validated by the caller; HVN_OK, HVN_E_LAUNCH, HVN_E_SIZE = too many tile rows
 int hvn_launch_resize_window(const uint8_t *src, int src_h, int src_w, int64_t src_pitch, int src_y0, int src_x0, int full_h, int full_w,
                              const int32_t *xofs, const int16_t *xcoef, const int32_t *yofs, const int16_t *ycoef, int taps, uint8_t *dst,
                              int dst_h, int dst_w, hipStream_t stream);
 
-// hvn_tissue.hip: arguments as hvn_tissue_gray_hist / hvn_tissue_mask (include/hvn.h), validated by the caller; 0, -2 launch failure
+// hvn_tissue.hip: arguments as hvn_tissue_gray_hist / hvn_tissue_mask (include/hvn.h), validated by the caller; HVN_OK or HVN_E_LAUNCH
 size_t hvn_tissue_workspace_bytes(int h, int w);
 int hvn_launch_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, hipStream_t stream);
 int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
                            uint8_t *tap_objects, uint8_t *tap_holes, void *workspace, hipStream_t stream);
 
-// hvn_viz.hip: arguments as hvn_viz_strip (include/hvn.h), validated by the caller (n_sel >= 1); 0, -2 launch failure
+// hvn_viz.hip: arguments as hvn_viz_strip (include/hvn.h), validated by the caller (n_sel >= 1); HVN_OK or HVN_E_LAUNCH
 int hvn_launch_viz_strip(const uint8_t *img, int n, int ih, int iw, const float *pred, int c, const int32_t *np_map, const float *hv_map,
                          const int32_t *tp_map, int h, int w, int nr_types, const int32_t *sel, int n_sel, const uint8_t *lut, uint8_t *out,
                          int n_blocks, hipStream_t stream);
@@ -166,7 +167,7 @@ struct PredMapArgs {
 int hvn_launch_predmap(const PredMapArgs &a, hipStream_t stream);
 
 // hvn_tta.hip: test-time augmentation over the eight views k = r + 4 f of the square (flip left-right if f, then r quarter turns
-// counter-clockwise); arguments validated by the caller (hvn_api.hip); 0, -2 launch failure
+// counter-clockwise); arguments validated by the caller (hvn_api.hip); HVN_OK or HVN_E_LAUNCH
 struct ViewArgs {
     const uint8_t *x;           // [N][H][W][3]
     long xsn, xsy;              // byte strides of a sample and a row (pixels are 3 contiguous bytes)
@@ -329,7 +330,6 @@ int hvn_launch_loss(const LossArgs &a, int stage, hipStream_t stream);
 int hvn_launch_adam(float *w, const float *g, float *m, float *v, long n, float b1, float b2, float eps, float step_size,
                     float inv_bc2_sqrt, hipStream_t stream);
 
-struct hvn_op;
 int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s);
 
 // ---- validation statistics (hvn_valid.hip) ------------------------------------------------------
@@ -338,11 +338,8 @@ int hvn_launch_valid_stats(const float *pred, const int32_t *np_map, const float
                            long long *counts, double *hv_sse, void *ws, size_t ws_bytes, hipStream_t stream);
 
 // ---- training targets (hvn_targets.hip) ---------------------------------------------------------
-struct hvn_aug_sample;   // include/hvn.h
 int hvn_launch_aug_shape(const uint8_t *img, const int32_t *ann, int h, int w, int c, const struct hvn_aug_sample *prm, int n, int oh, int ow,
                          uint8_t *oimg, int32_t *oann, hipStream_t stream);
-struct hvn_image_rec;
-struct hvn_patch_rec;
 int hvn_launch_aug_shape_images(const uint8_t *pix, const int32_t *ann, const struct hvn_image_rec *images, const struct hvn_patch_rec *patches,
                                 int n_images, int n_patches, long total_pixels, int win_h, int win_w, int c, const struct hvn_aug_sample *prm, int n,
                                 int oh, int ow, uint8_t *oimg, int32_t *oann, int32_t *status, hipStream_t stream);

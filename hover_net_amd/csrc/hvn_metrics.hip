@@ -333,6 +333,10 @@ __global__ void __launch_bounds__(MT_T) rl_permute(int32_t *map, long P, int32_t
 static long rl_words(int32_t max_id) { return (((long)max_id / 32 + 1) + RL_WORDS - 1) / RL_WORDS * RL_WORDS; }
 
 static bool mt_shape_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)h * w <= (1LL << 30) && n <= 65535; }
+static int mt_bad_shape(const char *what, int n, int h)
+{
+    return hvn_fail(HVN_E_ARG, "%s: n outside [1, 65535], h or w < 1, or h * w > 2^30 (n = %d, h = %d)", what, n, h);
+}
 
 static dim3 mt_grid(int n, long P) { return dim3((unsigned)((P + MT_BLK - 1) / MT_BLK), (unsigned)n); }
 
@@ -348,28 +352,32 @@ size_t hvn_pair_table_workspace_bytes(int n, int h, int w)
 int hvn_pair_table(const int32_t *true_map, const int32_t *pred_map, int n, int h, int w, int32_t *triples, int32_t *counts,
                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!true_map || !pred_map || !triples || !counts || !mt_shape_ok(n, h, w)) return HVN_E_ARG;
-    if (!workspace || workspace_bytes < hvn_pair_table_workspace_bytes(n, h, w)) return HVN_E_SIZE;
+    if (!true_map || !pred_map || !triples || !counts) return hvn_fail(HVN_E_ARG, "pair_table: null pointer");
+    if (!mt_shape_ok(n, h, w)) return mt_bad_shape("pair_table", n, h);
+    if (!workspace || workspace_bytes < hvn_pair_table_workspace_bytes(n, h, w))
+        return hvn_fail(HVN_E_SIZE, "pair_table: workspace NULL or smaller than hvn_pair_table_workspace_bytes (%zu bytes given)", workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     const long long C = mt_capacity(h, w);
     const long P = (long)h * w;
     unsigned long long *keys = (unsigned long long *)workspace;
     unsigned *cnt = (unsigned *)((unsigned char *)workspace + mt_align((size_t)n * C * 8));
-    if (hipMemsetAsync(workspace, 0, hvn_pair_table_workspace_bytes(n, h, w), s) != hipSuccess) return HVN_E_LAUNCH;
-    if (hipMemsetAsync(counts, 0, (size_t)n * 4, s) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemsetAsync(workspace, 0, hvn_pair_table_workspace_bytes(n, h, w), s) != hipSuccess ||
+        hipMemsetAsync(counts, 0, (size_t)n * 4, s) != hipSuccess)
+        return hvn_fail(HVN_E_LAUNCH, "pair_table: hipMemsetAsync failed");
     hipLaunchKernelGGL(mt_pair_local, mt_grid(n, P), dim3(MT_T), 0, s, true_map, pred_map, P, keys, cnt, C, triples, counts);
     hipLaunchKernelGGL(mt_pair_compact, dim3(64, n), dim3(MT_T), 0, s, keys, cnt, C, P, triples, counts);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("pair_table");
 }
 
 int hvn_label_range(const int32_t *map, int n, int h, int w, int32_t *range, void *stream)
 {
-    if (!map || !range || !mt_shape_ok(n, h, w)) return HVN_E_ARG;
+    if (!map || !range) return hvn_fail(HVN_E_ARG, "label_range: null pointer");
+    if (!mt_shape_ok(n, h, w)) return mt_bad_shape("label_range", n, h);
     hipStream_t s = (hipStream_t)stream;
     const long P = (long)h * w;
     hipLaunchKernelGGL(rl_range_init, dim3((n + MT_T - 1) / MT_T), dim3(MT_T), 0, s, range, n);
     hipLaunchKernelGGL(rl_range, mt_grid(n, P), dim3(MT_T), 0, s, map, P, range);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("label_range");
 }
 
 size_t hvn_remap_label_workspace_bytes(int n, int h, int w, int32_t max_id)
@@ -382,40 +390,47 @@ size_t hvn_remap_label_workspace_bytes(int n, int h, int w, int32_t max_id)
 int hvn_remap_label(const int32_t *map, int n, int h, int w, int32_t max_id, int32_t *out, int32_t *n_ids, void *workspace,
                     size_t workspace_bytes, void *stream)
 {
-    if (!map || !out || !n_ids || !mt_shape_ok(n, h, w) || max_id < 0) return HVN_E_ARG;
-    if (!workspace || workspace_bytes < hvn_remap_label_workspace_bytes(n, h, w, max_id)) return HVN_E_SIZE;
+    if (!map || !out || !n_ids) return hvn_fail(HVN_E_ARG, "remap_label: null pointer");
+    if (!mt_shape_ok(n, h, w)) return mt_bad_shape("remap_label", n, h);
+    if (max_id < 0) return hvn_fail(HVN_E_ARG, "remap_label: max_id %d < 0", max_id);
+    if (!workspace || workspace_bytes < hvn_remap_label_workspace_bytes(n, h, w, max_id))
+        return hvn_fail(HVN_E_SIZE, "remap_label: workspace NULL or smaller than hvn_remap_label_workspace_bytes (%zu bytes given)", workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     const long P = (long)h * w, Wd = rl_words(max_id);
     const int nbw = (int)(Wd / RL_WORDS);
     unsigned *bits = (unsigned *)workspace;
     unsigned *prefix = (unsigned *)((unsigned char *)workspace + mt_align((size_t)n * Wd * 4));
     unsigned *bsum = (unsigned *)((unsigned char *)prefix + mt_align((size_t)n * Wd * 4));
-    if (hipMemsetAsync(bits, 0, (size_t)n * Wd * 4, s) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemsetAsync(bits, 0, (size_t)n * Wd * 4, s) != hipSuccess) return hvn_fail(HVN_E_LAUNCH, "remap_label: hipMemsetAsync failed");
     hipLaunchKernelGGL(rl_mark, mt_grid(n, P), dim3(MT_T), 0, s, map, P, max_id, bits, Wd);
     hipLaunchKernelGGL(rl_block_sums, dim3(nbw, n), dim3(MT_T), 0, s, bits, Wd, bsum, nbw);
     hipLaunchKernelGGL(rl_scan_sums, dim3(n), dim3(MT_T), 0, s, bsum, nbw, n_ids);
     hipLaunchKernelGGL(rl_word_prefix, dim3(nbw, n), dim3(MT_T), 0, s, bits, Wd, bsum, nbw, prefix);
     hipLaunchKernelGGL(rl_relabel, mt_grid(n, P), dim3(MT_T), 0, s, map, P, max_id, bits, prefix, Wd, out);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("remap_label");
 }
 
 int hvn_label_areas(const int32_t *map, int n, int h, int w, int32_t max_label, int32_t *areas, void *stream)
 {
-    if (!map || !areas || !mt_shape_ok(n, h, w) || max_label < 0) return HVN_E_ARG;
+    if (!map || !areas) return hvn_fail(HVN_E_ARG, "label_areas: null pointer");
+    if (!mt_shape_ok(n, h, w)) return mt_bad_shape("label_areas", n, h);
+    if (max_label < 0) return hvn_fail(HVN_E_ARG, "label_areas: max_label %d < 0", max_label);
     hipStream_t s = (hipStream_t)stream;
     const long P = (long)h * w;
-    if (hipMemsetAsync(areas, 0, (size_t)n * ((size_t)max_label + 1) * 4, s) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemsetAsync(areas, 0, (size_t)n * ((size_t)max_label + 1) * 4, s) != hipSuccess) return hvn_fail(HVN_E_LAUNCH, "label_areas: hipMemsetAsync failed");
     hipLaunchKernelGGL(rl_areas, mt_grid(n, P), dim3(MT_T), 0, s, map, P, max_label, areas);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("label_areas");
 }
 
 int hvn_label_permute(int32_t *map, int n, int h, int w, int32_t max_label, const int32_t *perm, void *stream)
 {
-    if (!map || !perm || !mt_shape_ok(n, h, w) || max_label < 0) return HVN_E_ARG;
+    if (!map || !perm) return hvn_fail(HVN_E_ARG, "label_permute: null pointer");
+    if (!mt_shape_ok(n, h, w)) return mt_bad_shape("label_permute", n, h);
+    if (max_label < 0) return hvn_fail(HVN_E_ARG, "label_permute: max_label %d < 0", max_label);
     hipStream_t s = (hipStream_t)stream;
     const long P = (long)h * w;
     hipLaunchKernelGGL(rl_permute, mt_grid(n, P), dim3(MT_T), 0, s, map, P, max_label, perm);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("label_permute");
 }
 
 }  // extern "C"

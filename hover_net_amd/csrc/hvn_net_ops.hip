@@ -95,7 +95,7 @@ int hvn_launch_conv0(const Conv0Args &a, hipStream_t stream)
         hipLaunchKernelGGL(hvn_conv0_mfma<float>, grid, dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(hvn_conv0_mfma<uint8_t>, grid, dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -143,19 +143,19 @@ __global__ __launch_bounds__(256) void hvn_upadd_bf16(const UpAddArgs p, long to
 int hvn_launch_upadd(const UpAddArgs &a, hipStream_t stream)
 {
     if (a.bf16) {
-        if (a.C % 8) return -1;
+        if (a.C % 8) return HVN_E_ARG;
         const long total8 = (long)a.N * a.H * a.W * (a.C / 8);
         long blocks = (total8 + 255) / 256;
         if (blocks > 8192) blocks = 8192;
         hipLaunchKernelGGL(hvn_upadd_bf16, dim3((unsigned)blocks), dim3(256), 0, stream, a, total8);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
     }
-    if (a.C % 4) return -1;
+    if (a.C % 4) return HVN_E_ARG;
     const long total4 = (long)a.N * a.H * a.W * (a.C / 4);
     long blocks = (total4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(hvn_upadd, dim3((unsigned)blocks), dim3(256), 0, stream, a, total4);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -203,7 +203,7 @@ int hvn_launch_head(const HeadArgs &a, hipStream_t stream)
 {
     const long total = (long)a.N * a.H * a.W;
     hipLaunchKernelGGL(hvn_head, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -243,7 +243,7 @@ int hvn_launch_predmap(const PredMapArgs &a, hipStream_t stream)
 {
     const long total = (long)a.N * a.H * a.W;
     hipLaunchKernelGGL(hvn_predmap, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -338,8 +338,8 @@ int hvn_launch_wino_in(const WinoArgs &a, hipStream_t stream)
         const long total = (long)a.N * a.ty * a.tx * a.C;
         hipLaunchKernelGGL((hvn_wino_in<6, 5, 1>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
     } else
-        return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+        return HVN_E_ARG;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 template <int MO, int R, int VW>
@@ -413,8 +413,8 @@ int hvn_launch_wino_out(const WinoArgs &a, hipStream_t stream)
         const long total = (long)a.N * a.ty * a.tx * a.C;
         hipLaunchKernelGGL((hvn_wino_out<6, 5, 1>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
     } else
-        return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+        return HVN_E_ARG;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -454,5 +454,5 @@ int hvn_launch_extract_patches(const uint8_t *img, int H, int W, const int32_t *
     const long total = (long)P * win * win;
     hipLaunchKernelGGL(hvn_extract_patches_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, img, H, W, coords, win, pad_t, pad_l,
                        out, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

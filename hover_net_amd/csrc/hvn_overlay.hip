@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hvn.h"
+#include "hvn_error.h"   // include/hvn.h and hvn_fail
 
 #define OV_T 256
 #define OV_WAVES (OV_T / 64)
@@ -164,20 +164,24 @@ int hvn_draw_overlay(const uint8_t *image, uint8_t *overlay, int n, int h, int w
                      int slots, const uint8_t *rgba, const int32_t *centres, int thickness, int dot_radius, const uint8_t dot_rgb[3],
                      int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!image || !overlay || !offs || !rgba || !status || !dot_rgb || n <= 0 || h <= 0 || w <= 0 || slots <= 0 || n_pts < 0) return HVN_E_ARG;
-    if (n_pts > 0 && (!pts || ((uintptr_t)pts & 7))) return HVN_E_ARG;  // points are read as (x, y) pairs
-    if (((uintptr_t)image & 3) || ((uintptr_t)overlay & 3) || ((uintptr_t)rgba & 3) || ((uintptr_t)centres & 7)) return HVN_E_ARG;
-    if ((long)h * w >= (1L << 31) || (long)n * h * w >= (1L << 40)) return HVN_E_ARG;
-    if (thickness < 1 || thickness > 7 || dot_radius < 0 || dot_radius > 15) return HVN_E_SIZE;
+    if (!image || !overlay || !offs || !rgba || !status || !dot_rgb) return hvn_fail(HVN_E_ARG, "draw_overlay: null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || slots <= 0 || n_pts < 0) return hvn_fail(HVN_E_ARG, "draw_overlay: n, h, w or slots < 1, or n_pts < 0 (slots = %d)", slots);
+    if (n_pts > 0 && (!pts || ((uintptr_t)pts & 7))) return hvn_fail(HVN_E_ARG, "draw_overlay: pts NULL or not 8-byte aligned");  // points are read as (x, y) pairs
+    if (((uintptr_t)image & 3) || ((uintptr_t)overlay & 3) || ((uintptr_t)rgba & 3) || ((uintptr_t)centres & 7))
+        return hvn_fail(HVN_E_ARG, "draw_overlay: image, overlay and rgba must be 4-byte, centres 8-byte aligned");
+    if ((long)h * w >= (1L << 31) || (long)n * h * w >= (1L << 40)) return hvn_fail(HVN_E_ARG, "draw_overlay: h * w >= 2^31 or n * h * w >= 2^40 (h = %d)", h);
+    if (thickness < 1 || thickness > 7 || dot_radius < 0 || dot_radius > 15)
+        return hvn_fail(HVN_E_SIZE, "draw_overlay: thickness %d outside [1, 7] or dot_radius %d outside [0, 15]", thickness, dot_radius);
     const long M = (long)n * slots;
-    if (M >= (1L << 30) - 1) return HVN_E_SIZE;  // 2 * slot + 2 is an int32 key
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < hvn_overlay_workspace_bytes(n, h, w)) return HVN_E_SIZE;
+    if (M >= (1L << 30) - 1) return hvn_fail(HVN_E_SIZE, "draw_overlay: n * slots >= 2^30 - 1 (%ld slots)", M);  // 2 * slot + 2 is an int32 key
+    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < hvn_overlay_workspace_bytes(n, h, w))
+        return hvn_fail(HVN_E_SIZE, "draw_overlay: workspace NULL, not 16-byte aligned or smaller than hvn_overlay_workspace_bytes (%zu bytes given)", workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     int32_t *owner = (int32_t *)workspace;
     const long P = (long)n * h * w;
-    if (hipMemsetAsync(owner, 0, (size_t)P * sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
-    if (hipMemsetAsync(status, 0, 4 * sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
-    if (hipMemsetAsync(status + 1, 0xff, sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemsetAsync(owner, 0, (size_t)P * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status, 0, 4 * sizeof(int32_t), s) != hipSuccess ||
+        hipMemsetAsync(status + 1, 0xff, sizeof(int32_t), s) != hipSuccess)
+        return hvn_fail(HVN_E_LAUNCH, "draw_overlay: hipMemsetAsync failed");
     const int lo = -((thickness - 1) / 2), hi = thickness / 2;
     hipLaunchKernelGGL(ov_mark_contours, dim3((unsigned)((M + OV_WAVES - 1) / OV_WAVES)), dim3(OV_T), 0, s, (const int2 *)pts, n_pts, offs, slots,
                        M, rgba, h, w, lo, hi, owner, status);
@@ -189,7 +193,7 @@ int hvn_draw_overlay(const uint8_t *image, uint8_t *overlay, int n, int h, int w
     const long lanes = (P + OV_PX - 1) / OV_PX;
     hipLaunchKernelGGL(ov_paint, dim3((unsigned)((lanes + OV_T - 1) / OV_T)), dim3(OV_T), 0, s, image, overlay, P, (const int32_t *)owner, rgba,
                        uchar4{dot_rgb[0], dot_rgb[1], dot_rgb[2], 0});
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("draw_overlay");
 }
 
 }  // extern "C"

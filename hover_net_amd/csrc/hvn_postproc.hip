@@ -1323,17 +1323,17 @@ __global__ void pp_stat_init(TileStat *s, int n)
     for (int k = 0; k < 8; ++k) s[i].dbg[k] = 0;
 }
 
-static thread_local char pp_err[256] = "";
-const char *hvn_pp_last_error() { return pp_err; }
-
-static int postproc_impl(const float *pred, int n, int h, int w, int c, int c0, int32_t *inst, int32_t *tap_blb,
+// what: the entry point's name in a refusal's text
+static int postproc_impl(const char *what, const float *pred, int n, int h, int w, int c, int c0, int32_t *inst, int32_t *tap_blb,
                          double *tap_dist, int32_t *tap_marker, void *workspace, size_t workspace_bytes, hipStream_t s)
 {
-    if (!pred || !inst || n <= 0 || h <= 0 || w <= 0 || c0 < 0 || c0 + 3 > c) return HVN_E_ARG;
-    if ((long)h * w >= (1L << 31)) return HVN_E_ARG;
+    if (!pred || !inst) return hvn_fail(HVN_E_ARG, "%s: null pred or inst", what);
+    if (n <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1L << 31)) return hvn_fail(HVN_E_ARG, "%s: n, h or w < 1, or h * w >= 2^31 (h = %d)", what, h);
+    if (c0 < 0 || c0 + 3 > c) return hvn_fail(HVN_E_ARG, "%s: channels c0 .. c0 + 2 must lie in the map's %d (c0 = %d)", what, c, c0);
     PPBuf b;
     const size_t need = carve(b, (unsigned char *)workspace, n, h, w);
-    if (!workspace || workspace_bytes < need) return HVN_E_SIZE;
+    if (!workspace || workspace_bytes < need)
+        return hvn_fail(HVN_E_SIZE, "%s: workspace NULL or smaller than hvn_postproc_workspace_bytes (%zu of %zu bytes)", what, workspace_bytes, need);
     b.n = n; b.H = h; b.W = w; b.C = c; b.c0 = c0; b.P = (long)h * w;
     b.pred = pred; b.inst = inst;
     const dim3 grid((unsigned)((b.P + PP_T - 1) / PP_T), n), blk(PP_T);
@@ -1371,7 +1371,7 @@ static int postproc_impl(const float *pred, int n, int h, int w, int c, int c0, 
     if (maxc > 2048) maxc = 2048;
     static std::atomic<unsigned long long> ws_attr_c{0}, ws_attr_f{0};     // per device (hvn_kernels.h)
     if (hvn_max_lds_once((const void *)ws_component, WS_LDS_BYTES, ws_attr_c) || hvn_max_lds_once((const void *)ws_fallback, WS_LDS_BYTES, ws_attr_f))
-        return HVN_E_LAUNCH;
+        return hvn_fail(HVN_E_LAUNCH, "%s: the runtime refused the watershed kernels' LDS size", what);
     if (!ws_mode) {
         hipLaunchKernelGGL(ws_component, dim3((unsigned)maxc, n), dim3(64), WS_SMALL_LDS, s, b, 0, WS_SMALL_LDS);
         hipLaunchKernelGGL(ws_component, dim3((unsigned)maxc, n), dim3(64), WS_LDS_BYTES, s, b, 1, WS_LDS_BYTES);
@@ -1394,7 +1394,7 @@ static int postproc_impl(const float *pred, int n, int h, int w, int c, int c0, 
     const size_t NP = (size_t)n * b.P;
     if (tap_blb) hipMemcpyAsync(tap_blb, b.blb, NP * 4, hipMemcpyDeviceToDevice, s);
     if (tap_dist) hipMemcpyAsync(tap_dist, b.blur, NP * 8, hipMemcpyDeviceToDevice, s);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched(what);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1486,9 +1486,12 @@ int hvn_instance_table(const int32_t *inst, const float *pred, int n, int h, int
                        hvn_inst_rec *records, int32_t *counts, int max_inst, void *workspace, size_t workspace_bytes,
                        void *stream)
 {
-    if (!inst || !records || !counts || n <= 0 || h <= 0 || w <= 0 || max_inst <= 0 || nr_types < 0) return HVN_E_ARG;
-    if (nr_types > 0 && !pred) return HVN_E_ARG;
-    if (!workspace || workspace_bytes < hvn_instance_table_workspace_bytes(n, max_inst, nr_types)) return HVN_E_SIZE;
+    if (!inst || !records || !counts) return hvn_fail(HVN_E_ARG, "instance_table: null inst, records or counts");
+    if (n <= 0 || h <= 0 || w <= 0 || max_inst <= 0 || nr_types < 0)
+        return hvn_fail(HVN_E_ARG, "instance_table: n, h, w or max_inst < 1, or nr_types < 0 (max_inst = %d)", max_inst);
+    if (nr_types > 0 && !pred) return hvn_fail(HVN_E_ARG, "instance_table: nr_types > 0 needs pred");
+    if (!workspace || workspace_bytes < hvn_instance_table_workspace_bytes(n, max_inst, nr_types))
+        return hvn_fail(HVN_E_SIZE, "instance_table: workspace NULL or smaller than hvn_instance_table_workspace_bytes (%zu bytes given)", workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     InstAcc *acc = (InstAcc *)workspace;
     int32_t *hist = (int32_t *)((unsigned char *)workspace + align_up((size_t)n * max_inst * sizeof(InstAcc)));
@@ -1501,7 +1504,7 @@ int hvn_instance_table(const int32_t *inst, const float *pred, int n, int h, int
                        nr_types, acc, hist, max_inst);
     hipLaunchKernelGGL(it_finalize, dim3((max_inst + PP_T - 1) / PP_T, n), dim3(PP_T), 0, s, acc, hist, nr_types, max_inst,
                        records, counts);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("instance_table");
 }
 
 size_t hvn_postproc_workspace_bytes(int n, int h, int w)
@@ -1513,22 +1516,25 @@ size_t hvn_postproc_workspace_bytes(int n, int h, int w)
 int hvn_postproc(const float *pred, int n, int h, int w, int c, int c0, int32_t *inst, void *workspace,
                  size_t workspace_bytes, void *stream)
 {
-    return postproc_impl(pred, n, h, w, c, c0, inst, nullptr, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+    return postproc_impl("postproc", pred, n, h, w, c, c0, inst, nullptr, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int hvn_postproc_taps(const float *pred, int n, int h, int w, int c, int c0, int32_t *inst, int32_t *blb, double *dist,
                       int32_t *marker, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return postproc_impl(pred, n, h, w, c, c0, inst, blb, dist, marker, workspace, workspace_bytes, (hipStream_t)stream);
+    return postproc_impl("postproc_taps", pred, n, h, w, c, c0, inst, blb, dist, marker, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int hvn_postproc_stats(const void *workspace, size_t workspace_bytes, int n, int h, int w, long long out[10], void *stream)
 {
-    if (!workspace || !out || n <= 0 || h <= 0 || w <= 0) return HVN_E_ARG;
-    if (workspace_bytes < hvn_postproc_workspace_bytes(n, h, w)) return HVN_E_SIZE;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return HVN_E_LAUNCH;
+    if (!workspace || !out) return hvn_fail(HVN_E_ARG, "postproc_stats: null workspace or out");
+    if (n <= 0 || h <= 0 || w <= 0) return hvn_fail(HVN_E_ARG, "postproc_stats: n, h or w < 1 (h = %d)", h);
+    if (workspace_bytes < hvn_postproc_workspace_bytes(n, h, w))
+        return hvn_fail(HVN_E_SIZE, "postproc_stats: workspace smaller than hvn_postproc_workspace_bytes (%zu bytes given)", workspace_bytes);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return hvn_fail(HVN_E_LAUNCH, "postproc_stats: hipStreamSynchronize failed");
     std::vector<TileStat> hs(n);            // the per-map reduction slots lead the workspace (carve)
-    if (hipMemcpy(hs.data(), workspace, sizeof(TileStat) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return HVN_E_LAUNCH;
+    if (hipMemcpy(hs.data(), workspace, sizeof(TileStat) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return hvn_fail(HVN_E_LAUNCH, "postproc_stats: hipMemcpy of the per-map slots failed");
     for (int k = 0; k < 10; ++k) out[k] = 0;
     for (int i = 0; i < n; ++i) {
         out[0] += hs[i].n_comp;

@@ -137,12 +137,12 @@ int hvn_launch_resize_window(const uint8_t *src, int src_h, int src_w, int64_t s
                              int dst_h, int dst_w, hipStream_t stream)
 {
     const dim3 grid((unsigned)((dst_w + RS_TW - 1) / RS_TW), (unsigned)((dst_h + RS_TH - 1) / RS_TH));
-    if (grid.y > 65535u) return -4;
+    if (grid.y > 65535u) return HVN_E_SIZE;
     if (taps == 4)
         hipLaunchKernelGGL(rs_resize<4>, grid, dim3(RS_T), 0, stream, src, src_h, src_w, src_pitch, src_y0, src_x0, full_h, full_w, xofs, xcoef,
                            yofs, ycoef, dst, dst_h, dst_w);
     else
         hipLaunchKernelGGL(rs_resize<2>, grid, dim3(RS_T), 0, stream, src, src_h, src_w, src_pitch, src_y0, src_x0, full_h, full_w, xofs, xcoef,
                            yofs, ycoef, dst, dst_h, dst_w);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

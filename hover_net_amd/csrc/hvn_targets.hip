@@ -203,7 +203,7 @@ int hvn_launch_gen_targets(const int32_t *ann, int n, int h, int w, int ch, int 
                            hipStream_t stream)
 {
     TgBuf b;
-    if (tg_carve(b, (unsigned char *)ws, n, h, w) > ws_bytes) return -4;
+    if (tg_carve(b, (unsigned char *)ws, n, h, w) > ws_bytes) return HVN_E_SIZE;
     b.ann = ann; b.hv = hv; b.np_map = np_map;
     b.N = n; b.H = h; b.W = w; b.CH = ch; b.CW = cw;
     b.h0 = (int)((h - ch) * 0.5); b.w0 = (int)((w - cw) * 0.5);   // cropping_center
@@ -216,5 +216,5 @@ int hvn_launch_gen_targets(const int32_t *ann, int n, int h, int w, int ch, int 
     hipLaunchKernelGGL(tg_extrema, grid, dim3(TG_T), 0, stream, b);
     const dim3 cgrid((unsigned)(((long)ch * cw + TG_T - 1) / TG_T), (unsigned)n);
     hipLaunchKernelGGL(tg_write, cgrid, dim3(TG_T), 0, stream, b);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

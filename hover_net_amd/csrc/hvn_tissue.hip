@@ -247,7 +247,7 @@ size_t hvn_tissue_workspace_bytes(int h, int w)
 int hvn_launch_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray, uint32_t *hist256, hipStream_t s)
 {
     const long P = (long)h * w;
-    if (hipMemsetAsync(hist256, 0, 256 * sizeof(uint32_t), s) != hipSuccess) return -2;
+    if (hipMemsetAsync(hist256, 0, 256 * sizeof(uint32_t), s) != hipSuccess) return HVN_E_LAUNCH;
     const bool vec = (((uintptr_t)rgb | (uintptr_t)gray) & 3) == 0;
     const long items = vec ? (P >> 2) + 3 : P;
     long blocks = (items + TM_T - 1) / TM_T;
@@ -256,7 +256,7 @@ int hvn_launch_tissue_gray_hist(const uint8_t *rgb, int h, int w, uint8_t *gray,
         hipLaunchKernelGGL(tm_gray_hist<1>, dim3((unsigned)blocks), dim3(TM_T), 0, s, rgb, P, gray, hist256);
     else
         hipLaunchKernelGGL(tm_gray_hist<0>, dim3((unsigned)blocks), dim3(TM_T), 0, s, rgb, P, gray, hist256);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int min_obj, int max_hole, int radius, uint8_t *mask,
@@ -273,7 +273,7 @@ int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int
     const dim3 per_pixel((unsigned)((P + TM_T - 1) / TM_T)), per_row((unsigned)((h + TM_T / 64 - 1) / (TM_T / 64))), block(TM_T);
 
     for (int pass = 0; pass < 2; ++pass) {  // 0: objects of the thresholded grey plane; 1: holes = objects of the complement
-        if (hipMemsetAsync(cnt, 0, (size_t)P * sizeof(int32_t), s) != hipSuccess) return -2;
+        if (hipMemsetAsync(cnt, 0, (size_t)P * sizeof(int32_t), s) != hipSuccess) return HVN_E_LAUNCH;
         hipLaunchKernelGGL(tm_ccl_init, per_row, block, 0, s, pass ? obj : gray, h, w, pass, threshold, par);
         hipLaunchKernelGGL(tm_ccl_merge, per_pixel, block, 0, s, par, h, w, pass ? 0 : 1);
         hipLaunchKernelGGL(tm_ccl_count, per_pixel, block, 0, s, par, cnt, P);
@@ -282,5 +282,5 @@ int hvn_launch_tissue_mask(const uint8_t *gray, int h, int w, int threshold, int
     hipLaunchKernelGGL(tm_hdist, per_row, block, 0, s, hol, h, w, radius, dist);
     const int tiles_x = (w + TM_TW - 1) / TM_TW, tiles_y = (h + TM_TH - 1) / TM_TH;
     hipLaunchKernelGGL(tm_vdilate, dim3((unsigned)((long)tiles_x * tiles_y)), block, 0, s, dist, h, w, radius, tiles_x, mask);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

@@ -21,7 +21,7 @@
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-static inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -2; }
+static inline int launch_ok() { return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH; }
 
 // =========================================================================================
 // weight packing
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void hvn_pack_w_multi(const PackArgs *tbl, con
 
 int hvn_launch_pack_w_multi(const PackArgs *tbl, const int *first_block, int n, long blocks, hipStream_t stream)
 {
-    if (!tbl || !first_block || n <= 0 || blocks <= 0 || blocks > 0x7fffffffL) return -1;
+    if (!tbl || !first_block || n <= 0 || blocks <= 0 || blocks > 0x7fffffffL) return HVN_E_ARG;
     hipLaunchKernelGGL(hvn_pack_w_multi, dim3((unsigned)blocks), dim3(256), 0, stream, tbl, first_block, n);
     return launch_ok();
 }
@@ -159,7 +159,7 @@ int hvn_launch_pack_w(const PackArgs &a, hipStream_t stream)
 {
     long total;
     if (a.mode == 3 || a.mode == 4) {
-        if (a.groups != 1 || a.taps != 25 || !a.gmat) return -1;
+        if (a.groups != 1 || a.taps != 25 || !a.gmat) return HVN_E_ARG;
         total = (long)a.lead_pad * (a.mode == 3 ? a.cin_g : a.cout);
         hipLaunchKernelGGL(hvn_pack_wino, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
         return launch_ok();
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256) void hvn_reduce_parts(float *__restrict__ dst,
 
 int hvn_launch_reduce_parts(float *dst, const float *part, long elems, long nparts, long stride, hipStream_t stream)
 {
-    if (!dst || !part || elems <= 0 || nparts <= 0 || (elems + 63) / 64 >= (1L << 31)) return -1;
+    if (!dst || !part || elems <= 0 || nparts <= 0 || (elems + 63) / 64 >= (1L << 31)) return HVN_E_ARG;
     hipLaunchKernelGGL(hvn_reduce_parts, dim3((unsigned)((elems + 63) / 64)), dim3(256), 0, stream, dst, part, elems, nparts, stride);
     return launch_ok();
 }
@@ -459,21 +459,21 @@ static int launch_wgrad(WgradArgs a, hipStream_t stream)
     const long ksplit = hvn_wgrad_split(a, tiles, &a.rows_per_split);
     const long elems = wgrad_elems(a);
     if (a.part && ksplit > 1) {
-        if (ksplit * elems > a.part_cap) return -4;
+        if (ksplit * elems > a.part_cap) return HVN_E_SIZE;
         a.part_stride = elems;
     } else
         a.part = nullptr;       // a single split: one writer per element, 0 + x in any order
     auto k = hvn_conv_wgrad_f32<BM, BN, WAVES_M, WAVES_N>;
     static std::atomic<unsigned long long> attr{0};
-    if (hvn_max_lds_once(reinterpret_cast<const void *>(k), (int)lds, attr)) return -2;
+    if (hvn_max_lds_once(reinterpret_cast<const void *>(k), (int)lds, attr)) return HVN_E_LAUNCH;
     hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)ksplit, (unsigned)nb), dim3(256), lds, stream, a);
-    if (launch_ok()) return -2;
-    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, elems, ksplit, elems, stream) : 0;
+    if (launch_ok()) return HVN_E_LAUNCH;
+    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, elems, ksplit, elems, stream) : HVN_OK;
 }
 
 int hvn_launch_wgrad(const WgradArgs &a, hipStream_t stream)
 {
-    if (a.Cin % 32 || a.Cout % 32 || a.groups < 1 || a.Cin_g * a.groups != a.Cin) return -1;
+    if (a.Cin % 32 || a.Cout % 32 || a.groups < 1 || a.Cin_g * a.groups != a.Cin) return HVN_E_ARG;
     int bm, bn;
     wgrad_tile_shape(a, &bm, &bn);
     if (bm == 128 && bn == 128) return launch_wgrad<128, 128, 2, 2>(a, stream);
@@ -482,7 +482,7 @@ int hvn_launch_wgrad(const WgradArgs &a, hipStream_t stream)
     if (bm == 64 && bn == 128) return launch_wgrad<64, 128, 1, 4>(a, stream);
     if (bm == 64 && bn == 64) return launch_wgrad<64, 64, 2, 2>(a, stream);
     if (bm == 32 && bn == 128) return launch_wgrad<32, 128, 1, 4>(a, stream);
-    return -1;   // (64|32) x (64|32)-only channel counts do not occur in this network
+    return HVN_E_ARG;   // (64|32) x (64|32)-only channel counts do not occur in this network
 }
 
 
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void hvn_wino_dy(const WinoArgs p, long total)
 
 int hvn_launch_wino_dy(const WinoArgs &a, hipStream_t stream)
 {
-    if (a.C % 2) return -1;
+    if (a.C % 2) return HVN_E_ARG;
     const long total = (long)a.N * a.ty * a.tx * (a.C / 2);
     hipLaunchKernelGGL(hvn_wino_dy<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, total);
     return launch_ok();
@@ -797,7 +797,7 @@ static void bn_grid(BnArgs &a, dim3 &grid)
 
 int hvn_launch_bn_forward(BnArgs a, hipStream_t stream)
 {
-    if (a.C % 4 || (long)a.N * a.H * a.W * (a.C / 4) >= (1L << 31)) return -1;
+    if (a.C % 4 || (long)a.N * a.H * a.W * (a.C / 4) >= (1L << 31)) return HVN_E_ARG;
     dim3 grid;
     bn_grid(a, grid);
     hipLaunchKernelGGL(hvn_bn_reduce<0>, grid, dim3(256), 0, stream, a);
@@ -811,7 +811,7 @@ int hvn_launch_bn_forward(BnArgs a, hipStream_t stream)
 
 int hvn_launch_bn_backward(BnArgs a, hipStream_t stream)
 {
-    if (a.C % 4 || (long)a.N * a.H * a.W * (a.C / 4) >= (1L << 31)) return -1;
+    if (a.C % 4 || (long)a.N * a.H * a.W * (a.C / 4) >= (1L << 31)) return HVN_E_ARG;
     dim3 grid;
     bn_grid(a, grid);
     hipLaunchKernelGGL(hvn_bn_reduce<1>, grid, dim3(256), 0, stream, a);
@@ -862,9 +862,9 @@ __global__ __launch_bounds__(256) void hvn_upadd_bwd(const UpAddBwdArgs p, long 
 
 int hvn_launch_upadd_bwd(const UpAddBwdArgs &a, hipStream_t stream)
 {
-    if (a.C % 4 || a.H % 2 || a.W % 2) return -1;
+    if (a.C % 4 || a.H % 2 || a.W % 2) return HVN_E_ARG;
     const long total = (long)a.N * (a.H / 2) * (a.W / 2) * (a.C / 4);
-    if (total >= (1L << 31)) return -1;
+    if (total >= (1L << 31)) return HVN_E_ARG;
     long blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(hvn_upadd_bwd, dim3((unsigned)blocks), dim3(256), 0, stream, a, total);
@@ -956,15 +956,15 @@ long hvn_head_bwd_part_floats(const HeadBwdArgs &a) { return head_bwd_wgs(a) * (
 
 int hvn_launch_head_bwd(const HeadBwdArgs &a, hipStream_t stream)
 {
-    if (a.Cout < 1 || a.Cout > 16) return -1;
+    if (a.Cout < 1 || a.Cout > 16) return HVN_E_ARG;
     const long total = (long)a.N * a.H * a.W;
     const long wgs = head_bwd_wgs(a);
     const int nv = a.Cout * 64 + a.Cout;
-    if (a.part && wgs * nv > a.part_cap) return -4;
+    if (a.part && wgs * nv > a.part_cap) return HVN_E_SIZE;
     hipLaunchKernelGGL(hvn_head_bwd, dim3((unsigned)wgs), dim3(256), 0, stream, a, total);
-    if (launch_ok()) return -2;
-    if (!a.part) return 0;
-    if (hvn_launch_reduce_parts(a.dw, a.part, (long)a.Cout * 64, wgs, nv, stream)) return -2;
+    if (launch_ok()) return HVN_E_LAUNCH;
+    if (!a.part) return HVN_OK;
+    if (hvn_launch_reduce_parts(a.dw, a.part, (long)a.Cout * 64, wgs, nv, stream)) return HVN_E_LAUNCH;
     return hvn_launch_reduce_parts(a.db, a.part + (long)a.Cout * 64, a.Cout, wgs, nv, stream);
 }
 
@@ -1088,13 +1088,13 @@ int hvn_launch_conv0_wgrad(const Conv0WgradArgs &a, hipStream_t stream)
     const int tx = (a.Wo + W0_T - 1) / W0_T, ty = (a.Ho + W0_T - 1) / W0_T;
     const long total = (long)tx * ty * a.N;
     const long blocks = conv0_wgrad_wgs(a);
-    if (a.part && blocks * 64 * 147 > a.part_cap) return -4;
+    if (a.part && blocks * 64 * 147 > a.part_cap) return HVN_E_SIZE;
     const size_t lds = (size_t)(W0_P * W0M_PITCH + 64 * 160) * sizeof(float);
     static std::atomic<unsigned long long> attr{0};
-    if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv0_wgrad_mfma), (int)lds, attr)) return -2;
+    if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv0_wgrad_mfma), (int)lds, attr)) return HVN_E_LAUNCH;
     hipLaunchKernelGGL(hvn_conv0_wgrad_mfma, dim3((unsigned)blocks), dim3(256), lds, stream, a, tx, ty, total);
-    if (launch_ok()) return -2;
-    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, 64 * 147, blocks, 64 * 147, stream) : 0;
+    if (launch_ok()) return HVN_E_LAUNCH;
+    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, 64 * 147, blocks, 64 * 147, stream) : HVN_OK;
 }
 
 // =========================================================================================
@@ -1337,14 +1337,14 @@ __global__ __launch_bounds__(256) void hvn_loss_grad(const LossArgs p, long tota
 
 int hvn_launch_loss(const LossArgs &a, int stage, hipStream_t stream)
 {
-    if (a.T < 0 || a.T > 16) return -1;
+    if (a.T < 0 || a.T > 16) return HVN_E_ARG;
     const long total = (long)a.N * a.H * a.W;
     if (stage == 0) {
         const long rows = (total + 255) / 256;
-        if (a.parts && rows * 64 > a.parts_cap) return -4;
+        if (a.parts && rows * 64 > a.parts_cap) return HVN_E_SIZE;
         hipLaunchKernelGGL(hvn_loss_partial, dim3((unsigned)rows), dim3(256), 0, stream, a, total);
         if (a.parts) {
-            if (launch_ok()) return -2;
+            if (launch_ok()) return HVN_E_LAUNCH;
             hipLaunchKernelGGL(hvn_loss_finalize, dim3(1), dim3(1024), 0, stream, (const double *)a.parts, rows, a.sums);
         }
     } else

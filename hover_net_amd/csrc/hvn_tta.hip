@@ -22,7 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// the VIEW kernel below is called hvn_view, which include/hvn.h (reached through hvn_kernels.h for the status names) gives to a struct
+// that this file does not use: the struct goes by another name here, so that the kernel keeps its symbol
+#define hvn_view hvn_view_desc
 #include "hvn_kernels.h"
+#undef hvn_view
 
 #define VW_TILE 32
 #define VW_ROW 100      // bytes per LDS row: 96 of pixels + 4 of padding
@@ -87,7 +91,7 @@ int hvn_launch_view(const ViewArgs &a, hipStream_t stream)
     const int Ho = (a.k & 1) ? a.W : a.H, Wo = (a.k & 1) ? a.H : a.W;
     const dim3 grid((unsigned)((Wo + VW_TILE - 1) / VW_TILE), (unsigned)((Ho + VW_TILE - 1) / VW_TILE), (unsigned)a.N);
     hipLaunchKernelGGL(hvn_view, grid, dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -166,5 +170,5 @@ int hvn_launch_tta(const TtaArgs &a, hipStream_t stream)
 {
     const dim3 grid((unsigned)((a.W + 15) / 16), (unsigned)((a.H + 15) / 16), (unsigned)a.N);
     hipLaunchKernelGGL(hvn_tta, grid, dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

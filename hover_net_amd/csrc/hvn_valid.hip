@@ -160,7 +160,7 @@ size_t hvn_valid_ws_bytes(long P)
 int hvn_launch_valid_stats(const float *pred, const int32_t *np_map, const float *hv_map, const int32_t *tp_map, long P, int c, int nr_types,
                            long long *counts, double *hv_sse, void *ws, size_t ws_bytes, hipStream_t stream)
 {
-    if (ws_bytes < hvn_valid_ws_bytes(P)) return -4;
+    if (ws_bytes < hvn_valid_ws_bytes(P)) return HVN_E_SIZE;
     const long rows = vs_blocks(P);
     double *part_sse = (double *)ws;
     unsigned *part_cnt = (unsigned *)((unsigned char *)ws + vs_align((size_t)rows * sizeof(double)));
@@ -169,8 +169,8 @@ int hvn_launch_valid_stats(const float *pred, const int32_t *np_map, const float
     else
         hipLaunchKernelGGL(vs_partial<4>, dim3((unsigned)rows), dim3(VS_T), 0, stream, pred, np_map, hv_map, tp_map, P, nr_types, part_sse,
                            part_cnt);
-    if (hipGetLastError() != hipSuccess) return -2;
+    if (hipGetLastError() != hipSuccess) return HVN_E_LAUNCH;
     hipLaunchKernelGGL(vs_finalize, dim3(1), dim3(VS_T), 0, stream, (const double *)part_sse, (const unsigned *)part_cnt, rows, P,
                        c == 3 ? 0 : nr_types, counts, hv_sse);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

@@ -115,5 +115,5 @@ int hvn_launch_viz_strip(const uint8_t *img, int n, int ih, int iw, const float 
     const long P = 2L * h * a.ncol * w;
     const long items = (P >> 2) + 1;                              // groups of four pixels, and the item of the scalar ends
     hipLaunchKernelGGL(vz_strip, dim3((unsigned)((items + VZ_T - 1) / VZ_T), (unsigned)n_sel), dim3(VZ_T), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
 }

@@ -208,7 +208,7 @@ int hvn_wgrad_x3_supported(const WgradArgs &a)
 
 int hvn_launch_wgrad_x3(WgradArgs a, int terms, hipStream_t stream)
 {
-    if (!hvn_wgrad_x3_supported(a) || (terms != 6 && terms != 9)) return -1;
+    if (!hvn_wgrad_x3_supported(a) || (terms != 6 && terms != 9)) return HVN_E_ARG;
     const size_t lds = 2 * WX_OPER;
     a.tiles_m = (a.Cout + 127) / 128;
     a.tiles_n = a.Cin / 128;
@@ -218,18 +218,18 @@ int hvn_launch_wgrad_x3(WgradArgs a, int terms, hipStream_t stream)
     const long ksplit = hvn_wgrad_split(a, tiles, &a.rows_per_split);
     const long elems = a.nbatch > 1 ? (long)a.nbatch * a.wb : (long)a.Cout * a.KH * a.KW * a.Cin_g;
     if (a.part && ksplit > 1) {
-        if (ksplit * elems > a.part_cap) return -4;
+        if (ksplit * elems > a.part_cap) return HVN_E_SIZE;
         a.part_stride = elems;
     } else
         a.part = nullptr;       // a single split: one writer per element
     static std::atomic<unsigned long long> attr6{0}, attr9{0};
     if (terms == 6) {
-        if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv_wgrad_x3<6>), (int)lds, attr6)) return -2;
+        if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv_wgrad_x3<6>), (int)lds, attr6)) return HVN_E_LAUNCH;
         hipLaunchKernelGGL(hvn_conv_wgrad_x3<6>, dim3((unsigned)tiles, (unsigned)ksplit, (unsigned)nb), dim3(256), lds, stream, a);
     } else {
-        if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv_wgrad_x3<9>), (int)lds, attr9)) return -2;
+        if (hvn_max_lds_once(reinterpret_cast<const void *>(hvn_conv_wgrad_x3<9>), (int)lds, attr9)) return HVN_E_LAUNCH;
         hipLaunchKernelGGL(hvn_conv_wgrad_x3<9>, dim3((unsigned)tiles, (unsigned)ksplit, (unsigned)nb), dim3(256), lds, stream, a);
     }
-    if (hipGetLastError() != hipSuccess) return -2;
-    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, elems, ksplit, elems, stream) : 0;
+    if (hipGetLastError() != hipSuccess) return HVN_E_LAUNCH;
+    return a.part ? hvn_launch_reduce_parts(a.dw, a.part, elems, ksplit, elems, stream) : HVN_OK;
 }

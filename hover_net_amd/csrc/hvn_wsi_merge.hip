@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hvn.h"
+#include "hvn_error.h"   // include/hvn.h and hvn_fail
 
 #define MG_T 256
 
@@ -131,19 +131,21 @@ extern "C" {
 
 int hvn_wsi_merge_normal(int32_t *inst_map, int64_t map_w, int y0, int x0, int h, int w, const int32_t *pred_inst, int32_t off, void *stream)
 {
-    if (!inst_map || !pred_inst || h <= 0 || w <= 0 || map_w < x0 + w || y0 < 0 || x0 < 0) return HVN_E_ARG;
+    if (!inst_map || !pred_inst) return hvn_fail(HVN_E_ARG, "wsi_merge_normal: null pointer");
+    if (h <= 0 || w <= 0 || map_w < x0 + w || y0 < 0 || x0 < 0) return hvn_fail(HVN_E_ARG, "wsi_merge_normal: the %d x %d tile at (%d, %d) is empty or leaves the map", h, w, y0, x0);
     const long n = (long)h * w;
     hipLaunchKernelGGL(mg_normal, dim3((unsigned)((n + MG_T - 1) / MG_T)), dim3(MG_T), 0, (hipStream_t)stream, inst_map, (long)map_w, y0, x0, h, w, pred_inst, off);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("wsi_merge_normal");
 }
 
 int hvn_wsi_merge_fixing(int32_t *inst_map, int64_t map_w, int y0, int x0, int h, int w, const int32_t *pred_inst, int32_t n_local,
                          int32_t off, int32_t epoch, int32_t *id_flags, int64_t cap, int32_t *removed, int32_t removed_cap,
                          int32_t *counters, uint8_t *touching, void *stream)
 {
-    if (!inst_map || !pred_inst || !id_flags || !removed || !counters || !touching || h <= 0 || w <= 0 || map_w < x0 + w || y0 < 0 || x0 < 0 ||
-        n_local < 0 || cap <= 0 || removed_cap <= 0 || epoch <= 0)
-        return HVN_E_ARG;
+    if (!inst_map || !pred_inst || !id_flags || !removed || !counters || !touching) return hvn_fail(HVN_E_ARG, "wsi_merge_fixing: null pointer");
+    if (h <= 0 || w <= 0 || map_w < x0 + w || y0 < 0 || x0 < 0) return hvn_fail(HVN_E_ARG, "wsi_merge_fixing: the %d x %d tile at (%d, %d) is empty or leaves the map", h, w, y0, x0);
+    if (n_local < 0 || cap <= 0 || removed_cap <= 0 || epoch <= 0)
+        return hvn_fail(HVN_E_ARG, "wsi_merge_fixing: n_local < 0, or cap, removed_cap or epoch < 1 (epoch = %d)", epoch);
     MergeArgs a;
     a.map = inst_map; a.map_w = (long)map_w; a.y0 = y0; a.x0 = x0; a.h = h; a.w = w; a.pred = pred_inst; a.off = off; a.epoch = epoch;
     a.edge_flag = id_flags; a.rem_flag = id_flags + cap; a.cap = (long)cap; a.removed = removed; a.removed_cap = removed_cap;
@@ -156,7 +158,7 @@ int hvn_wsi_merge_fixing(int32_t *inst_map, int64_t map_w, int y0, int x0, int h
     hipLaunchKernelGGL(mg_remove, grid, blk, 0, s, a);
     hipLaunchKernelGGL(mg_touch, grid, blk, 0, s, a);
     hipLaunchKernelGGL(mg_write, grid, blk, 0, s, a);
-    return hipGetLastError() == hipSuccess ? HVN_OK : HVN_E_LAUNCH;
+    return hvn_launched("wsi_merge_fixing");
 }
 
 }  // extern "C"

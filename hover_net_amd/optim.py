@@ -13,11 +13,6 @@ import torch
 from . import lib as L
 
 
-def _check(rc):
-    if rc != 0:   # the training entry points report through hvn_train_last_error
-        raise L.HvnError("hvn_adam_step failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
-
-
 def _bump(params):
     """The kernel writes the weights through raw pointers, behind torch's version counters; bump one so that anything keyed
     on `p._version` (HoVerNet._weights_version hashes every parameter's version -> the cached inference plan) sees the
@@ -53,7 +48,6 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        lib = L.lib()
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             st = self.state.setdefault("group%d" % gi, {})
@@ -68,9 +62,8 @@ class FusedAdam(torch.optim.Optimizer):
                 if "m" not in st or st["m"].numel() != n + 4:
                     st["m"] = torch.zeros(n + 4, dtype=torch.float32, device=dev)
                     st["v"] = torch.zeros(n + 4, dtype=torch.float32, device=dev)
-                rc = lib.hvn_adam_step(ws + 4 * lo, gs + 4 * lo, st["m"].data_ptr(), st["v"].data_ptr(), n, group["lr"], b1, b2,
-                                       group["eps"], st["step"], stream)
-                _check(rc)
+                L.call("hvn_adam_step", ws + 4 * lo, gs + 4 * lo, st["m"].data_ptr(), st["v"].data_ptr(), n, group["lr"], b1, b2,
+                       group["eps"], st["step"], stream)
                 self.fused_launches += 1
                 _bump(group["params"])
                 continue
@@ -82,9 +75,8 @@ class FusedAdam(torch.optim.Optimizer):
                 ps = self.state.setdefault(p, {})
                 if "m" not in ps:
                     ps["m"], ps["v"] = torch.zeros_like(p.data), torch.zeros_like(p.data)
-                rc = lib.hvn_adam_step(p.data_ptr(), p.grad.data_ptr(), ps["m"].data_ptr(), ps["v"].data_ptr(), p.numel(), group["lr"], b1, b2,
-                                       group["eps"], st["step"], stream)
-                _check(rc)
+                L.call("hvn_adam_step", p.data_ptr(), p.grad.data_ptr(), ps["m"].data_ptr(), ps["v"].data_ptr(), p.numel(), group["lr"], b1, b2,
+                       group["eps"], st["step"], stream)
                 self.fallback_launches += 1
                 _bump([p])
         return loss

@@ -193,13 +193,11 @@ def _launch(store, prm, out_hw, status=None, **declared):
     oimg = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
     oann = torch.empty((n, oh, ow, store.c), dtype=torch.int32, device=dev)
     status = store.status if status is None else status
-    rc = L.lib().hvn_augment_shape_images(store.pixels.data_ptr(), store.ann.data_ptr(), store.image_dev.data_ptr(), store.patch_dev.data_ptr(),
-                                          int(declared.get("n_images", store.n_images)), int(declared.get("n_patches", store.n_patches)),
-                                          int(declared.get("total_pixels", store.total_pixels)),
-                                          store.win[0], store.win[1], store.c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
-                                          status.data_ptr(), L.stream_ptr(dev))
-    if rc:
-        raise L.HvnError("hvn_augment_shape_images failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
+    L.call("hvn_augment_shape_images", store.pixels.data_ptr(), store.ann.data_ptr(), store.image_dev.data_ptr(), store.patch_dev.data_ptr(),
+           int(declared.get("n_images", store.n_images)), int(declared.get("n_patches", store.n_patches)),
+           int(declared.get("total_pixels", store.total_pixels)),
+           store.win[0], store.win[1], store.c, prm_dev.data_ptr(), n, oh, ow, oimg.data_ptr(), oann.data_ptr(),
+           status.data_ptr(), L.stream_ptr(dev))
     return oimg, oann
 
 

@@ -22,10 +22,8 @@ def gen_targets_device(ann_dev, crop_shape):
     _WS[key] = L.grown(_WS.get(key), L.lib().hvn_gen_targets_workspace_bytes(n, h, w), ann_dev.device)
     hv = torch.empty((n, ch, cw, 2), dtype=torch.float32, device=ann_dev.device)
     npm = torch.empty((n, ch, cw), dtype=torch.int32, device=ann_dev.device)
-    rc = L.lib().hvn_gen_targets(ann_dev.data_ptr(), n, h, w, ch, cw, hv.data_ptr(), npm.data_ptr(), _WS[key].data_ptr(), _WS[key].numel(),
-                                 L.stream_ptr(ann_dev.device))
-    if rc:
-        raise L.HvnError("hvn_gen_targets failed (%d): %s" % (rc, L.lib().hvn_train_last_error().decode()))
+    L.call("hvn_gen_targets", ann_dev.data_ptr(), n, h, w, ch, cw, hv.data_ptr(), npm.data_ptr(), _WS[key].data_ptr(), _WS[key].numel(),
+           L.stream_ptr(ann_dev.device))
     return {"hv_map": hv, "np_map": npm}
 
 

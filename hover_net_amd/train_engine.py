@@ -614,9 +614,7 @@ class TrainEngine:
         base = ctypes.addressof(self.bwd_ops)
 
         def run_top(i):
-            rc = lib.hvn_run_train_plan(base + i * tsz, 1, self.n, stream)
-            if rc:
-                raise L.HvnError("hvn_run_train_plan (autotune) failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
+            L.check(lib.hvn_run_train_plan(base + i * tsz, 1, self.n, stream), "hvn_run_train_plan (autotune)")
 
         for i in range(len(self.bwd_ops)):
             t = self.bwd_ops[i]
@@ -733,8 +731,7 @@ class TrainEngine:
             rc = lib.hvn_run_train_plan_ws(ops_addr, n_ops, self.n, self._stream(), ws.data_ptr(), 4 * ws.numel())
         else:
             rc = lib.hvn_run_train_plan(ops_addr, n_ops, self.n, self._stream())
-        if rc:
-            raise L.HvnError("hvn_run_train_plan(%s) failed (%d): %s" % (what, rc, lib.hvn_train_last_error().decode()))
+        L.check(rc, "hvn_run_train_plan(%s)" % what)
 
     def _run_section(self, ops, a, b, what, scr=0):
         """Launches [a, b) of a lowered list on the current stream, its floating weight gradients (`_floats`, backward list only) on the
@@ -807,12 +804,9 @@ class TrainEngine:
 
     def loss_forward(self):
         """Zero the gradient memory, run loss stage 1 -> this rank's partial sums (device float64 [64])."""
-        lib = L.lib()
         self._gzero.zero_()
         self.sums.zero_()
-        rc = lib.hvn_loss_forward(ctypes.byref(self._loss), self._stream())
-        if rc:
-            raise L.HvnError("hvn_loss_forward failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
+        L.call("hvn_loss_forward", ctypes.byref(self._loss), self._stream())
         return self.sums
 
     def backward(self, world=1, all_reduce=None):
@@ -820,12 +814,9 @@ class TrainEngine:
         `all_reduce(tensor, async_op)` (data-parallel training) the gradient slab is reduced in two buckets: the
         decoder's (the tail of the slab, complete once the decoder branches' backward ops have run) is launched
         asynchronously and overlaps the encoder's backward pass, the encoder's follows at the end."""
-        lib = L.lib()
         s = self._stream()
         self._loss.total_pixels = float(world * self.n * self._loss.h * self._loss.w)
-        rc = lib.hvn_loss_backward(ctypes.byref(self._loss), s)
-        if rc:
-            raise L.HvnError("hvn_loss_backward failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
+        L.call("hvn_loss_backward", ctypes.byref(self._loss), s)
         n = len(self.bwd_ops)
 
         def run(lo, hi):

@@ -23,14 +23,11 @@ MAX_TYPES = 16      # the kernel's cap on nr_types
 def launch(pred, np_map, hv_map, tp_map, shape, nr_types, counts, hv_sse, workspace):
     """`hvn_valid_stats` (include/hvn.h) on device tensors, on the current stream of `counts`' device: adds the batch of
     `shape` = (n, h, w, c) to `counts` / `hv_sse`.  No sync.  Whatever the library refuses raises HvnError with the state untouched."""
-    lib = L.lib()
     n, h, w, c = (int(v) for v in shape)
     with torch.cuda.device(counts.device):
-        rc = lib.hvn_valid_stats(pred.data_ptr(), np_map.data_ptr(), hv_map.data_ptr(), None if tp_map is None else tp_map.data_ptr(), n, h, w, c,
-                                 int(nr_types), counts.data_ptr(), hv_sse.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                 L.stream_ptr(counts.device))
-    if rc != 0:
-        raise L.HvnError("hvn_valid_stats failed (%d): %s" % (rc, lib.hvn_train_last_error().decode()))
+        L.call("hvn_valid_stats", pred.data_ptr(), np_map.data_ptr(), hv_map.data_ptr(), None if tp_map is None else tp_map.data_ptr(), n, h, w, c,
+               int(nr_types), counts.data_ptr(), hv_sse.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+               L.stream_ptr(counts.device))
 
 
 class ValidStats:

@@ -24,10 +24,10 @@ extern "C" {
 typedef enum hvn_status {
     HVN_OK = 0,
     HVN_E_ARG = -1,      /* malformed descriptor (alignment, channel multiple, kind) */
-    HVN_E_LAUNCH = -2,   /* hipLaunch / hipGetLastError failure (hvn_last_error() has the text) */
+    HVN_E_LAUNCH = -2,   /* hipLaunch / hipGetLastError failure */
     HVN_E_NOGPU = -3,    /* no gfx950 device visible */
     HVN_E_SIZE = -4      /* workspace too small */
-} hvn_status;
+} hvn_status;            /* every nonzero status comes with a text: hvn_last_error() */
 
 /* Strided view: element (n,y,x,c) lives at base[n*sn + y*sy + x*sx + c*sc].  Every kernel but
  * CONV0 requires channels-last (sc = 1; 0 is read as 1). */
@@ -125,6 +125,9 @@ typedef struct hvn_op {
 /* -- library ---------------------------------------------------------------------- */
 HVN_API int         hvn_version(void);
 HVN_API const char *hvn_build_id(void);   /* id of the sources the binary was compiled from; the Python binding refuses a stale library */
+/* Text of the most recent call on this thread that returned a nonzero status, whichever entry point it was; it leads with that entry
+ * point's name without hvn_ ("postproc: ..."; an op of a plan: "train op 7: wgrad: ...").  Every failing path writes it, so it never
+ * repeats an earlier failure; a successful call leaves it alone. */
 HVN_API const char *hvn_last_error(void);
 HVN_API int         hvn_device_ok(void);  /* 1 if a gfx950 device is current */
 
@@ -409,7 +412,7 @@ HVN_API int hvn_run_train_plan(const hvn_top *ops, int n_ops, int batch, void *s
  * batch) bytes (HVN_E_SIZE otherwise), shared by all ops of the list (they run in stream order); NULL = hvn_run_train_plan. */
 HVN_API int hvn_run_train_plan_ws(const hvn_top *ops, int n_ops, int batch, void *stream, void *workspace, size_t workspace_bytes);
 HVN_API size_t hvn_train_workspace_bytes(const hvn_top *ops, int n_ops, int batch);
-HVN_API const char *hvn_train_last_error(void);
+HVN_API const char *hvn_train_last_error(void);   /* = hvn_last_error(): an alias kept for existing callers */
 
 /* Losses of run_desc.py:40-82 with opt.py:47-51 weights (np: bce + dice, hv: mse + msge, tp: bce + dice).
  * logits_* / grad_*: dev float32 NCHW [n][c][h][w] (c = 2, 2, nr_types); true_np / true_tp: dev int32 [n][h][w];

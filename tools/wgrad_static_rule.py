@@ -20,7 +20,6 @@ TARGETS = (3072, 1536, 1024, 768, 512, 384, 256)
 
 
 def main():
-    lib = L.lib()
     seen = {}
     for tag, mode, nt, freeze, bs in (("phase0_b16", "original", 5, True, 16), ("phase1_b4", "original", 5, False, 4), ("fit_fast_b8", "fast", None, False, 8)):
         net = net_desc.create_model(mode=mode, nr_types=nt, input_ch=3, freeze=freeze)
@@ -53,8 +52,7 @@ def main():
                     best = 1e9
                     for r in range(4):
                         e0.record()
-                        rc = lib.hvn_run_train_plan_ws(base + i * tsz, 1, bs, eng._stream(), ws.data_ptr(), 4 * ws.numel())
-                        assert rc == 0, lib.hvn_train_last_error()
+                        L.call("hvn_run_train_plan_ws", base + i * tsz, 1, bs, eng._stream(), ws.data_ptr(), 4 * ws.numel())
                         e1.record()
                         e1.synchronize()
                         if r:
