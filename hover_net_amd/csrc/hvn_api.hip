@@ -118,6 +118,21 @@ template <class T> static inline void set_view(const hvn_view &v, T *&p, long &s
 // every stride a multiple of mask + 1 elements (3: 16 bytes of fp32, 7: 16 bytes of bf16)
 static inline bool strides_ok(const hvn_view &v, long mask) { return ((v.sn | v.sy | v.sx) & mask) == 0; }
 
+// the image view of a STAIN op: uint8 [batch][h][w][3], byte strides (0 = dense); 0 = accepted, sn / sy resolved
+static int stain_image(const char *what, const hvn_op *op, const hvn_view &v, int batch, long &sn, long &sy)
+{
+    if (!v.base) return hvn_fail(HVN_E_ARG, "%s: null pointer", what);
+    if (op->x_dtype != 0) return hvn_fail(HVN_E_ARG, "%s: uint8 pixels only (x_dtype %d)", what, op->x_dtype);
+    if (v.h < 1 || v.w < 1 || v.c != 3) return hvn_fail(HVN_E_ARG, "%s: h, w >= 1 and three channels (c = %d)", what, v.c);
+    if ((int64_t)v.h * v.w > ((int64_t)1 << 30)) return hvn_fail(HVN_E_SIZE, "%s: h * w > 2^30 (h = %d)", what, v.h);
+    if (batch > 65535) return hvn_fail(HVN_E_ARG, "%s: batch %d above 65535", what, batch);
+    if ((v.sx && v.sx != 3) || v.sc > 1) return hvn_fail(HVN_E_ARG, "%s: pixels are three contiguous bytes", what);
+    sy = v.sy ? v.sy : 3L * v.w;
+    sn = v.sn ? v.sn : sy * v.h;
+    if (sy < 3L * v.w || sn < sy * v.h) return hvn_fail(HVN_E_ARG, "%s: a stride shorter than a row or a sample", what);
+    return 0;
+}
+
 int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
 {
     switch (op->kind) {
@@ -361,6 +376,46 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if (a.last && (a.nr_types > 0 ? !aligned16(a.y) : (((uintptr_t)a.y & 3) != 0))) return hvn_fail(HVN_E_ARG, "tta: output not 16-byte aligned");
         if (batch > 65535) return hvn_fail(HVN_E_ARG, "tta: batch %d above 65535", batch);
         return hvn_launch_status(hvn_launch_tta(a, s), "tta");
+    }
+    case HVN_OP_STAIN_HIST: {
+        StainHistArgs a;
+        a.x = (const uint8_t *)op->x.base;
+        a.mask = (const uint8_t *)op->res.base;
+        a.bins = (uint32_t *)op->y.base;
+        a.N = batch; a.H = op->x.h; a.W = op->x.w;
+        if (!a.bins) return hvn_fail(HVN_E_ARG, "stain_hist: null pointer");
+        if (int rc = stain_image("stain_hist", op, op->x, batch, a.xsn, a.xsy)) return rc;
+        if ((uintptr_t)a.bins & 3) return hvn_fail(HVN_E_ARG, "stain_hist: misaligned bins");
+        return hvn_launch_status(hvn_launch_stain_hist(a, s), "stain_hist");
+    }
+    case HVN_OP_STAIN_COMPACT: {
+        uint32_t *bins = (uint32_t *)op->x.base, *list = (uint32_t *)op->y.base;
+        int64_t *status = (int64_t *)op->y2.base;
+        void *ws = op->x2.base;
+        if (!bins || !list || !status || !ws) return hvn_fail(HVN_E_ARG, "stain_compact: null pointer");
+        if (batch != 1) return hvn_fail(HVN_E_ARG, "stain_compact: batch %d, not 1", batch);
+        if (((uintptr_t)bins & 15) || ((uintptr_t)list & 7) || ((uintptr_t)status & 7) || ((uintptr_t)ws & 7))
+            return hvn_fail(HVN_E_ARG, "stain_compact: misaligned bins (16), list, status or workspace (8)");
+        if (op->y.h < 1 || op->y.h > (1 << 24)) return hvn_fail(HVN_E_SIZE, "stain_compact: list capacity %d outside [1, 2^24]", op->y.h);
+        return hvn_launch_status(hvn_launch_stain_compact(bins, list, (uint32_t)op->y.h, status, ws, op->_rsv != 0, s), "stain_compact");
+    }
+    case HVN_OP_STAIN_APPLY: {
+        StainApplyArgs a;
+        a.x = (const uint8_t *)op->x.base;
+        a.y = (uint8_t *)op->y.base;
+        a.tables = (const double *)op->w;
+        a.N = batch; a.H = op->x.h; a.W = op->x.w;
+        if (!a.y || !a.tables) return hvn_fail(HVN_E_ARG, "stain_apply: null pointer");
+        if (int rc = stain_image("stain_apply", op, op->x, batch, a.xsn, a.xsy)) return rc;
+        if (op->y.h != a.H || op->y.w != a.W) return hvn_fail(HVN_E_ARG, "stain_apply: x and y must have the same extents (y.h = %d)", op->y.h);
+        if (int rc = stain_image("stain_apply", op, op->y, batch, a.ysn, a.ysy)) return rc;
+        if ((uintptr_t)a.tables & 7) return hvn_fail(HVN_E_ARG, "stain_apply: misaligned tables");
+        if (!((const uint8_t *)a.y == a.x && a.ysn == a.xsn && a.ysy == a.xsy)) {       // y is x itself, or the two do not meet
+            const uintptr_t x0 = (uintptr_t)a.x, x1 = x0 + (uintptr_t)((batch - 1) * a.xsn + (a.H - 1) * a.xsy + 3L * a.W);
+            const uintptr_t y0 = (uintptr_t)a.y, y1 = y0 + (uintptr_t)((batch - 1) * a.ysn + (a.H - 1) * a.ysy + 3L * a.W);
+            if (x0 < y1 && y0 < x1) return hvn_fail(HVN_E_ARG, "stain_apply: x and y overlap without being the same view");
+        }
+        return hvn_launch_status(hvn_launch_stain_apply(a, s), "stain_apply");
     }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);

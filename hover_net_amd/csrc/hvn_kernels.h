@@ -186,6 +186,28 @@ struct TtaArgs {
 };
 int hvn_launch_tta(const TtaArgs &a, hipStream_t stream);
 
+// hvn_stain.hip: Macenko stain normalisation (hover_net_amd/stain.py); arguments validated by the caller (hvn_api.hip); HVN_OK or HVN_E_LAUNCH
+struct StainHistArgs {
+    const uint8_t *x;           // [N][H][W][3]
+    long xsn, xsy;              // byte strides of a sample and a row (pixels are 3 contiguous bytes)
+    const uint8_t *mask;        // dense [N][H][W], non-zero = count the pixel; NULL = all
+    uint32_t *bins;             // [1 << 24], bin = r << 16 | g << 8 | b; the launch ADDS to it
+    int N, H, W;
+};
+int hvn_launch_stain_hist(const StainHistArgs &a, hipStream_t stream);
+#define HVN_STAIN_WORKSPACE_BYTES 65536      // of hvn_launch_stain_compact, 8-byte aligned
+// list: uint32 [cap][2] = (key, count) of the non-empty bins, ascending; status: int64 {non-empty bins, pixels counted}
+int hvn_launch_stain_compact(uint32_t *bins, uint32_t *list, uint32_t cap, int64_t *status, void *workspace, int clear, hipStream_t stream);
+struct StainApplyArgs {
+    const uint8_t *x;           // [N][H][W][3]
+    long xsn, xsy;
+    uint8_t *y;                 // same extents; may be x itself (same strides)
+    long ysn, ysy;
+    const double *tables;       // [3][3][256]: T[c][k][v]
+    int N, H, W;
+};
+int hvn_launch_stain_apply(const StainApplyArgs &a, hipStream_t stream);
+
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)
     long xsn, xsy, xsx;

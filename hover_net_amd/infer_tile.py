@@ -334,7 +334,7 @@ def run_sharded(items, step_fn, batch_size, gather=True):
 
 # --------------------------------------------------------------------------------------------
 def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384, *,
-                   return_features=False, tta=None):
+                   return_features=False, tta=None, stain_norm=None):
     """images: list of uint8 [H,W,3] arrays (RGB).  Returns a list of (pred_inst int32 [H,W] numpy, inst_info_dict | None)
     in input order: complete on rank 0 (the writer); the other ranks hold their own images' results and None elsewhere.
     `return_raw=True` appends the stitched float32 prediction map [H,W,3|4] to each tuple (`--save_raw_map`,
@@ -344,6 +344,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     (`PostProc.features`); the feature bytes travel to rank 0 as one more array of the item.
     `tta`: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every network step is the
     test-time-augmented one (`Engine.run_tta`); the sharding is the same, the augmentation lives inside the step.
+    `stain_norm`: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py): every image is fitted on itself
+    and normalised on the device right after its upload, into a new tensor the patches are cut from (the host-geometry branch uses
+    the host forms: the same bytes); the colour features of `return_features` keep reading the image as given; a degenerate image
+    (`stain.StainFitError`) passes through unnormalised with one warning.  Composes with `tta` (stain first, then the views).
     The images are worked off in groups of at most `max_patches` network patches (3.6 GB of uint8 patches + 1.7 GB of maps at the
     default), so that a large cache round of `process_file_list` never has all its overlapping patches in HBM at once; every rank
     forms the same groups (the collectives inside stay matched)."""
@@ -351,6 +355,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         from . import tta as TT
 
         tta = TT.views(tta)
+    if stain_norm is not None:
+        from . import stain as ST
+
+        stain_norm = ST.resolve(stain_norm)
     win = 270 if (model.module if hasattr(model, "module") and not hasattr(model, "engine") else model).mode == "original" else 256
     msk = 80 if win == 270 else 164
     groups, cur, cur_n = [], [], 0
@@ -368,14 +376,16 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         more = {"return_features": True} if return_features else {}
         if tta is not None:
             more["tta"] = tta
+        if stain_norm is not None:
+            more["stain_norm"] = stain_norm
         for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
                                                     return_raw, **more)):
             out[i] = res
     return out
 
 
-def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False, tta=None):
-    """One group of `process_images`.
+def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False, tta=None, stain_norm=None):
+    """One group of `process_images` (`stain_norm`: None or the resolved target, a `stain.StainFit`).
 
     Pipeline per call: patch extraction -> sharded HIP network (`run_desc.infer_step_device`)
     -> one all_to_all of the per-patch maps to the images' owners (`route_to_owners`) -> per-image stitch on the GPU -> on-GPU instance
@@ -383,6 +393,7 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
     -> tensor gather of instance maps / record tables / contours to rank 0 (`gather_items_to_rank0`).
     An item's arrays: [0:4] `result_to_arrays`, [4] the raw map with `return_raw`, LAST the feature bytes with `return_features`."""
     from . import post_proc, run_desc
+    from . import stain as ST
 
     net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
     win = 270 if net.mode == "original" else 256
@@ -394,10 +405,17 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
         if dev.type == "cuda":      # source image up once, reflect padding + overlapping crops on the GPU
             info, pad_tl = patch_grid(img.shape, win, msk)
             img_dev = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-            patches.append(extract_patches_device(img_dev, info, win, pad_tl))
+            src_dev = img_dev
+            if stain_norm is not None:  # fitted on itself (one readback of its colour list), normalised into a new tensor
+                tab = ST.tables_or_none(img_dev, stain_norm)
+                src_dev = img_dev if tab is None else ST.apply_device(img_dev, tab)
+            patches.append(extract_patches_device(src_dev, info, win, pad_tl))
             if return_features and i % world == rank:
                 uploaded[i] = img_dev           # the colour features of the images this rank owns read it again
         else:                       # host geometry (CPU tests of the sharding logic)
+            if stain_norm is not None:
+                tab = ST.tables_or_none(np.ascontiguousarray(img[..., :3]), stain_norm)
+                img = img if tab is None else ST.apply_host(img[..., :3], tab)
             padded, info = prepare_patching(img, win, msk)
             patches.append(torch.from_numpy(extract_patches(padded, info, win)))
         infos.append(info)

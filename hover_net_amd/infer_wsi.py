@@ -510,8 +510,17 @@ class DeviceMerger:
 # --------------------------------------------------------------------------------------------
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
-                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None):
-        """tta: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every stage-1 network step is
+                 patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
+                 stain_norm=None):
+        """stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
+        `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
+        (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every
+        region it reads, in place on the device after any GPU resample and before the patches are cut (the CPU branch uses
+        `stain.apply_host`).  Every rank computes the same fit from the same thumbnail, so no collective is added.  The thumbnails of
+        `ArraySlide` / `TiledSlide` are sub-sampled TRUE pixels, so the fit sees colours the slide holds; a backend whose thumbnail
+        averages pixels changes what is fitted (mixed colours at every edge).  A degenerate thumbnail leaves the slide unnormalised
+        with one warning.  Composes with `tta` (stain first, then the views).
+        tta: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every stage-1 network step is
         the test-time-augmented one (`Engine.run_tta`); the stitching and stage 2 see its maps as they see the plain ones.
         features=True: every entry of the instance dict gains "features" (`features.derive`): the SHAPE features of the nucleus,
         computed per post-processed tile right after its record table (`PostProc.features`, image=None) and carried wherever the
@@ -530,6 +539,10 @@ class WsiInference:
         from . import tta as TT
 
         self.tta = TT.views(tta)
+        from . import stain as ST
+
+        self.stain_norm = ST.resolve(stain_norm)
+        self._stain_tables = None                   # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
@@ -566,10 +579,14 @@ class WsiInference:
         rank to the patch rows of its row slab (`row_slabs`): a rank reads, of every chunk that crosses its slab, only the rows
         it needs, predicts those patches and scatters them into its LOCAL tensor (slab + halo rows, 1 / world of the map).  The
         halo rows -- what its stage-2 tiles reach into the neighbours' slabs -- then arrive in one `all_to_all_single`.
+        With `stain_norm`, every region is normalised with the tables `fit_stain` left (`run` calls it; a direct caller does).
         Returns the whole map as a tensor (one rank), or a `SlabMap` (as_slab=True; always on several ranks)."""
+        from . import stain as ST
+
         t_start = time.perf_counter()
         shape = np.array(slide.shape[:2])
         H, W = int(shape[0]), int(shape[1])
+        stain_dev = ST.tables_device(self._stain_tables, self.device) if self._stain_tables is not None and self.device.type == "cuda" else None
         dist, rank, world = infer_tile._dist()
         bounds = row_slabs(H, world, self.pin[0], self.pout[0])
         need = needed_rows(self.tile_lists(shape, mask), bounds, H) if world > 1 else np.array([[0, H]])
@@ -610,10 +627,14 @@ class WsiInference:
                 # the GPU (hvn_extract_patches; every crop is in bounds, so its reflect rule never fires)
                 region_dev = (slide.read_region_device((x0, y0), size, self.device) if hasattr(slide, "read_region_device") else
                               torch.from_numpy(np.ascontiguousarray(slide.read_region((x0, y0), size)[..., :3])).to(self.device))
+                if stain_dev is not None:
+                    ST.apply_device(region_dev, stain_dev, out=region_dev)
                 patches = infer_tile.extract_patches_device(region_dev, rel.astype(np.int32), win, 0)
                 del region_dev
             else:
                 region = slide.read_region((x0, y0), size)
+                if self._stain_tables is not None:
+                    region = ST.apply_host(np.asarray(region)[..., :3], self._stain_tables)
                 patches = torch.from_numpy(np.ascontiguousarray(np.stack([region[y:y + win, x:x + win] for y, x in rel])))
             outs = [self._step(patches[b0:b0 + self.batch_size]).clone() for b0 in range(0, patches.shape[0], self.batch_size)]
             out = torch.cat(outs, 0)
@@ -636,6 +657,22 @@ class WsiInference:
                 tm["halo_exchange_s"] = time.perf_counter() - t_h
                 tm["halo_rows"] = int((hi - lo) - (bounds[rank + 1] - bounds[rank]))
         return local if (as_slab or world > 1) else local.t
+
+    def fit_stain(self, slide, mask=None):
+        """The slide's stain tables from `slide.thumbnail(8)` under `mask` (see __init__), kept for `raw_prediction`; None without
+        `stain_norm` or for a degenerate thumbnail.  The colour list comes from the GPU where the model is on one: the same fit."""
+        self._stain_tables = None
+        if self.stain_norm is None:
+            return None
+        from . import stain as ST
+
+        thumb = np.ascontiguousarray(np.asarray(slide.thumbnail(8))[..., :3], dtype=np.uint8)
+        tmask = None if mask is None else ST.thumbnail_mask(thumb.shape[:2], mask)
+        if self.device.type == "cuda":
+            thumb = torch.from_numpy(thumb).to(self.device)
+            tmask = None if tmask is None else torch.from_numpy(tmask).to(self.device)
+        self._stain_tables = ST.tables_or_none(thumb, self.stain_norm, tmask)
+        return self._stain_tables
 
     def _step(self, batch):
         return run_desc.infer_step_device(batch.to(self.device), self.model, **({"tta": self.tta} if self.tta is not None else {}))
@@ -814,6 +851,7 @@ class WsiInference:
             mask = tissue_mask.simple_get_mask(slide.thumbnail(32), device=self.device if self.device_mask else None)
         if mask is None:
             mask = np.ones((max(1, int(shape[0]) // 32), max(1, int(shape[1]) // 32)), np.uint8)
+        self.fit_stain(slide, mask)
         pred_map = self.raw_prediction(slide, mask, as_slab=True)
         return self.stitch_instances(pred_map, mask, shape=shape)
 

@@ -38,7 +38,8 @@ typedef struct hvn_view {
     int32_t sc;          /* channel stride in elements (CONV0 input only, e.g. h*w for NCHW) */
 } hvn_view;
 
-enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10 };
+enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
+       HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -95,6 +96,28 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           R = [[0, 1], [-1, 0]].  Sums run in call order, without atomics: the hv channels equal the same fp32 sum bit for bit, and
  *           one view (k = 0, K = 1) gives PREDMAP's np and hv bits.  HVN_E_ARG: k outside 0..7, h != w with odd r, no accumulator, a
  *           last view without y or with K < 1, y not 16-byte aligned (with types)
+ *   STAIN_HIST / STAIN_COMPACT / STAIN_APPLY   Macenko stain normalisation (hover_net_amd/stain.py holds the definition; csrc/hvn_stain.hip).
+ *           Never part of a plan.  Images are uint8 [n][h][w][3] (x_dtype 0 only, c = 3), strides in BYTES as VIEW (sy / sn = 0: dense
+ *           rows / samples; sx 0 | 3), h * w <= 2^30, n <= 65535.  A refusal launches nothing and leaves every output untouched.
+ *     STAIN_HIST     adds the pixels of x to the colour histogram y.base = uint32 [1 << 24], bin = r << 16 | g << 8 | b (4-byte aligned; the
+ *           call ADDS: the caller clears the table, or lets STAIN_COMPACT do it, and bounds the pixels added to one table by 2^32 - 1);
+ *           res.base = optional uint8 mask, dense [n][h][w]: non-zero = count the pixel, NULL = all.  Integer atomics only: the table is
+ *           a function of the inputs alone.  No other field is read.
+ *     STAIN_COMPACT  (batch must be 1) x.base = the bins (16-byte aligned); y.base = uint32 [cap][2] list (8-byte aligned), cap = y.h in
+ *           [1, 2^24]: the non-empty bins as (key, count) pairs in ascending key order -- np.unique(return_counts=True) of the keys; a
+ *           table of more non-empty bins than cap gives the first cap pairs; y2.base = int64 status [2] = { non-empty bins (the TRUE
+ *           number, also past cap), pixels counted } (8-byte aligned); x2.base = 65536 bytes of device workspace (8-byte aligned);
+ *           `_rsv` != 0: every non-empty bin read is also stored back as 0 (past cap too), which leaves the whole table clear for the
+ *           next image.  The list's layout is a function of the bins alone.  HVN_E_SIZE: cap outside [1, 2^24].
+ *     STAIN_APPLY    y = the normalised x: x and y have the same extents; y may be the very view x is (same base and strides: in place),
+ *           any other overlap of the two is refused; w = float64 tables T[3][3][256] on the device (8-byte aligned; read as doubles
+ *           whatever the pointer's declared type), T[c][k][v] = exp(-M[c][k] * od[v]) as stain.tables makes them.  Per channel c of a
+ *           pixel (r, g, b): t = ((240.0 * T[c][0][r]) * T[c][1][g]) * T[c][2][b] in float64, multiplied in that order, and the byte is
+ *           (uint8) (t < 255 ? t : 255), truncating (NaN and +inf give 255; entries are expected non-negative).  Only multiplications:
+ *           equal to stain.apply_host bit for bit.
+ *           HVN_E_ARG: a null pointer (the mask excepted), c != 3, x_dtype != 0, h or w < 1, a stride shorter than a row or a sample,
+ *           a misaligned table / list / status / workspace, n > 65535, x and y of different extents or partly overlapping.
+ *           HVN_E_SIZE: h * w > 2^30.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
