@@ -133,6 +133,24 @@ static int stain_image(const char *what, const hvn_op *op, const hvn_view &v, in
     return 0;
 }
 
+// what the two NBR ops share: the table, the workspace, N and the grid; 0 = accepted
+static int nbr_common(const char *what, const hvn_op *op, int batch)
+{
+    const int N = op->x.h;
+    if (!op->w || !op->x2.base) return hvn_fail(HVN_E_ARG, "%s: null pointer", what);
+    if (batch != 1) return hvn_fail(HVN_E_ARG, "%s: batch %d, not 1", what, batch);
+    if (((uintptr_t)op->w & 7) || ((uintptr_t)op->x2.base & 7)) return hvn_fail(HVN_E_ARG, "%s: misaligned table or workspace (8)", what);
+    if (N < 1) return hvn_fail(HVN_E_ARG, "%s: N = %d, fewer than one point", what, N);
+    if (op->kh < 1 || op->kw < 1) return hvn_fail(HVN_E_ARG, "%s: a grid of %d x %d cells", what, op->kh, op->kw);
+    if (N > HVN_NBR_MAX_N) return hvn_fail(HVN_E_SIZE, "%s: N = %d above 2^26", what, N);
+    const long cells = (long)op->kh * op->kw;
+    if (op->kh > HVN_NBR_MAX_AXIS || op->kw > HVN_NBR_MAX_AXIS || cells > HVN_NBR_MAX_CELLS)
+        return hvn_fail(HVN_E_SIZE, "%s: a grid of %d x %d cells, more than 4096 per axis or 2^22 in all", what, op->kh, op->kw);
+    if ((long)op->x2.sn < HVN_NBR_WORKSPACE_BYTES(N, cells))
+        return hvn_fail(HVN_E_SIZE, "%s: workspace of %ld bytes, %ld needed", what, (long)op->x2.sn, HVN_NBR_WORKSPACE_BYTES(N, cells));
+    return 0;
+}
+
 int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
 {
     switch (op->kind) {
@@ -416,6 +434,31 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
             if (x0 < y1 && y0 < x1) return hvn_fail(HVN_E_ARG, "stain_apply: x and y overlap without being the same view");
         }
         return hvn_launch_status(hvn_launch_stain_apply(a, s), "stain_apply");
+    }
+    case HVN_OP_NBR_GRID: {
+        NbrGridArgs a;
+        a.xy = (const double *)op->x.base;
+        a.types = (const int *)op->res.base;
+        a.table = (const double *)op->w;
+        a.workspace = op->x2.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw;
+        if (!a.xy || !a.workspace) return hvn_fail(HVN_E_ARG, "nbr_grid: null pointer");
+        if (int rc = nbr_common("nbr_grid", op, batch)) return rc;
+        if (((uintptr_t)a.xy & 7) || ((uintptr_t)a.types & 3)) return hvn_fail(HVN_E_ARG, "nbr_grid: misaligned xy (8) or types (4)");
+        return hvn_launch_status(hvn_launch_nbr_grid(a, s), "nbr_grid");
+    }
+    case HVN_OP_NBR_QUERY: {
+        NbrQueryArgs a;
+        a.table = (const double *)op->w;
+        a.workspace = op->x2.base;
+        a.count = (int *)op->y.base; a.knn = (int *)op->y2.base; a.nearest = (int *)op->res.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.k = op->_rsv;
+        if (!a.workspace || !a.count || !a.knn || !a.nearest) return hvn_fail(HVN_E_ARG, "nbr_query: null pointer");
+        if (a.k < 1 || a.k > 16) return hvn_fail(HVN_E_ARG, "nbr_query: k = %d outside 1..16", a.k);
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_query: %d types outside 1..16", a.T);
+        if (int rc = nbr_common("nbr_query", op, batch)) return rc;
+        if (((uintptr_t)a.count | (uintptr_t)a.knn | (uintptr_t)a.nearest) & 3) return hvn_fail(HVN_E_ARG, "nbr_query: misaligned count, knn or nearest (4)");
+        return hvn_launch_status(hvn_launch_nbr_query(a, s), "nbr_query");
     }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);

@@ -208,6 +208,33 @@ struct StainApplyArgs {
 };
 int hvn_launch_stain_apply(const StainApplyArgs &a, hipStream_t stream);
 
+// hvn_neighbours.hip: fixed-radius neighbours of centroids (hover_net_amd/neighbours.py); arguments validated by the caller (hvn_api.hip); HVN_OK or HVN_E_LAUNCH
+#define HVN_NBR_MAX_N (1L << 26)
+#define HVN_NBR_MAX_AXIS 4096
+#define HVN_NBR_MAX_CELLS (1L << 22)
+// the one workspace of both ops, 8-byte aligned, in this order: x, y of the points in cell order (float64 [N] each), their positions and
+// types (int32 [N] each), cell_start (int32 [cells + 1]), the cell counters / cursors (int32 [cells]), the scan's block sums (int32 [1024])
+#define HVN_NBR_WORKSPACE_BYTES(N, cells) (24L * (N) + 4L * (2L * (cells) + 1) + 4096L)
+struct NbrWorkspace {
+    double *sx, *sy;
+    int *spos, *stype, *cell_start, *cursor, *bsum;
+};
+struct NbrGridArgs {
+    const double *xy;           // [N][2] = (x, y)
+    const int *types;           // [N] or NULL (all 0)
+    const double *table;        // {x0, y0, c, r2}
+    void *workspace;
+    int N, ncy, ncx;
+};
+int hvn_launch_nbr_grid(const NbrGridArgs &a, hipStream_t stream);
+struct NbrQueryArgs {
+    const double *table;
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    int *count, *knn, *nearest; // [N][T], [N][k], [N][T]
+    int N, ncy, ncx, T, k;
+};
+int hvn_launch_nbr_query(const NbrQueryArgs &a, hipStream_t stream);
+
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)
     long xsn, xsy, xsx;

@@ -511,8 +511,12 @@ class DeviceMerger:
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
-                 stain_norm=None):
-        """stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
+                 stain_norm=None, neighbours=None):
+        """neighbours: None or {"radius": r, "k": k} in pixels of the processed slide: every entry of the instance dict gains
+        "neighbours" (`neighbours.annotate`), computed ONCE on the final dict after the merge, in slide coordinates (the tiles' origins
+        are already in the centroids), so neighbours are found across tile seams.  It runs on rank 0, where the dict lives (on the
+        GPU where the model is on one); no collective is added.
+        stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
         `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
         (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every
         region it reads, in place on the device after any GPU resample and before the patches are cut (the CPU branch uses
@@ -542,7 +546,10 @@ class WsiInference:
         from . import stain as ST
 
         self.stain_norm = ST.resolve(stain_norm)
-        self._stain_tables = None                   # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
+        from . import neighbours as NB
+
+        self.neighbours = NB.resolve(neighbours)
+        self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         self.model, self.nr_types, self.batch_size = model, nr_types, batch_size
@@ -891,7 +898,15 @@ class WsiInference:
             out = merger.result()
             if getattr(self, "timing", None) is not None:
                 self.timing["map_d2h_s"] = time.perf_counter() - t0
-            return out
+            return self._with_neighbours(out)
         if rank != 0:
             return None, None
-        return merger.inst_map, merger.inst_info
+        return self._with_neighbours((merger.inst_map, merger.inst_info))
+
+    def _with_neighbours(self, out):
+        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours`, the dict's entries gain "neighbours"."""
+        if self.neighbours is not None and out[1]:
+            from . import neighbours as NB
+
+            NB.annotate(out[1], self.neighbours[0], self.neighbours[1], self.nr_types, device=self.device if self.device.type == "cuda" else None)
+        return out

@@ -1,0 +1,311 @@
+"""Nucleus neighbourhoods: typed counts within a radius, the k nearest neighbours and the nearest neighbour of every type -- the
+definition of the result, its host form, and the device form that returns the same integers (csrc/hvn_neighbours.hip, DESIGN.md
+4.18).  Opt-in everywhere.  numpy only; imports without a GPU.
+
+Inputs: `xy` float64 [N, 2] of (x, y), all finite; `types` int32 [N] in [0, T) or None (then T = 1 and every type is 0); `radius`
+r > 0; 1 <= k <= 16; T <= 16.  All arithmetic is IEEE float64, one rounding per operation, no fused multiply-add:
+
+    dx = xj - xi;  dy = yj - yi;  d2(i, j) = (dx * dx) + (dy * dy);  r2 = r * r
+    j is a neighbour of i  <=>  j != i and d2(i, j) <= r2
+
+d2 is symmetric bit for bit (negation is exact), so the relation is symmetric.  Outputs per point i, all int32, positions j being row
+numbers of `xy`:
+
+    count[i, t]            the number of neighbours of type t
+    knn[i, 0..k)           the neighbours in ascending (d2, j) order, the first k, padded with -1
+    nearest_of_type[i, t]  the neighbour of type t that is smallest in (d2, j), or -1
+
+Coincident points (d2 == 0, j != i) are neighbours, ordered by j.  Distances are not outputs of the search: `distances` derives
+sqrt(d2(i, j)) from returned positions with the formula above, so the device is compared in integers only and every float a user
+sees is numpy's.
+
+Three implementations: tests/neighbours_ref.py (O(N^2), the oracle), `query_host` (a uniform grid to gather candidates, then the rule
+above: a million points are feasible without a GPU) and `query_device` (HVN_OP_NBR_GRID + HVN_OP_NBR_QUERY).  The three agree with ==.
+
+The grid (`grid`).  x0 = min x, y0 = min y, and the cell of a point is (floor((y - y0) / c), floor((x - x0) / c)), clamped into
+[0, ncy) x [0, ncx).  The 3 x 3 cells around a point must hold all its neighbours, and c = r does not achieve that: with r = 1 and
+points at x = 0, 1 - 2^-53 and 2, the difference 2 - (1 - 2^-53) rounds to exactly 1.0, the last two points are neighbours, and at
+c = 1 they land in cells 0 and 2.  So c = r (1 + 2^-20), or wider.  The argument, per axis:
+  * d2 <= r2 gives fl(dx)^2 <= r^2 (1 + 2^-53)^2 up to the rounding of dx * dx, hence |fl(dx)| <= r (1 + 2^-52), and the true
+    difference |xj - xi| <= r (1 + 2^-51)  (`_check` refuses a radius whose square is not a normal number, where this would fail);
+  * the true cell coordinate u = (x - x0) / c is below the per-axis cap of 4096 cells + 1, and the computed one carries two roundings
+    (the subtraction, the division): |fl(u) - u| <= 4097 * 2^-52 < 2^-39;
+  * the true coordinates of two neighbours differ by at most r (1 + 2^-51) / c <= (1 + 2^-51) / (1 + 2^-20) < 1 - 2^-21, the computed
+    ones by less than 1 - 2^-21 + 2^-38 < 1, so their floors differ by at most 1 (clamping moves both the same way).
+The grid is capped at 4096 cells per axis and 2^22 cells in all; c is widened where the extent needs more.  Wider cells are slower,
+never wrong.
+"""
+import collections
+import ctypes
+
+import numpy as np
+
+MARGIN = 1.0 + 2.0 ** -20
+MAX_AXIS, MAX_CELLS, MAX_N, MAX_K, MAX_T = 4096, 1 << 22, 1 << 26, 16, 16
+MIN_R2 = 2.0 ** -1000
+_PAIRS = 1 << 22                # candidate pairs per round of `query_host`
+
+Grid = collections.namedtuple("Grid", "x0 y0 c ncx ncy")
+
+
+def _check(xy, types, radius, k, nr_types):
+    """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, k, T)."""
+    if not isinstance(xy, np.ndarray) or xy.dtype != np.float64:
+        raise TypeError("xy must be a float64 numpy array [N, 2], got %s" % (getattr(xy, "dtype", type(xy).__name__),))
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+        raise ValueError("xy must be [N, 2] with N >= 1, got %s" % (xy.shape,))
+    n = xy.shape[0]
+    if n > MAX_N:
+        raise ValueError("%d points, more than 2^26" % n)
+    if not np.isfinite(xy).all():
+        raise ValueError("xy holds a coordinate that is not finite")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(xy.max(0) - xy.min(0)).all():
+            raise ValueError("the extent of xy is not a finite float64")
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError("radius must be a number, got %r" % (radius,))
+    r = float(radius)
+    if not (r > 0.0 and np.isfinite(r) and np.isfinite(r * r) and r * r >= MIN_R2):
+        raise ValueError("radius = %r: it must be positive and its square a normal, finite float64" % (radius,))
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise TypeError("k must be an integer, got %r" % (k,))
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError("k = %d outside 1..%d" % (k, MAX_K))
+    if nr_types is not None and (isinstance(nr_types, (bool, np.bool_)) or not isinstance(nr_types, (int, np.integer))):
+        raise TypeError("nr_types must be an integer or None, got %r" % (nr_types,))
+    if types is None:
+        t = 1 if nr_types is None else int(nr_types)
+    else:
+        if not isinstance(types, np.ndarray) or types.dtype != np.int32:
+            raise TypeError("types must be an int32 numpy array [N] or None, got %s" % (getattr(types, "dtype", type(types).__name__),))
+        if types.shape != (n,):
+            raise ValueError("types %s is not parallel to xy %s" % (types.shape, xy.shape))
+        t = int(types.max()) + 1 if nr_types is None else int(nr_types)
+    if not 1 <= t <= MAX_T:
+        raise ValueError("%d types outside 1..%d" % (t, MAX_T))
+    if types is not None and (int(types.min()) < 0 or int(types.max()) >= t):
+        raise ValueError("types outside [0, %d)" % t)
+    return np.ascontiguousarray(xy), None if types is None else np.ascontiguousarray(types), r, int(k), t
+
+
+def grid(xy, radius):
+    """The grid of the module docstring for checked inputs -> Grid(x0, y0, c, ncx, ncy)."""
+    x0, y0 = float(xy[:, 0].min()), float(xy[:, 1].min())
+    ex, ey = float(xy[:, 0].max()) - x0, float(xy[:, 1].max()) - y0
+    c = max(radius * MARGIN, ex / (MAX_AXIS - 1), ey / (MAX_AXIS - 1))
+    while True:
+        ncx, ncy = int(np.floor(ex / c)) + 1, int(np.floor(ey / c)) + 1
+        if ncx <= MAX_AXIS and ncy <= MAX_AXIS and ncx * ncy <= MAX_CELLS:
+            return Grid(x0, y0, c, ncx, ncy)
+        c *= 1.25
+
+
+def cells(xy, g):
+    """(cx, cy) int64 [N] of every point: floor of the float64 quotient, clamped into the grid."""
+    cx = np.clip(np.floor((xy[:, 0] - g.x0) / g.c), 0, g.ncx - 1).astype(np.int64)
+    cy = np.clip(np.floor((xy[:, 1] - g.y0) / g.c), 0, g.ncy - 1).astype(np.int64)
+    return cx, cy
+
+
+def _empty(n, k, t):
+    return {"count": np.zeros((n, t), np.int32), "knn": np.full((n, k), -1, np.int32), "nearest_of_type": np.full((n, t), -1, np.int32)}
+
+
+def query_host(xy, types, radius, k, nr_types=None):
+    """The definition on the host -> {"count": int32 [N, T], "knn": int32 [N, k], "nearest_of_type": int32 [N, T]}.  Candidates
+    come from the grid (three contiguous runs of the cell-ordered points per query), in rounds of about 4 million pairs; the rule
+    and the two orders are the docstring's."""
+    xy, types, r, k, t = _check(xy, types, radius, k, nr_types)
+    n = xy.shape[0]
+    g = grid(xy, r)
+    r2 = r * r
+    cx, cy = cells(xy, g)
+    cell = cy * g.ncx + cx
+    order = np.argsort(cell, kind="stable")
+    start = np.zeros(g.ncx * g.ncy + 1, np.int64)
+    np.cumsum(np.bincount(cell, minlength=g.ncx * g.ncy), out=start[1:])
+    sx, sy = xy[order, 0], xy[order, 1]
+    st = np.zeros(n, np.int64) if types is None else types[order].astype(np.int64)
+    scx, scy = cx[order], cy[order]
+    lo, hi = np.empty((3, n), np.int64), np.empty((3, n), np.int64)
+    ca, cb = np.maximum(scx - 1, 0), np.minimum(scx + 1, g.ncx - 1)
+    for row in range(3):
+        yy = scy + (row - 1)
+        ok = (yy >= 0) & (yy < g.ncy)
+        base = np.clip(yy, 0, g.ncy - 1) * g.ncx
+        lo[row] = start[base + ca]
+        hi[row] = np.where(ok, start[base + cb + 1], lo[row])
+    out = _empty(n, k, t)
+    ends = np.cumsum((hi - lo).sum(0))
+    a = 0
+    while a < n:
+        b = max(a + 1, int(np.searchsorted(ends, (ends[a - 1] if a else 0) + _PAIRS, side="right")))
+        qi, cand = [], []
+        for row in range(3):
+            lens = hi[row, a:b] - lo[row, a:b]
+            first = np.cumsum(lens) - lens
+            qi.append(np.repeat(np.arange(a, b, dtype=np.int64), lens))
+            cand.append(np.repeat(lo[row, a:b] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64))
+        qi, cand = np.concatenate(qi), np.concatenate(cand)
+        dx, dy = sx[cand] - sx[qi], sy[cand] - sy[qi]
+        d2 = (dx * dx) + (dy * dy)
+        keep = (d2 <= r2) & (cand != qi)
+        qi, cand, d2 = qi[keep], cand[keep], d2[keep]
+        j, tj = order[cand], st[cand]
+        rows = order[a:b]
+        out["count"][rows] = np.bincount((qi - a) * t + tj, minlength=(b - a) * t).reshape(b - a, t)
+        o = np.lexsort((j, d2, qi))
+        qs = qi[o]
+        rank = np.arange(qs.shape[0], dtype=np.int64) - np.searchsorted(qs, np.arange(a, b, dtype=np.int64))[qs - a]
+        sel = rank < k
+        out["knn"][order[qs[sel]], rank[sel]] = j[o][sel]
+        key = (qi * t + tj)[o]
+        o = o[np.argsort(key, kind="stable")]          # ascending (i, type, d2, j)
+        key = (qi * t + tj)[o]
+        head = np.ones(key.shape[0], bool)
+        head[1:] = key[1:] != key[:-1]
+        out["nearest_of_type"][order[key[head] // t], key[head] % t] = j[o][head]
+        a = b
+    return out
+
+
+# ---- the device ----------------------------------------------------------------------------------
+def workspace_bytes(n, n_cells):
+    """Bytes of the one workspace of the two ops (include/hvn.h, NBR_GRID)."""
+    return 24 * n + 4 * (2 * n_cells + 1) + 4096
+
+
+class DeviceQuery:
+    """The tensors and the two ops of one device query; `run_grid` and `run_query` launch on the current stream without
+    synchronising (tools/neighbours_bench.py times them apart), `result` reads the three arrays back."""
+
+    def __init__(self, xy, types, radius, k, nr_types=None, device="cuda"):
+        import torch
+
+        from . import lib as L
+        from . import plan as PL
+
+        xy, types, r, k, t = _check(xy, types, radius, k, nr_types)     # raises before anything is allocated or launched
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("query_device needs a GPU device, got %r" % (device,))
+        n, g = xy.shape[0], grid(xy, r)
+        self.n, self.k, self.t, self.grid = n, k, t, g
+        with torch.cuda.device(self.device):
+            up = lambda a: torch.from_numpy(a if a.flags.writeable else a.copy()).to(self.device)  # noqa: E731  (torch warns on read-only arrays)
+            self.xy = up(xy)
+            self.types = None if types is None else up(types)
+            self.table = torch.tensor([g.x0, g.y0, g.c, r * r], dtype=torch.float64, device=self.device)
+            nbytes = workspace_bytes(n, g.ncx * g.ncy)
+            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.count = torch.empty((n, t), dtype=torch.int32, device=self.device)
+            self.knn = torch.empty((n, k), dtype=torch.int32, device=self.device)
+            self.nearest = torch.empty((n, t), dtype=torch.int32, device=self.device)
+        ops = []
+        for kind in (PL.OP_NBR_GRID, PL.OP_NBR_QUERY):
+            op = L.hvn_op()
+            op.kind, op.kh, op.kw, op.x.h = kind, g.ncy, g.ncx, n
+            op.w, op.x2.base, op.x2.sn = self.table.data_ptr(), self.ws.data_ptr(), nbytes
+            ops.append(op)
+        ops[0].x.base = self.xy.data_ptr()
+        ops[0].res.base = None if self.types is None else self.types.data_ptr()
+        ops[1].cout, ops[1]._rsv = t, k
+        ops[1].y.base, ops[1].y2.base, ops[1].res.base = self.count.data_ptr(), self.knn.data_ptr(), self.nearest.data_ptr()
+        self._ops = ops
+
+    def _run(self, i):
+        import torch
+
+        from . import lib as L
+
+        with torch.cuda.device(self.device):
+            L.call("hvn_run_op", ctypes.addressof(self._ops[i]), 1, L.stream_ptr(self.device))
+
+    def run_grid(self):
+        self._run(0)
+
+    def run_query(self):
+        self._run(1)
+
+    def result(self):
+        return {"count": self.count.cpu().numpy(), "knn": self.knn.cpu().numpy(), "nearest_of_type": self.nearest.cpu().numpy()}
+
+
+def query_device(xy, types, radius, k, nr_types=None, device="cuda"):
+    """`query_host` on the GPU: the same three arrays.  The grid is chosen here on the host; the device builds it and answers the
+    query (two ops on the current stream); the one synchronisation is the readback."""
+    q = DeviceQuery(xy, types, radius, k, nr_types, device)
+    q.run_grid()
+    q.run_query()
+    return q.result()
+
+
+def query(xy, types, radius, k, nr_types=None, device=None):
+    """`query_host` with device=None, `query_device` on `device` otherwise."""
+    if device is None:
+        return query_host(xy, types, radius, k, nr_types)
+    return query_device(xy, types, radius, k, nr_types, device)
+
+
+# ---- what a user reads ---------------------------------------------------------------------------
+def distances(xy, idx):
+    """float64 distances from point i to the positions idx[i, ...] (`knn` or `nearest_of_type`): sqrt(d2(i, j)) with the
+    definition's d2, inf where the index is -1."""
+    xy, idx = np.asarray(xy, np.float64), np.asarray(idx)
+    if idx.ndim != 2 or idx.shape[0] != xy.shape[0]:
+        raise ValueError("idx %s is not [N, m] for xy %s" % (idx.shape, xy.shape))
+    j = np.where(idx < 0, 0, idx)
+    dx, dy = xy[j, 0] - xy[:, None, 0], xy[j, 1] - xy[:, None, 1]
+    return np.where(idx < 0, np.inf, np.sqrt((dx * dx) + (dy * dy)))
+
+
+def edges(knn):
+    """The undirected edge list of the k-nearest graph: unique (min, max) position pairs, sorted; int32 [E, 2]."""
+    knn = np.asarray(knn)
+    i = np.repeat(np.arange(knn.shape[0], dtype=np.int64), knn.shape[1])
+    j = knn.reshape(-1).astype(np.int64)
+    i, j = i[j >= 0], j[j >= 0]
+    pairs = np.stack([np.minimum(i, j), np.maximum(i, j)], 1)
+    return np.unique(pairs, axis=0).astype(np.int32).reshape(-1, 2)
+
+
+def resolve(spec):
+    """What a `neighbours` argument of the pipeline names: None -> None (off), {"radius": r, "k": k} -> (r, k), in pixels of the
+    processed image.  ValueError / TypeError otherwise, before any work."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict) or set(spec) != {"radius", "k"}:
+        raise ValueError('neighbours=%r: None or {"radius": r, "k": k}' % (spec,))
+    _check(np.zeros((1, 2)), None, spec["radius"], spec["k"], None)
+    return float(spec["radius"]), int(spec["k"])
+
+
+def annotate(info, radius, k, nr_types, device=None):
+    """Adds "neighbours" to every entry of an instance dict (`post_proc.process` / `WsiInference.run`) and returns the dict.
+    Positions follow dict order; the centroids are the points, entry["type"] the types (nr_types=None: untyped, one column).
+    entry["neighbours"] = {"count": [T ints], "knn": [labels], "knn_dist": [floats], "nearest_of_type": [label | None],
+    "nearest_of_type_dist": [float | None]}: instance labels instead of positions, the padding of knn removed, plain Python values
+    (JSON-serialisable as they are).  An empty dict is returned unchanged.  device=None: `query_host`."""
+    if not info:
+        return info
+    labels = list(info)
+    xy = np.array([np.asarray(info[lab]["centroid"], np.float64).reshape(2) for lab in labels], np.float64).reshape(-1, 2)
+    types = None
+    if nr_types is not None:
+        raw = [info[lab]["type"] for lab in labels]
+        if any(v is None or isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in raw):
+            raise ValueError("nr_types = %r needs an integer type on every entry" % (nr_types,))
+        types = np.array(raw, np.int64)
+        if types.min() < 0 or types.max() >= nr_types:
+            raise ValueError("types outside [0, %d)" % nr_types)
+        types = types.astype(np.int32)
+    res = query(xy, types, radius, k, nr_types, device)
+    kd, nd = distances(xy, res["knn"]), distances(xy, res["nearest_of_type"])
+    count, knn, near = res["count"].tolist(), res["knn"].tolist(), res["nearest_of_type"].tolist()
+    kd, nd = kd.tolist(), nd.tolist()
+    for i, lab in enumerate(labels):
+        m = sum(1 for j in knn[i] if j >= 0)
+        info[lab]["neighbours"] = {"count": count[i], "knn": [labels[j] for j in knn[i][:m]], "knn_dist": kd[i][:m],
+                                   "nearest_of_type": [labels[j] if j >= 0 else None for j in near[i]],
+                                   "nearest_of_type_dist": [d if j >= 0 else None for j, d in zip(near[i], nd[i])]}
+    return info

@@ -38,6 +38,7 @@ from .knobs import knob
 OP_CONV0, OP_CONV, OP_UPADD, OP_HEAD, OP_PREDMAP, OP_WINO_IN, OP_WINO_OUT, OP_CHAIN = 1, 2, 3, 4, 5, 6, 7, 8
 OP_VIEW, OP_TTA = 9, 10     # test-time augmentation (tta.py): never part of a plan, issued around it by Engine.run_tta
 OP_STAIN_HIST, OP_STAIN_COMPACT, OP_STAIN_APPLY = 11, 12, 13     # stain normalisation (stain.py): never part of a plan
+OP_NBR_GRID, OP_NBR_QUERY = 14, 15     # nucleus neighbourhoods (neighbours.py): never part of a plan
 
 
 @dataclass

@@ -310,12 +310,18 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
     return out
 
 
-def process(pred_map, nr_types=None, return_centroids=False, contours="host", *, features=False, image=None):
+def process(pred_map, nr_types=None, return_centroids=False, contours="host", *, features=False, image=None, neighbours=None):
     """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32.  contours="device" traces the contours on
     the GPU (`trace_contours_device`) instead of on the host; the result is the same.  features=True adds "features" to every
-    entry of the dict (`features.derive`; it implies return_centroids); `image` (host uint8 [H,W,3], RGB) adds mean_rgb / std_rgb."""
+    entry of the dict (`features.derive`; it implies return_centroids); `image` (host uint8 [H,W,3], RGB) adds mean_rgb / std_rgb.
+    neighbours={"radius": r, "k": k} (pixels; it implies return_centroids) adds "neighbours" to every entry: `neighbours.annotate` of
+    the finished dict, the search on the GPU."""
+    from . import neighbours as NB
+
     if contours not in ("host", "device"):
         raise ValueError('contours must be "host" or "device", got %r' % (contours,))
+    nbr = NB.resolve(neighbours)
+    return_centroids = return_centroids or nbr is not None
     img_dev = None
     if image is not None:
         if not features:
@@ -335,4 +341,6 @@ def process(pred_map, nr_types=None, return_centroids=False, contours="host", *,
     if rec is not None:
         info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat,
                                feat_host=None if feat is None else feat[0].cpu().numpy(), with_colour=image is not None)
+        if nbr is not None:
+            NB.annotate(info, nbr[0], nbr[1], nr_types, device=pred.device)
     return pred_inst, info

@@ -1,0 +1,125 @@
+"""Times the neighbour search (hover_net_amd/neighbours.py, csrc/hvn_neighbours.hip) on one GPU next to its host path on the same
+box, for 10^5 and 10^6 synthetic centroids, and prints a small table plus ONE JSON line.
+
+    python tools/neighbours_bench.py [--reps 10] [--sizes 100000,1000000] [--out profiles/neighbours_bench.txt]
+
+Input: tissue-like density, about one nucleus per 20 x 20 px -- 70 % of the points uniform over a square of side 20 sqrt(N), 30 % in
+Gaussian clusters (sigma 40 px, 200 points each), five types; radius = 100 px, k = 5.  Per size, `query_device` is first checked
+against `query_host` with == on all three arrays (the host path is the one tests/test_neighbours_host.py holds to the O(N^2) oracle);
+a difference ends the run.
+legs (warm; one sample = the launches of one op between two HIP events on the current stream; median of --reps samples, min and max)
+    grid      HVN_OP_NBR_GRID: memset, count, three scan launches, scatter           -> points/s
+    query     HVN_OP_NBR_QUERY                                                       -> points/s and distance tests/s (the candidates of
+              the 3 x 3 cells of every point, counted on the host from the grid)
+    host      `query_host`, wall clock, once (numpy on the same box)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+RADIUS, K, TYPES = 100.0, 5, 5
+
+
+def points(n, seed):
+    rng = np.random.default_rng(seed)
+    side = 20.0 * np.sqrt(n)
+    n_cl = int(0.3 * n)
+    centres = rng.random((max(1, n_cl // 200), 2)) * side
+    cl = centres[rng.integers(0, centres.shape[0], n_cl)] + rng.normal(0.0, 40.0, (n_cl, 2))
+    xy = np.concatenate([rng.random((n - n_cl, 2)) * side, np.clip(cl, 0.0, side)])
+    return np.ascontiguousarray(xy[rng.permutation(n)]), rng.integers(0, TYPES, n).astype(np.int32), side
+
+
+def candidates(xy, g):
+    """Distance tests a 3 x 3 search needs: per point, the points in the nine cells around it (itself included)."""
+    from hover_net_amd import neighbours as NB
+
+    cx, cy = NB.cells(xy, g)
+    per = np.zeros((g.ncy + 2, g.ncx + 2), np.int64)
+    np.add.at(per, (cy + 1, cx + 1), 1)
+    box = sum(per[1 + dy:g.ncy + 1 + dy, 1 + dx:g.ncx + 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1))
+    return int((box * per[1:-1, 1:-1]).sum())
+
+
+def stat(xs):
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--sizes", default="100000,1000000")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+
+    from hover_net_amd import lib as L
+    from hover_net_amd import neighbours as NB
+
+    L.require_gpu()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    out, lines = {"reps": a.reps, "radius": RADIUS, "k": K, "types": TYPES}, []
+    lines.append("Neighbour search on one GPU, radius %g px, k = %d, %d types: ms, median [min .. max] of %d samples; host = query_host once, wall clock"
+                 % (RADIUS, K, TYPES, a.reps))
+    for n in (int(s) for s in a.sizes.split(",")):
+        xy, types, side = points(n, seed=n % 1000 + 3)
+        q = NB.DeviceQuery(xy, types, RADIUS, K, TYPES)
+        g = q.grid
+        q.run_grid()
+        q.run_query()
+        dev = q.result()
+        print("%d points: device done, host running" % n, flush=True)
+        t0 = time.perf_counter()
+        host = NB.query_host(xy, types, RADIUS, K, TYPES)
+        host_s = time.perf_counter() - t0
+        for name in ("count", "knn", "nearest_of_type"):
+            assert np.array_equal(dev[name], host[name]), "%d points: the device's %s differs from query_host's" % (n, name)
+        samp = {"grid": [], "query": []}
+        for it in range(a.reps + 2):
+            for name, fn in (("grid", q.run_grid), ("query", q.run_query)):
+                ms = timed(fn)
+                if it >= 2:
+                    samp[name].append(ms)
+        again = q.result()
+        assert all(np.array_equal(again[name], host[name]) for name in host), "the timed launches changed the result"
+        med = {name: statistics.median(v) for name, v in samp.items()}
+        tests = candidates(xy, g)
+        mean_nb = float(host["count"].sum(1).mean())
+        out[str(n)] = {"grid_ms": stat(samp["grid"]), "query_ms": stat(samp["query"]), "host_s": round(host_s, 2), "equal": True, "cells": [g.ncy, g.ncx],
+                       "cell_side": g.c, "mean_neighbours": round(mean_nb, 2), "max_neighbours": int(host["count"].sum(1).max()), "distance_tests": tests,
+                       "query_points_per_s": round(n / med["query"] * 1e3, 0), "query_tests_per_s": round(tests / med["query"] * 1e3, 0)}
+        lines.append("%d points in %.0f x %.0f px, %d x %d cells of %.4f px; %.1f neighbours per point on average, %d at most; device == host: yes"
+                     % (n, side, side, g.ncy, g.ncx, g.c, mean_nb, int(host["count"].sum(1).max())))
+        lines.append("    %-6s %10.4f  [%10.4f .. %10.4f]   %.3g points/s" % ("grid", med["grid"], min(samp["grid"]), max(samp["grid"]), n / med["grid"] * 1e3))
+        lines.append("    %-6s %10.4f  [%10.4f .. %10.4f]   %.3g points/s, %.3g distance tests/s (%d tests in the 3 x 3 cells)"
+                     % ("query", med["query"], min(samp["query"]), max(samp["query"]), n / med["query"] * 1e3, tests / med["query"] * 1e3, tests))
+        lines.append("    %-6s %10.1f   query_host, numpy (once): %.0f times grid + query" % ("host", host_s * 1e3, host_s * 1e3 / (med["grid"] + med["query"])))
+        del q
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps({"neighbours_bench": out}))
+
+
+if __name__ == "__main__":
+    main()
