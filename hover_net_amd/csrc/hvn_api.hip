@@ -133,7 +133,7 @@ static int stain_image(const char *what, const hvn_op *op, const hvn_view &v, in
     return 0;
 }
 
-// what the two NBR ops share: the table, the workspace, N and the grid; 0 = accepted
+// what the NBR ops share: the table, the workspace, N and the grid; 0 = accepted
 static int nbr_common(const char *what, const hvn_op *op, int batch)
 {
     const int N = op->x.h;
@@ -459,6 +459,24 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if (int rc = nbr_common("nbr_query", op, batch)) return rc;
         if (((uintptr_t)a.count | (uintptr_t)a.knn | (uintptr_t)a.nearest) & 3) return hvn_fail(HVN_E_ARG, "nbr_query: misaligned count, knn or nearest (4)");
         return hvn_launch_status(hvn_launch_nbr_query(a, s), "nbr_query");
+    }
+    case HVN_OP_NBR_CLUSTER: {
+        NbrClusterArgs a;
+        a.table = (const double *)op->w;
+        a.workspace = op->x2.base;
+        a.workspace2 = op->res.base;
+        a.label = (int *)op->y.base; a.degree = (int *)op->y2.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.min_pts = op->cout; a.mask = (unsigned)op->groups;
+        if (!a.workspace || !a.workspace2 || !a.label || !a.degree) return hvn_fail(HVN_E_ARG, "nbr_cluster: null pointer");
+        if (a.min_pts < 1) return hvn_fail(HVN_E_ARG, "nbr_cluster: min_pts = %d, below 1", a.min_pts);
+        if (a.mask == 0) return hvn_fail(HVN_E_ARG, "nbr_cluster: a type mask of 0 selects no point");
+        if (a.min_pts > HVN_NBR_CLUSTER_MAX_MIN_PTS) return hvn_fail(HVN_E_SIZE, "nbr_cluster: min_pts = %d above 2^26", a.min_pts);
+        if (int rc = nbr_common("nbr_cluster", op, batch)) return rc;
+        if (((uintptr_t)a.label | (uintptr_t)a.degree) & 3) return hvn_fail(HVN_E_ARG, "nbr_cluster: misaligned label or degree (4)");
+        if ((uintptr_t)a.workspace2 & 7) return hvn_fail(HVN_E_ARG, "nbr_cluster: misaligned second workspace (8)");
+        if ((long)op->res.sn < HVN_NBR_CLUSTER_WORKSPACE_BYTES(a.N))
+            return hvn_fail(HVN_E_SIZE, "nbr_cluster: second workspace of %ld bytes, %ld needed", (long)op->res.sn, HVN_NBR_CLUSTER_WORKSPACE_BYTES(a.N));
+        return hvn_launch_status(hvn_launch_nbr_cluster(a, s), "nbr_cluster");
     }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);

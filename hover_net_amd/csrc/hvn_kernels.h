@@ -219,6 +219,34 @@ struct NbrWorkspace {
     double *sx, *sy;
     int *spos, *stype, *cell_start, *cursor, *bsum;
 };
+// the carve-up of that workspace, for every launcher that reads it (hvn_neighbours.hip, hvn_clusters.hip)
+static inline NbrWorkspace hvn_nbr_workspace(void *ws, long N, long cells)
+{
+    NbrWorkspace w;
+    w.sx = (double *)ws;
+    w.sy = w.sx + N;
+    w.spos = (int *)(w.sy + N);
+    w.stype = w.spos + N;
+    w.cell_start = w.stype + N;
+    w.cursor = w.cell_start + cells + 1;
+    w.bsum = w.cursor + cells;
+    return w;
+}
+#ifdef __HIPCC__
+// the cell coordinate of v on one axis: the quotient is brought into [0, 4096] as a double BEFORE the conversion (a NaN compares false
+// and becomes 0) and into [0, n) as an integer after it
+__device__ __forceinline__ int hvn_nbr_axis(double v, double v0, double c, int n)
+{
+    double q = floor(__ddiv_rn(__dsub_rn(v, v0), c));
+    q = q >= 0.0 ? q : 0.0;            // NaN and negatives
+    q = q <= 4096.0 ? q : 4096.0;
+    int i = (int)q;
+    i = i < 0 ? 0 : i;
+    return i > n - 1 ? n - 1 : i;
+}
+__device__ __forceinline__ int hvn_nbr_clamp(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }      // a cell_start value into [0, N]
+__device__ __forceinline__ bool hvn_nbr_less(double d, int j, double D, int J) { return d < D || (d == D && j < J); }   // the total order (d2, j)
+#endif
 struct NbrGridArgs {
     const double *xy;           // [N][2] = (x, y)
     const int *types;           // [N] or NULL (all 0)
@@ -234,6 +262,19 @@ struct NbrQueryArgs {
     int N, ncy, ncx, T, k;
 };
 int hvn_launch_nbr_query(const NbrQueryArgs &a, hipStream_t stream);
+// hvn_clusters.hip: DBSCAN over that grid (hover_net_amd/clusters.py); the second workspace, 8-byte aligned, by slot (the cell-ordered
+// index): the union-find parent, the smallest position of a root's cores, the degree (int32 [N] each)
+#define HVN_NBR_CLUSTER_MAX_MIN_PTS (1 << 26)
+#define HVN_NBR_CLUSTER_WORKSPACE_BYTES(N) (12L * (N))
+struct NbrClusterArgs {
+    const double *table;
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    void *workspace2;           // HVN_NBR_CLUSTER_WORKSPACE_BYTES(N); every word read is written first
+    int *label, *degree;        // [N] each, by position
+    int N, ncy, ncx, min_pts;
+    unsigned mask;              // bit t selects type t; 0xFFFFFFFF selects every point whatever its type
+};
+int hvn_launch_nbr_cluster(const NbrClusterArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

@@ -35,17 +35,7 @@
 #define NB_BLOCK 4096         // cells per scan block
 #define NB_NONE 0x7FFFFFFF
 
-__device__ __forceinline__ int nb_axis(double v, double v0, double c, int n)
-{
-    double q = floor(__ddiv_rn(__dsub_rn(v, v0), c));
-    q = q >= 0.0 ? q : 0.0;            // NaN and negatives
-    q = q <= 4096.0 ? q : 4096.0;
-    int i = (int)q;
-    i = i < 0 ? 0 : i;
-    return i > n - 1 ? n - 1 : i;
-}
-
-__device__ __forceinline__ int nb_clamp(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
+// hvn_nbr_axis, hvn_nbr_clamp, hvn_nbr_less and the workspace carve-up live in hvn_kernels.h: hvn_clusters.hip reads the same grid
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NB_T) void nb_count(const double *__restrict__ xy, const double *__restrict__ table, int *__restrict__ cursor, int N, int ncy,
@@ -53,7 +43,7 @@ __global__ __launch_bounds__(NB_T) void nb_count(const double *__restrict__ xy, 
 {
     const double x0 = table[0], y0 = table[1], c = table[2];
     for (long i = (long)blockIdx.x * NB_T + threadIdx.x; i < N; i += (long)gridDim.x * NB_T) {
-        const int cx = nb_axis(xy[2 * i], x0, c, ncx), cy = nb_axis(xy[2 * i + 1], y0, c, ncy);
+        const int cx = hvn_nbr_axis(xy[2 * i], x0, c, ncx), cy = hvn_nbr_axis(xy[2 * i + 1], y0, c, ncy);
         atomicAdd(cursor + (long)cy * ncx + cx, 1);
     }
 }
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(NB_T) void nb_scatter(const double *__restrict__ xy
     const double x0 = table[0], y0 = table[1], c = table[2];
     for (long i = (long)blockIdx.x * NB_T + threadIdx.x; i < N; i += (long)gridDim.x * NB_T) {
         const double x = xy[2 * i], y = xy[2 * i + 1];
-        const int cx = nb_axis(x, x0, c, ncx), cy = nb_axis(y, y0, c, ncy);
+        const int cx = hvn_nbr_axis(x, x0, c, ncx), cy = hvn_nbr_axis(y, y0, c, ncy);
         const int slot = atomicAdd(cursor + (long)cy * ncx + cx, 1);
         if ((unsigned)slot < (unsigned)N) {
             sx[slot] = x;
@@ -144,23 +134,10 @@ __global__ __launch_bounds__(NB_T) void nb_scatter(const double *__restrict__ xy
     }
 }
 
-static NbrWorkspace nb_workspace(void *ws, long N, long cells)
-{
-    NbrWorkspace w;
-    w.sx = (double *)ws;
-    w.sy = w.sx + N;
-    w.spos = (int *)(w.sy + N);
-    w.stype = w.spos + N;
-    w.cell_start = w.stype + N;
-    w.cursor = w.cell_start + cells + 1;
-    w.bsum = w.cursor + cells;
-    return w;
-}
-
 int hvn_launch_nbr_grid(const NbrGridArgs &a, hipStream_t stream)
 {
     const long cells = (long)a.ncy * a.ncx;
-    const NbrWorkspace w = nb_workspace(a.workspace, a.N, cells);
+    const NbrWorkspace w = hvn_nbr_workspace(a.workspace, a.N, cells);
     const int nblocks = (int)((cells + NB_BLOCK - 1) / NB_BLOCK);
     const long pb = ((long)a.N + NB_T - 1) / NB_T;
     const dim3 pgrid((unsigned)(pb < 2048 ? pb : 2048));
@@ -174,8 +151,6 @@ int hvn_launch_nbr_grid(const NbrGridArgs &a, hipStream_t stream)
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool nb_less(double d, int j, double D, int J) { return d < D || (d == D && j < J); }
-
 struct NbrQueryDev {
     const double *sx, *sy, *table;
     const int *spos, *stype, *cell_start;
@@ -203,8 +178,8 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
         qx = a.sx[q];
         qy = a.sy[q];
         qpos = a.spos[q];
-        cx = nb_axis(qx, x0, c, a.ncx);
-        cy = nb_axis(qy, y0, c, a.ncy);
+        cx = hvn_nbr_axis(qx, x0, c, a.ncx);
+        cy = hvn_nbr_axis(qy, y0, c, a.ncy);
     }
     double bd[KM], td[TM];
     int bj[KM], tb[TM], cnt[TM];
@@ -226,8 +201,8 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
         if (valid && yy >= 0 && yy < a.ncy) {
             const long row = (long)yy * a.ncx;
             const int ca = cx > 0 ? cx - 1 : 0, cb = cx + 1 < a.ncx ? cx + 1 : a.ncx - 1;
-            lo = nb_clamp(a.cell_start[row + ca], N);
-            hi = nb_clamp(a.cell_start[row + cb + 1], N);
+            lo = hvn_nbr_clamp(a.cell_start[row + ca], N);
+            hi = hvn_nbr_clamp(a.cell_start[row + cb + 1], N);
             if (hi <= lo) {
                 lo = NB_NONE;
                 hi = 0;
@@ -266,12 +241,12 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
                 const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
                 const int j = tj[i];
                 if (!(d2 <= r2) || j == qpos) continue;
-                if (nb_less(d2, j, bd[KM - 1], bj[KM - 1])) {
+                if (hvn_nbr_less(d2, j, bd[KM - 1], bj[KM - 1])) {
                     double cd = d2;
                     int cj = j;
 #pragma unroll
                     for (int s = 0; s < KM; ++s) {
-                        const bool sw = nb_less(cd, cj, bd[s], bj[s]);
+                        const bool sw = hvn_nbr_less(cd, cj, bd[s], bj[s]);
                         const double od = bd[s];
                         const int oj = bj[s];
                         bd[s] = sw ? cd : od;
@@ -285,7 +260,7 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
                 for (int t = 0; t < TM; ++t) {
                     const bool m = ty_ == t;
                     cnt[t] += m ? 1 : 0;
-                    const bool b = m && nb_less(d2, j, td[t], tb[t]);
+                    const bool b = m && hvn_nbr_less(d2, j, td[t], tb[t]);
                     td[t] = b ? d2 : td[t];
                     tb[t] = b ? j : tb[t];
                 }
@@ -308,7 +283,7 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
 
 int hvn_launch_nbr_query(const NbrQueryArgs &a, hipStream_t stream)
 {
-    const NbrWorkspace w = nb_workspace(a.workspace, a.N, (long)a.ncy * a.ncx);
+    const NbrWorkspace w = hvn_nbr_workspace(a.workspace, a.N, (long)a.ncy * a.ncx);
     NbrQueryDev d;
     d.sx = w.sx; d.sy = w.sy; d.table = a.table;
     d.spos = w.spos; d.stype = w.stype; d.cell_start = w.cell_start;

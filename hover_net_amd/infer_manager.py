@@ -153,10 +153,13 @@ class InferManager:
         `stain.StainFit` of a target image -- every image is fitted on itself and Macenko-normalised on the GPU before its patches
         are cut (hover_net_amd/stain.py); neighbours (default None): {"radius": r, "k": k} in pixels -- every nucleus of `json/` gains
         "neighbours" (`neighbours.annotate`: typed counts within r, the k nearest nuclei and the nearest of every type, with distances).
+        clusters (default None): {"radius": r, "min_pts": m} with an optional "types": [ints], in pixels -- every nucleus of `json/` gains
+        "cluster" (`clusters.annotate`: the id of its DBSCAN cluster's root nucleus or null, whether it is a core, its degree).
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
+        from . import clusters as CL
         from . import neighbours as NB
         from . import stain as ST
         from . import tta as TT
@@ -173,6 +176,8 @@ class InferManager:
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         neighbours = run_args.get("neighbours")
         NB.resolve(neighbours)                              # likewise
+        clusters = run_args.get("clusters")
+        CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -187,7 +192,8 @@ class InferManager:
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
             **({"return_features": True} if save_features else {}), **({"tta": tta} if tta is not None else {}),
             **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-            **({"neighbours": neighbours} if neighbours is not None else {})))
+            **({"neighbours": neighbours} if neighbours is not None else {}),
+            **({"clusters": clusters} if clusters is not None else {})))
         done = []
         self.rounds = []                                   # files per caching round (inspected by the tests)
         while pending:
@@ -287,10 +293,12 @@ class WsiManager(InferManager):
         hover_net_amd.tta -- every stage-1 network step averages the views' outputs on the GPU (`Engine.run_tta`); stain_norm (default None): "macenko"
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
         (`WsiInference(stain_norm=...)`); neighbours (default None): {"radius": r, "k": k} in pixels at proc_mag -- every nucleus of the json gains
-        "neighbours" (`neighbours.annotate` of the merged slide dict, in slide coordinates).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        "neighbours" (`neighbours.annotate` of the merged slide dict, in slide coordinates); clusters (default None): {"radius": r, "min_pts": m} with an
+        optional "types": [ints], in pixels at proc_mag -- every nucleus of the json gains "cluster" (`clusters.annotate` of the merged slide dict).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
+        from . import clusters as CL
         from . import neighbours as NB
         from . import stain as ST
         from . import tta as TT
@@ -299,6 +307,8 @@ class WsiManager(InferManager):
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         neighbours = run_args.get("neighbours")
         NB.resolve(neighbours)                              # likewise
+        clusters = run_args.get("clusters")
+        CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -345,7 +355,8 @@ class WsiManager(InferManager):
                                                  **({"features": True} if run_args.get("save_features", False) else {}),
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-                                                 **({"neighbours": neighbours} if neighbours is not None else {}))
+                                                 **({"neighbours": neighbours} if neighbours is not None else {}),
+                                                 **({"clusters": clusters} if clusters is not None else {}))
                     _inst_map, inst_info = wsi.run(slide, mask)
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)

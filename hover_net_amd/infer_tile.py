@@ -334,7 +334,7 @@ def run_sharded(items, step_fn, batch_size, gather=True):
 
 # --------------------------------------------------------------------------------------------
 def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384, *,
-                   return_features=False, tta=None, stain_norm=None, neighbours=None):
+                   return_features=False, tta=None, stain_norm=None, neighbours=None, clusters=None):
     """images: list of uint8 [H,W,3] arrays (RGB).  Returns a list of (pred_inst int32 [H,W] numpy, inst_info_dict | None)
     in input order: complete on rank 0 (the writer); the other ranks hold their own images' results and None elsewhere.
     `return_raw=True` appends the stitched float32 prediction map [H,W,3|4] to each tuple (`--save_raw_map`,
@@ -351,6 +351,8 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     `neighbours`: None or {"radius": r, "k": k} in pixels (implies the instance dict): every entry of every image's dict gains
     "neighbours" (`neighbours.annotate` of the finished dict, the search on the GPU where the model is on one).  It runs on rank 0,
     where the dicts already are; no collective is added, and the other ranks' own results stay without the entry.
+    `clusters`: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels; implies the instance dict; "types" needs
+    nr_types): every entry gains "cluster" (`clusters.annotate` of the finished dict), on rank 0 like `neighbours`, no collective.
     The images are worked off in groups of at most `max_patches` network patches (3.6 GB of uint8 patches + 1.7 GB of maps at the
     default), so that a large cache round of `process_file_list` never has all its overlapping patches in HBM at once; every rank
     forms the same groups (the collectives inside stay matched)."""
@@ -366,6 +368,11 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         from . import neighbours as NB
 
         neighbours = NB.resolve(neighbours)
+        return_centroids = True
+    if clusters is not None:
+        from . import clusters as CL
+
+        clusters = CL.resolve(clusters, typed=nr_types is not None)
         return_centroids = True
     win = 270 if (model.module if hasattr(model, "module") and not hasattr(model, "engine") else model).mode == "original" else 256
     msk = 80 if win == 270 else 164
@@ -389,12 +396,15 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
                                                     return_raw, **more)):
             out[i] = res
-    if neighbours is not None and _dist()[1] == 0:
+    if (neighbours is not None or clusters is not None) and _dist()[1] == 0:
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         dev = next(net.parameters()).device
         for res in out:
             if res is not None and res[1] is not None:
-                NB.annotate(res[1], neighbours[0], neighbours[1], nr_types, device=dev if dev.type == "cuda" else None)
+                if neighbours is not None:
+                    NB.annotate(res[1], neighbours[0], neighbours[1], nr_types, device=dev if dev.type == "cuda" else None)
+                if clusters is not None:
+                    CL.annotate(res[1], clusters[0], clusters[1], nr_types, clusters[2], device=dev if dev.type == "cuda" else None)
     return out
 
 

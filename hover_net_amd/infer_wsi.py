@@ -511,8 +511,11 @@ class DeviceMerger:
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
-                 stain_norm=None, neighbours=None):
-        """neighbours: None or {"radius": r, "k": k} in pixels of the processed slide: every entry of the instance dict gains
+                 stain_norm=None, neighbours=None, clusters=None):
+        """clusters: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels of the processed slide; "types" needs
+        nr_types): every entry of the instance dict gains "cluster" (`clusters.annotate`), computed ONCE on the final dict after the merge,
+        in slide coordinates, so clusters cross tile seams; on rank 0, no collective.
+        neighbours: None or {"radius": r, "k": k} in pixels of the processed slide: every entry of the instance dict gains
         "neighbours" (`neighbours.annotate`), computed ONCE on the final dict after the merge, in slide coordinates (the tiles' origins
         are already in the centroids), so neighbours are found across tile seams.  It runs on rank 0, where the dict lives (on the
         GPU where the model is on one); no collective is added.
@@ -549,6 +552,9 @@ class WsiInference:
         from . import neighbours as NB
 
         self.neighbours = NB.resolve(neighbours)
+        from . import clusters as CL
+
+        self.clusters = CL.resolve(clusters, typed=nr_types is not None)
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -904,9 +910,13 @@ class WsiInference:
         return self._with_neighbours((merger.inst_map, merger.inst_info))
 
     def _with_neighbours(self, out):
-        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours`, the dict's entries gain "neighbours"."""
+        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours` / `clusters`, the dict's entries gain "neighbours" / "cluster"."""
         if self.neighbours is not None and out[1]:
             from . import neighbours as NB
 
             NB.annotate(out[1], self.neighbours[0], self.neighbours[1], self.nr_types, device=self.device if self.device.type == "cuda" else None)
+        if self.clusters is not None and out[1]:
+            from . import clusters as CL
+
+            CL.annotate(out[1], self.clusters[0], self.clusters[1], self.nr_types, self.clusters[2], device=self.device if self.device.type == "cuda" else None)
         return out

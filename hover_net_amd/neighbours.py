@@ -88,6 +88,17 @@ def _check(xy, types, radius, k, nr_types):
     return np.ascontiguousarray(xy), None if types is None else np.ascontiguousarray(types), r, int(k), t
 
 
+def d2_of(xi, yi, xj, yj):
+    """The docstring's d2(i, j) for coordinates or arrays of them (clusters.py takes it from here)."""
+    dx, dy = xj - xi, yj - yi
+    return (dx * dx) + (dy * dy)
+
+
+def r2_of(r):
+    """The docstring's r2 for a checked radius."""
+    return r * r
+
+
 def grid(xy, radius):
     """The grid of the module docstring for checked inputs -> Grid(x0, y0, c, ncx, ncy)."""
     x0, y0 = float(xy[:, 0].min()), float(xy[:, 1].min())
@@ -118,7 +129,7 @@ def query_host(xy, types, radius, k, nr_types=None):
     xy, types, r, k, t = _check(xy, types, radius, k, nr_types)
     n = xy.shape[0]
     g = grid(xy, r)
-    r2 = r * r
+    r2 = r2_of(r)
     cx, cy = cells(xy, g)
     cell = cy * g.ncx + cx
     order = np.argsort(cell, kind="stable")
@@ -147,8 +158,7 @@ def query_host(xy, types, radius, k, nr_types=None):
             qi.append(np.repeat(np.arange(a, b, dtype=np.int64), lens))
             cand.append(np.repeat(lo[row, a:b] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64))
         qi, cand = np.concatenate(qi), np.concatenate(cand)
-        dx, dy = sx[cand] - sx[qi], sy[cand] - sy[qi]
-        d2 = (dx * dx) + (dy * dy)
+        d2 = d2_of(sx[qi], sy[qi], sx[cand], sy[cand])
         keep = (d2 <= r2) & (cand != qi)
         qi, cand, d2 = qi[keep], cand[keep], d2[keep]
         j, tj = order[cand], st[cand]

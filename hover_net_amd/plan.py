@@ -39,6 +39,7 @@ OP_CONV0, OP_CONV, OP_UPADD, OP_HEAD, OP_PREDMAP, OP_WINO_IN, OP_WINO_OUT, OP_CH
 OP_VIEW, OP_TTA = 9, 10     # test-time augmentation (tta.py): never part of a plan, issued around it by Engine.run_tta
 OP_STAIN_HIST, OP_STAIN_COMPACT, OP_STAIN_APPLY = 11, 12, 13     # stain normalisation (stain.py): never part of a plan
 OP_NBR_GRID, OP_NBR_QUERY = 14, 15     # nucleus neighbourhoods (neighbours.py): never part of a plan
+OP_NBR_CLUSTER = 16     # nucleus clusters over the same grid (clusters.py): never part of a plan
 
 
 @dataclass

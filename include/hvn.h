@@ -39,7 +39,8 @@ typedef struct hvn_view {
 } hvn_view;
 
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
-       HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15 };
+       HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
+       HVN_OP_NBR_CLUSTER = 16 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -140,6 +141,24 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           numbers, no access outside the arrays.
  *           HVN_E_ARG: a null pointer (types excepted), xy / table / workspace not 8-byte or an int32 array not 4-byte aligned, batch
  *           != 1, N < 1, k or T outside 1..16, kh or kw < 1.  HVN_E_SIZE: N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn too small.
+ *     NBR_CLUSTER    DBSCAN clusters over the same grid (hover_net_amd/clusters.py holds the definition; csrc/hvn_clusters.hip).  Runs
+ *           after NBR_GRID on the same stream and reads the workspace as that op left it for the same N, kh, kw and table (x.base is
+ *           not read); x.h, kh, kw, w, x2.base and x2.sn are the shared fields above.  cout = min_pts in [1, 2^26]; groups = the type
+ *           mask: bit t selects type t, -1 selects every point whatever its type, and with any other mask a type outside [0, 16) is
+ *           unselected; y.base = int32 label [N], y2.base = int32 degree [N] (4-byte aligned); res.base = a second device workspace of
+ *           the op's own (8-byte aligned) of res.sn BYTES >= 12 N: per slot of the cell order the union-find parent, the smallest
+ *           position among a root's cores and the degree (int32 [N] each).  The op writes every word of it that it reads: its content
+ *           before the call does not matter.  With the neighbour relation of NBR_QUERY (d2 <= r2): degree[i] = 1 + the number of
+ *           selected neighbours of a selected i, 0 for an unselected i; i is a core when degree[i] >= min_pts; a cluster is a connected
+ *           component of the cores and label = the smallest position among them; a selected non-core with a core neighbour takes the
+ *           label of its (d2, j)-smallest core neighbour j; every other point gets -1.  Integer sums, set unions and minima under a
+ *           total order: the outputs are a function of the inputs alone.  No loop waits for another thread: a find steps only to a
+ *           strictly smaller slot, a failed hook is retried only on a strictly smaller value, candidate loops are bounded by
+ *           cell_start values clamped to [0, N] and every output row by N: a workspace NBR_GRID did not fill gives wrong numbers, no
+ *           access outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer, label / degree not 4-byte or a table / workspace not 8-byte aligned, batch != 1, N < 1,
+ *           min_pts < 1, a mask of 0, kh or kw < 1.  HVN_E_SIZE: min_pts > 2^26, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
+ *           or res.sn too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
