@@ -478,6 +478,23 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
             return hvn_fail(HVN_E_SIZE, "nbr_cluster: second workspace of %ld bytes, %ld needed", (long)op->res.sn, HVN_NBR_CLUSTER_WORKSPACE_BYTES(a.N));
         return hvn_launch_status(hvn_launch_nbr_cluster(a, s), "nbr_cluster");
     }
+    case HVN_OP_NBR_DENSITY: {
+        NbrDensityArgs a;
+        a.table = (const double *)op->w;
+        a.raster = (const double *)op->bias;
+        a.workspace = op->x2.base;
+        a.count = (int *)op->y.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.H = op->y.h; a.W = op->y.w;
+        if (!a.workspace || !a.count || !a.raster) return hvn_fail(HVN_E_ARG, "nbr_density: null pointer");
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_density: %d types outside 1..16", a.T);
+        if (a.H < 1 || a.W < 1) return hvn_fail(HVN_E_ARG, "nbr_density: a raster of %d x %d nodes", a.H, a.W);
+        if (a.H > HVN_NBR_DENSITY_MAX_AXIS || a.W > HVN_NBR_DENSITY_MAX_AXIS || (long)a.T * a.H * a.W > HVN_NBR_DENSITY_MAX_NODES)
+            return hvn_fail(HVN_E_SIZE, "nbr_density: %d planes of %d x %d nodes, more than 16384 per axis or 2^28 in all", a.T, a.H, a.W);
+        if (int rc = nbr_common("nbr_density", op, batch)) return rc;
+        if ((uintptr_t)a.count & 3) return hvn_fail(HVN_E_ARG, "nbr_density: misaligned count (4)");
+        if ((uintptr_t)a.raster & 7) return hvn_fail(HVN_E_ARG, "nbr_density: misaligned raster table (8)");
+        return hvn_launch_status(hvn_launch_nbr_density(a, s), "nbr_density");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

@@ -275,6 +275,17 @@ struct NbrClusterArgs {
     unsigned mask;              // bit t selects type t; 0xFFFFFFFF selects every point whatever its type
 };
 int hvn_launch_nbr_cluster(const NbrClusterArgs &a, hipStream_t stream);
+// hvn_density.hip: typed counts within the radius of every node of a regular raster (hover_net_amd/density.py)
+#define HVN_NBR_DENSITY_MAX_AXIS 16384
+#define HVN_NBR_DENSITY_MAX_NODES (1L << 28)     // T * H * W
+struct NbrDensityArgs {
+    const double *table;        // {x0, y0, c, r2}, as for the grid
+    const double *raster;       // {ox, oy, s}: node (u, v) is at (ox + u * s, oy + v * s)
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    int *count;                 // [T][H][W]; every element is written
+    int N, ncy, ncx, T, H, W;
+};
+int hvn_launch_nbr_density(const NbrDensityArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

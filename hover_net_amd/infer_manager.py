@@ -155,11 +155,16 @@ class InferManager:
         "neighbours" (`neighbours.annotate`: typed counts within r, the k nearest nuclei and the nearest of every type, with distances).
         clusters (default None): {"radius": r, "min_pts": m} with an optional "types": [ints], in pixels -- every nucleus of `json/` gains
         "cluster" (`clusters.annotate`: the id of its DBSCAN cluster's root nucleus or null, whether it is a core, its degree).
+        density (default None): {"radius": r, "step": s}, in pixels, `step` an integer >= 1 -- rank 0 also writes `density/<name>.npz` with
+        `count` (int32 [T, H, W]: nuclei of every type within r of every node of a raster with one node per step x step pixels), `origin`,
+        `step` and `radius` (`density.of_info` of the image's finished dict and size, on the GPU where the model is on one); `json/` is as
+        without it.
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
         from . import clusters as CL
+        from . import density as DN
         from . import neighbours as NB
         from . import stain as ST
         from . import tta as TT
@@ -178,6 +183,7 @@ class InferManager:
         NB.resolve(neighbours)                              # likewise
         clusters = run_args.get("clusters")
         CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
+        density = DN.resolve(run_args.get("density"))       # likewise
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -186,7 +192,7 @@ class InferManager:
 
         pending = list_files(input_dir)
         if rank == 0:
-            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()):
+            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if density is not None else ()):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
@@ -218,8 +224,17 @@ class InferManager:
                 pred_inst, inst_info = res[0], res[1]
                 raw_map = res[2] if save_raw_map else None
                 self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
+                if density is not None:
+                    DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], density))
                 done.append(name)
         return done
+
+    def _density_of(self, inst_info, size_hw, density):
+        """`density.of_info` of a finished dict for a resolved `density` argument, on the GPU where the model is on one."""
+        from . import density as DN
+
+        dev = self._collective_device()
+        return DN.of_info(inst_info, size_hw, density[0], density[1], self.nr_types, device=dev if dev is not None and dev.type == "cuda" else None)
 
     def _collective_device(self):
         try:
@@ -294,11 +309,14 @@ class WsiManager(InferManager):
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
         (`WsiInference(stain_norm=...)`); neighbours (default None): {"radius": r, "k": k} in pixels at proc_mag -- every nucleus of the json gains
         "neighbours" (`neighbours.annotate` of the merged slide dict, in slide coordinates); clusters (default None): {"radius": r, "min_pts": m} with an
-        optional "types": [ints], in pixels at proc_mag -- every nucleus of the json gains "cluster" (`clusters.annotate` of the merged slide dict).  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        optional "types": [ints], in pixels at proc_mag -- every nucleus of the json gains "cluster" (`clusters.annotate` of the merged slide dict);
+        density (default None): {"radius": r, "step": s}, in pixels at proc_mag, `step` an integer >= 1 -- rank 0 also writes `density/<name>.npz` with `count`
+        (int32 [T, H, W]), `origin`, `step` and `radius`: `WsiInference(density=...)`'s map of the merged slide dict over the processed slide; the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
         from . import clusters as CL
+        from . import density as DN
         from . import neighbours as NB
         from . import stain as ST
         from . import tta as TT
@@ -309,6 +327,8 @@ class WsiManager(InferManager):
         NB.resolve(neighbours)                              # likewise
         clusters = run_args.get("clusters")
         CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
+        density = run_args.get("density")
+        density_rs = DN.resolve(density)                    # likewise
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -323,6 +343,8 @@ class WsiManager(InferManager):
                 os.makedirs(output_dir + "/thumb/", exist_ok=True)
             if save_mask:
                 os.makedirs(output_dir + "/mask/", exist_ok=True)
+            if density is not None:
+                os.makedirs(output_dir + "/density/", exist_ok=True)
         status = {}
         for wsi_path in sorted(glob.glob(input_dir + "/*")):
             if os.path.isdir(wsi_path):
@@ -348,6 +370,7 @@ class WsiManager(InferManager):
                     viz.save_png("%s/thumb/%s.png" % (output_dir, name), slide.thumbnail(32))
                 if self.wsi_fn is not None:
                     _inst_map, inst_info = self.wsi_fn(slide, mask)
+                    dmap = None if density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], density_rs)
                 else:
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
@@ -356,10 +379,14 @@ class WsiManager(InferManager):
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
                                                  **({"neighbours": neighbours} if neighbours is not None else {}),
-                                                 **({"clusters": clusters} if clusters is not None else {}))
+                                                 **({"clusters": clusters} if clusters is not None else {}),
+                                                 **({"density": density} if density is not None else {}))
                     _inst_map, inst_info = wsi.run(slide, mask)
+                    dmap = wsi.density
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)
+                    if density is not None:
+                        DN.save("%s/density/%s.npz" % (output_dir, name), dmap)
                 status[name] = "done"
             except Exception:                                 # noqa: BLE001  (the reference logs and moves on to the next slide)
                 logging.exception("Crash")

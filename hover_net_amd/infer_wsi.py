@@ -511,8 +511,13 @@ class DeviceMerger:
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
-                 stain_norm=None, neighbours=None, clusters=None):
-        """clusters: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels of the processed slide; "types" needs
+                 stain_norm=None, neighbours=None, clusters=None, density=None):
+        """density: None or {"radius": r, "step": s} (pixels of the processed slide; `step` an integer >= 1): after the merge, once per
+        slide, `self.density` holds the `density.DensityMap` of the finished dict over the slide's processed size (`density.of_info`:
+        typed nucleus counts within r of every node of a raster with one node per step x step pixels), in slide coordinates, so a
+        node's disc crosses tile seams; on rank 0 (None elsewhere and before the first slide), on the GPU where the model is on one,
+        no collective.  The return value of `run` is unchanged.
+        clusters: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels of the processed slide; "types" needs
         nr_types): every entry of the instance dict gains "cluster" (`clusters.annotate`), computed ONCE on the final dict after the merge,
         in slide coordinates, so clusters cross tile seams; on rank 0, no collective.
         neighbours: None or {"radius": r, "k": k} in pixels of the processed slide: every entry of the instance dict gains
@@ -555,6 +560,10 @@ class WsiInference:
         from . import clusters as CL
 
         self.clusters = CL.resolve(clusters, typed=nr_types is not None)
+        from . import density as DN
+
+        self.density_spec = DN.resolve(density)
+        self.density = None                        # the last slide's DensityMap (rank 0), with `density`
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -876,6 +885,10 @@ class WsiInference:
             shape = pred_map.shape[:2]
         shape = np.array([int(shape[0]), int(shape[1])])
         self._shape = shape
+        if self.density_spec is not None:          # a raster the op would refuse raises here, before any tile is processed
+            from . import density as DN
+
+            DN._check_raster(DN.raster_of(shape, self.density_spec[1]), 1 if self.nr_types is None else int(self.nr_types))
         if mask is None:
             mask = np.ones((max(1, int(shape[0]) // 32), max(1, int(shape[1]) // 32)), np.uint8)
 
@@ -910,7 +923,8 @@ class WsiInference:
         return self._with_neighbours((merger.inst_map, merger.inst_info))
 
     def _with_neighbours(self, out):
-        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours` / `clusters`, the dict's entries gain "neighbours" / "cluster"."""
+        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours` / `clusters`, the dict's entries gain "neighbours" / "cluster"; with
+        `density`, `self.density` is set."""
         if self.neighbours is not None and out[1]:
             from . import neighbours as NB
 
@@ -919,4 +933,9 @@ class WsiInference:
             from . import clusters as CL
 
             CL.annotate(out[1], self.clusters[0], self.clusters[1], self.nr_types, self.clusters[2], device=self.device if self.device.type == "cuda" else None)
+        if self.density_spec is not None:
+            from . import density as DN
+
+            self.density = DN.of_info(out[1], self._shape, self.density_spec[0], self.density_spec[1], self.nr_types,
+                                      device=self.device if self.device.type == "cuda" else None)
         return out

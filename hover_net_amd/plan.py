@@ -40,6 +40,7 @@ OP_VIEW, OP_TTA = 9, 10     # test-time augmentation (tta.py): never part of a p
 OP_STAIN_HIST, OP_STAIN_COMPACT, OP_STAIN_APPLY = 11, 12, 13     # stain normalisation (stain.py): never part of a plan
 OP_NBR_GRID, OP_NBR_QUERY = 14, 15     # nucleus neighbourhoods (neighbours.py): never part of a plan
 OP_NBR_CLUSTER = 16     # nucleus clusters over the same grid (clusters.py): never part of a plan
+OP_NBR_DENSITY = 17     # nucleus density maps over the same grid (density.py): never part of a plan
 
 
 @dataclass

@@ -40,7 +40,7 @@ typedef struct hvn_view {
 
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
-       HVN_OP_NBR_CLUSTER = 16 };
+       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -159,6 +159,22 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: a null pointer, label / degree not 4-byte or a table / workspace not 8-byte aligned, batch != 1, N < 1,
  *           min_pts < 1, a mask of 0, kh or kw < 1.  HVN_E_SIZE: min_pts > 2^26, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
  *           or res.sn too small.
+ *     NBR_DENSITY    typed counts within the radius of every NODE of a regular raster, over the same grid (hover_net_amd/density.py holds
+ *           the definition; csrc/hvn_density.hip).  Runs after NBR_GRID on the same stream and reads the workspace as that op left it
+ *           for the same N, kh, kw and table (x.base is not read); x.h, kh, kw, w, x2.base and x2.sn are the shared fields above.
+ *           cout = T in 1..16; y.base = int32 count [T][H][W], contiguous (4-byte aligned), y.h = H and y.w = W, each in [1, 16384],
+ *           T H W <= 2^28; bias = float64 table {ox, oy, s} on the device (8-byte aligned; read as doubles whatever the pointer's
+ *           declared type, as w is).  Node (u, v) lies at px = ox + (u * s), py = oy + (v * s), computed in the kernel, never stored;
+ *           with dx = xj - px, dy = yj - py, d2 = (dx * dx) + (dy * dy) in float64, one rounding per operation and no fused
+ *           multiply-add, count[t][v][u] = the number of points j of type t with d2 <= r2.  A point exactly on a node counts (no j != i
+ *           here: nodes are not points); a type outside [0, T) is counted in no plane.  A node's cell comes from NBR_GRID's formula and
+ *           clamp, so nodes may lie anywhere, also far outside the points' extent.  EVERY element of count is written, whatever it held
+ *           before: the caller clears nothing.  No atomics on the output, integer sums: a function of the inputs alone.  Loops are
+ *           bounded by cell_start values clamped to [0, N] and by the grid's rows: a workspace NBR_GRID did not fill gives wrong
+ *           numbers, no access outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer, count not 4-byte or a table / workspace not 8-byte aligned, batch != 1, N < 1, T outside
+ *           1..16, H or W < 1, kh or kw < 1.  HVN_E_SIZE: H or W > 16384, T H W > 2^28, N > 2^26, kh or kw > 4096 or kh * kw > 2^22,
+ *           x2.sn too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
