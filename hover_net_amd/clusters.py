@@ -24,15 +24,14 @@ DBSCAN's (sklearn.cluster.DBSCAN(eps=r, min_samples=m)) wherever no pair sits wi
 sqrt(d2) <= r.  The assignment of border points is THIS module's rule: sklearn gives a border point to the cluster whose expansion
 reached it first.
 
-Three implementations: tests/clusters_ref.py (O(N^2), the oracle), `cluster_host` (candidates from `neighbours.grid` /
-`neighbours.cells` in rounds, a vectorised union-find: a million points are feasible without a GPU) and `cluster_device`
+Three implementations: tests/clusters_ref.py (O(N^2), the oracle), `cluster_host` (candidates from `neighbours.grid` by
+`points.candidate_runs`, in rounds, a vectorised union-find: a million points are feasible without a GPU) and `cluster_device`
 (HVN_OP_NBR_GRID + HVN_OP_NBR_CLUSTER).  The three agree with ==.
 """
-import ctypes
-
 import numpy as np
 
 from . import neighbours as NB
+from . import points as P
 
 MAX_MIN_PTS, MAX_T = 1 << 26, NB.MAX_T
 
@@ -40,7 +39,7 @@ MAX_MIN_PTS, MAX_T = 1 << 26, NB.MAX_T
 def _check(xy, types, radius, min_pts, of_types):
     """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, m, of_types tuple | None)."""
     xy, types, r, _, _ = NB._check(xy, types, radius, 1, None)
-    if isinstance(min_pts, (bool, np.bool_)) or not isinstance(min_pts, (int, np.integer)):
+    if not P.is_integer(min_pts):
         raise TypeError("min_pts must be an integer, got %r" % (min_pts,))
     if not 1 <= int(min_pts) <= MAX_MIN_PTS:
         raise ValueError("min_pts = %d outside 1..2^26" % min_pts)
@@ -53,7 +52,7 @@ def _of_types(of_types, typed):
     if isinstance(of_types, (str, bytes)) or not hasattr(of_types, "__iter__"):
         raise TypeError("of_types must be None or a collection of integer types, got %r" % (of_types,))
     of = list(of_types)
-    if any(isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) for t in of):
+    if not all(P.is_integer(t) for t in of):
         raise TypeError("of_types must hold integers, got %r" % (of,))
     if not of or min(of) < 0 or max(of) >= MAX_T:
         raise ValueError("of_types = %r: a non-empty collection of types in [0, %d)" % (of, MAX_T))
@@ -71,48 +70,6 @@ def type_mask(of_types):
 
 # ---- the host --------------------------------------------------------------------------------------
 _PAIRS = 1 << 22                # candidate pairs per round of `cluster_host`
-
-
-def _runs(pts, g):
-    """The cell order of `pts` on grid g and, per cell-ordered point (a SLOT), its three contiguous runs of candidate slots
-    (`neighbours.query_host`): -> order [n], lo [3, n], hi [3, n]."""
-    n = pts.shape[0]
-    cx, cy = NB.cells(pts, g)
-    cell = cy * g.ncx + cx
-    order = np.argsort(cell, kind="stable")
-    start = np.zeros(g.ncx * g.ncy + 1, np.int64)
-    np.cumsum(np.bincount(cell, minlength=g.ncx * g.ncy), out=start[1:])
-    scx, scy = cx[order], cy[order]
-    lo, hi = np.empty((3, n), np.int64), np.empty((3, n), np.int64)
-    ca, cb = np.maximum(scx - 1, 0), np.minimum(scx + 1, g.ncx - 1)
-    for row in range(3):
-        yy = scy + (row - 1)
-        ok = (yy >= 0) & (yy < g.ncy)
-        base = np.clip(yy, 0, g.ncy - 1) * g.ncx
-        lo[row] = start[base + ca]
-        hi[row] = np.where(ok, start[base + cb + 1], lo[row])
-    return order, lo, hi
-
-
-def _pairs(sx, sy, lo, hi, r2):
-    """Rounds of about `_PAIRS` candidate pairs, all candidates of a query in one round: yields (qi, cand, d2) of the pairs with
-    d2 <= r2, in slots; (s, s) is among them."""
-    n = sx.shape[0]
-    ends = np.cumsum((hi - lo).sum(0))
-    a = 0
-    while a < n:
-        b = max(a + 1, int(np.searchsorted(ends, (ends[a - 1] if a else 0) + _PAIRS, side="right")))
-        qi, cand = [], []
-        for row in range(3):
-            lens = hi[row, a:b] - lo[row, a:b]
-            first = np.cumsum(lens) - lens
-            qi.append(np.repeat(np.arange(a, b, dtype=np.int64), lens))
-            cand.append(np.repeat(lo[row, a:b] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64))
-        qi, cand = np.concatenate(qi), np.concatenate(cand)
-        d2 = NB.d2_of(sx[qi], sy[qi], sx[cand], sy[cand])
-        keep = d2 <= r2
-        yield qi[keep], cand[keep], d2[keep]
-        a = b
 
 
 def _merge(comp, u, v):
@@ -146,15 +103,15 @@ def cluster_host(xy, types, radius, min_pts, of_types=None):
         return {"label": label, "degree": degree}
     pts = xy[sel]
     r2 = NB.r2_of(r)
-    order, lo, hi = _runs(pts, NB.grid(pts, r))
+    order, lo, hi, _, _ = P.candidate_runs(pts, NB.grid(pts, r))
     ns = order.shape[0]
     sx, sy, pos = pts[order, 0], pts[order, 1], sel[order]        # pos: the position of a slot
     deg = np.zeros(ns, np.int64)
-    for qi, _cand, _d2 in _pairs(sx, sy, lo, hi, r2):
+    for _a, _b, qi, _cand, _d2 in P.pair_rounds(sx, sy, lo, hi, r2, _PAIRS):
         deg += np.bincount(qi, minlength=ns)                      # (s, s) is a pair: the point counts itself
     core = deg >= m
     comp, near = np.arange(ns, dtype=np.int64), np.full(ns, -1, np.int64)
-    for qi, cand, d2 in _pairs(sx, sy, lo, hi, r2):
+    for _a, _b, qi, cand, d2 in P.pair_rounds(sx, sy, lo, hi, r2, _PAIRS):
         to_core = core[cand]
         link = to_core & core[qi] & (cand < qi)
         comp = _merge(comp, qi[link], cand[link])
@@ -179,56 +136,23 @@ def cluster_workspace_bytes(n):
     return 12 * n
 
 
-class DeviceClusters:
-    """The tensors and the two ops of one device clustering; `run_grid` (the HVN_OP_NBR_GRID of neighbours.py, on `neighbours.grid`)
-    and `run_cluster` launch on the current stream without synchronising (tools/clusters_bench.py times them apart), `result`
-    reads the two arrays back."""
+class DeviceClusters(P.DeviceGrid):
+    """One device clustering (`points.DeviceGrid`): `run_grid` and `run_cluster` launch on the current stream without synchronising
+    (tools/clusters_bench.py times them apart), `result` reads the two arrays back."""
 
     def __init__(self, xy, types, radius, min_pts, of_types=None, device="cuda"):
         import torch
 
-        from . import lib as L
-        from . import plan as PL
-
         xy, types, r, m, of = _check(xy, types, radius, min_pts, of_types)      # raises before anything is allocated or launched
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("cluster_device needs a GPU device, got %r" % (device,))
-        n, g = xy.shape[0], NB.grid(xy, r)
-        self.n, self.min_pts, self.of_types, self.grid = n, m, of, g
-        with torch.cuda.device(self.device):
-            up = lambda a: torch.from_numpy(a if a.flags.writeable else a.copy()).to(self.device)  # noqa: E731  (torch warns on read-only arrays)
-            self.xy = up(xy)
-            self.types = None if types is None else up(types)
-            self.table = torch.tensor([g.x0, g.y0, g.c, NB.r2_of(r)], dtype=torch.float64, device=self.device)
-            nbytes, nbytes2 = NB.workspace_bytes(n, g.ncx * g.ncy), cluster_workspace_bytes(n)
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.ws2 = torch.empty(nbytes2, dtype=torch.uint8, device=self.device)
-            self.label = torch.empty(n, dtype=torch.int32, device=self.device)
-            self.degree = torch.empty(n, dtype=torch.int32, device=self.device)
-        ops = []
-        for kind in (PL.OP_NBR_GRID, PL.OP_NBR_CLUSTER):
-            op = L.hvn_op()
-            op.kind, op.kh, op.kw, op.x.h = kind, g.ncy, g.ncx, n
-            op.w, op.x2.base, op.x2.sn = self.table.data_ptr(), self.ws.data_ptr(), nbytes
-            ops.append(op)
-        ops[0].x.base = self.xy.data_ptr()
-        ops[0].res.base = None if self.types is None else self.types.data_ptr()
-        ops[1].cout, ops[1].groups = m, type_mask(of)
-        ops[1].y.base, ops[1].y2.base = self.label.data_ptr(), self.degree.data_ptr()
-        ops[1].res.base, ops[1].res.sn = self.ws2.data_ptr(), nbytes2
-        self._ops = ops
-
-    def _run(self, i):
-        import torch
-
-        from . import lib as L
-
-        with torch.cuda.device(self.device):
-            L.call("hvn_run_op", ctypes.addressof(self._ops[i]), 1, L.stream_ptr(self.device))
-
-    def run_grid(self):
-        self._run(0)
+        super().__init__(xy, types, r, device, "cluster_device", "OP_NBR_CLUSTER")
+        self.min_pts, self.of_types = m, of
+        nbytes2 = cluster_workspace_bytes(self.n)
+        self.ws2 = self.empty(nbytes2, torch.uint8)
+        self.label, self.degree = self.empty(self.n), self.empty(self.n)
+        op = self._ops[1]
+        op.cout, op.groups = m, type_mask(of)
+        op.y.base, op.y2.base = self.label.data_ptr(), self.degree.data_ptr()
+        op.res.base, op.res.sn = self.ws2.data_ptr(), nbytes2
 
     def run_cluster(self):
         self._run(1)
@@ -276,17 +200,7 @@ def annotate(info, radius, min_pts, nr_types, of_types=None, device=None):
     values (JSON-serialisable as they are).  An empty dict is returned unchanged.  device=None: `cluster_host`."""
     if not info:
         return info
-    labels = list(info)
-    xy = np.array([np.asarray(info[lab]["centroid"], np.float64).reshape(2) for lab in labels], np.float64).reshape(-1, 2)
-    types = None
-    if nr_types is not None:
-        raw = [info[lab]["type"] for lab in labels]
-        if any(v is None or isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in raw):
-            raise ValueError("nr_types = %r needs an integer type on every entry" % (nr_types,))
-        types = np.array(raw, np.int64)
-        if types.min() < 0 or types.max() >= nr_types:
-            raise ValueError("types outside [0, %d)" % nr_types)
-        types = types.astype(np.int32)
+    labels, xy, types = P.from_info(info, nr_types)
     res = cluster(xy, types, radius, min_pts, of_types, device)
     lab_of, deg = res["label"].tolist(), res["degree"].tolist()
     for i, lab in enumerate(labels):

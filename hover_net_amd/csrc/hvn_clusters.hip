@@ -106,11 +106,7 @@ __device__ __forceinline__ void cl_walk(const ClusterDev &a, bool active, const 
     }
 }
 
-__device__ __forceinline__ double cl_d2(const ClusterDev &a, int g, const ClusterLane &l)
-{
-    const double dx = __dsub_rn(a.sx[g], l.x), dy = __dsub_rn(a.sy[g], l.y);
-    return __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-}
+__device__ __forceinline__ double cl_d2(const ClusterDev &a, int g, const ClusterLane &l) { return hvn_nbr_d2(a.sx[g], a.sy[g], l.x, l.y); }
 
 // the root of s, s in [0, N): steps only to a strictly smaller slot.  HALVE: inside cl_link, where the trees change -- agent-scope
 // loads, path halving; otherwise the trees are final (a later launch) and plain loads do, which the L1 may keep

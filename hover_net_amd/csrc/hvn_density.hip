@@ -116,8 +116,7 @@ __global__ __launch_bounds__(DN_T) void dn_density(const DensityDev a)
 #pragma unroll 4
             for (int i = c0 + wave; i < c1; i += DN_W) {
                 const int g = base + i;
-                const double dx = __dsub_rn(tx[i], px), dy = __dsub_rn(ty[i], py);
-                const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+                const double d2 = hvn_nbr_d2(tx[i], ty[i], px, py);
                 const int hit = (g >= lo && g < hi && d2 <= r2) ? tt[i] : -1;      // a type outside [0, T) matches no column
 #pragma unroll
                 for (int t = 0; t < TM; ++t) cnt[t] += hit == t ? 1 : 0;

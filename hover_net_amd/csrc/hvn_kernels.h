@@ -219,7 +219,7 @@ struct NbrWorkspace {
     double *sx, *sy;
     int *spos, *stype, *cell_start, *cursor, *bsum;
 };
-// the carve-up of that workspace, for every launcher that reads it (hvn_neighbours.hip, hvn_clusters.hip)
+// the carve-up of that workspace, for every launcher that reads it
 static inline NbrWorkspace hvn_nbr_workspace(void *ws, long N, long cells)
 {
     NbrWorkspace w;
@@ -246,6 +246,12 @@ __device__ __forceinline__ int hvn_nbr_axis(double v, double v0, double c, int n
 }
 __device__ __forceinline__ int hvn_nbr_clamp(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }      // a cell_start value into [0, N]
 __device__ __forceinline__ bool hvn_nbr_less(double d, int j, double D, int J) { return d < D || (d == D && j < J); }   // the total order (d2, j)
+// d2 of a candidate (x, y) from (qx, qy): four float64 roundings, each named, so that nothing can be contracted (points.py: `d2_of`)
+__device__ __forceinline__ double hvn_nbr_d2(double x, double y, double qx, double qy)
+{
+    const double dx = __dsub_rn(x, qx), dy = __dsub_rn(y, qy);
+    return __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+}
 #endif
 struct NbrGridArgs {
     const double *xy;           // [N][2] = (x, y)

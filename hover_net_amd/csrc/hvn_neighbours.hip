@@ -35,7 +35,8 @@
 #define NB_BLOCK 4096         // cells per scan block
 #define NB_NONE 0x7FFFFFFF
 
-// hvn_nbr_axis, hvn_nbr_clamp, hvn_nbr_less and the workspace carve-up live in hvn_kernels.h: hvn_clusters.hip reads the same grid
+// hvn_nbr_axis, hvn_nbr_clamp, hvn_nbr_less, hvn_nbr_d2 and the workspace carve-up live in hvn_kernels.h: hvn_clusters.hip and
+// hvn_density.hip read the same grid
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NB_T) void nb_count(const double *__restrict__ xy, const double *__restrict__ table, int *__restrict__ cursor, int N, int ncy,
@@ -237,8 +238,7 @@ __global__ __launch_bounds__(NB_T) void nb_query(const NbrQueryDev a)
             for (int i = c0; i < c1; ++i) {
                 const int g = base + i;
                 if (g < lo || g >= hi) continue;
-                const double dx = __dsub_rn(tx[i], qx), dy = __dsub_rn(ty[i], qy);
-                const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+                const double d2 = hvn_nbr_d2(tx[i], ty[i], qx, qy);
                 const int j = tj[i];
                 if (!(d2 <= r2) || j == qpos) continue;
                 if (hvn_nbr_less(d2, j, bd[KM - 1], bj[KM - 1])) {

@@ -45,12 +45,12 @@ H = ceil(h / step), ox = oy = (step - 1) / 2 (exact), s = step: node (u, v) is t
 [v step, (v + 1) step), so the map lines up with the image downsampled by `step`.
 """
 import collections
-import ctypes
 import math
 
 import numpy as np
 
 from . import neighbours as NB
+from . import points as P
 
 MAX_AXIS, MAX_NODES, MAX_T = 16384, 1 << 28, NB.MAX_T
 _PAIRS = 1 << 22                # (node, point) pairs per round of `density_host`
@@ -62,22 +62,14 @@ Raster = collections.namedtuple("Raster", "ox oy s W H")
 DensityMap = collections.namedtuple("DensityMap", "count origin step radius")
 
 
-def _number(v):
-    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
-
-
-def _integer(v):
-    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
-
-
 def _check_raster(raster, t):
     """A raster as the definition names it, for T = t channels, or TypeError / ValueError: -> Raster of floats and ints."""
     if isinstance(raster, (str, bytes)) or not hasattr(raster, "__len__") or len(raster) != 5:
         raise TypeError("raster must be (ox, oy, s, W, H), got %r" % (raster,))
     ox, oy, s, w, h = raster
-    if not (_number(ox) and _number(oy) and _number(s)):
+    if not (P.is_number(ox) and P.is_number(oy) and P.is_number(s)):
         raise TypeError("raster (ox, oy, s) must be numbers, got %r" % ((ox, oy, s),))
-    if not (_integer(w) and _integer(h)):
+    if not (P.is_integer(w) and P.is_integer(h)):
         raise TypeError("raster (W, H) must be integers, got %r" % ((w, h),))
     ox, oy, s, w, h = float(ox), float(oy), float(s), int(w), int(h)
     if not (np.isfinite(ox) and np.isfinite(oy)):
@@ -143,7 +135,7 @@ def density_host(xy, types, radius, raster, nr_types=None):
     ends = np.cumsum(area)
     a = 0
     while a < n:
-        b = max(a + 1, int(np.searchsorted(ends, (ends[a - 1] if a else 0) + _PAIRS, side="right")))
+        b = P.round_end(ends, a, _PAIRS)
         if b == a + 1 and area[a] > _PAIRS:
             rows = max(1, _PAIRS // int(wl[a]))
             for v0 in range(int(va[a]), int(vb[a]), rows):
@@ -155,54 +147,22 @@ def density_host(xy, types, radius, raster, nr_types=None):
 
 
 # ---- the device ----------------------------------------------------------------------------------
-class DeviceDensity:
-    """The tensors and the two ops of one device density map; `run_grid` (the HVN_OP_NBR_GRID of neighbours.py, on `neighbours.grid`
-    of the points) and `run_density` launch on the current stream without synchronising (tools/density_bench.py times them apart),
-    `result` reads the map back.  The op writes every element of `count`: nothing is cleared here."""
+class DeviceDensity(P.DeviceGrid):
+    """One device density map (`points.DeviceGrid`, the grid being that of the points): `run_grid` and `run_density` launch on the
+    current stream without synchronising (tools/density_bench.py times them apart), `result` reads the map back.  The op writes
+    every element of `count`: nothing is cleared here."""
 
     def __init__(self, xy, types, radius, raster, nr_types=None, device="cuda"):
         import torch
 
-        from . import lib as L
-        from . import plan as PL
-
         xy, types, r, ra, t = _check(xy, types, radius, raster, nr_types)      # raises before anything is allocated or launched
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("density_device needs a GPU device, got %r" % (device,))
-        n, g = xy.shape[0], NB.grid(xy, r)
-        self.n, self.t, self.raster, self.grid = n, t, ra, g
-        with torch.cuda.device(self.device):
-            up = lambda a: torch.from_numpy(a if a.flags.writeable else a.copy()).to(self.device)  # noqa: E731  (torch warns on read-only arrays)
-            self.xy = up(xy)
-            self.types = None if types is None else up(types)
-            self.table = torch.tensor([g.x0, g.y0, g.c, NB.r2_of(r)], dtype=torch.float64, device=self.device)
-            self.raster_table = torch.tensor([ra.ox, ra.oy, ra.s], dtype=torch.float64, device=self.device)
-            nbytes = workspace_bytes(n, g.ncx * g.ncy)
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.count = torch.empty((t, ra.H, ra.W), dtype=torch.int32, device=self.device)
-        ops = []
-        for kind in (PL.OP_NBR_GRID, PL.OP_NBR_DENSITY):
-            op = L.hvn_op()
-            op.kind, op.kh, op.kw, op.x.h = kind, g.ncy, g.ncx, n
-            op.w, op.x2.base, op.x2.sn = self.table.data_ptr(), self.ws.data_ptr(), nbytes
-            ops.append(op)
-        ops[0].x.base = self.xy.data_ptr()
-        ops[0].res.base = None if self.types is None else self.types.data_ptr()
-        ops[1].cout, ops[1].bias = t, self.raster_table.data_ptr()
-        ops[1].y.base, ops[1].y.h, ops[1].y.w = self.count.data_ptr(), ra.H, ra.W
-        self._ops = ops
-
-    def _run(self, i):
-        import torch
-
-        from . import lib as L
-
-        with torch.cuda.device(self.device):
-            L.call("hvn_run_op", ctypes.addressof(self._ops[i]), 1, L.stream_ptr(self.device))
-
-    def run_grid(self):
-        self._run(0)
+        super().__init__(xy, types, r, device, "density_device", "OP_NBR_DENSITY")
+        self.t, self.raster = t, ra
+        self.raster_table = torch.tensor([ra.ox, ra.oy, ra.s], dtype=torch.float64, device=self.device)
+        self.count = self.empty((t, ra.H, ra.W))
+        op = self._ops[1]
+        op.cout, op.bias = t, self.raster_table.data_ptr()
+        op.y.base, op.y.h, op.y.w = self.count.data_ptr(), ra.H, ra.W
 
     def run_density(self):
         self._run(1)
@@ -237,7 +197,7 @@ def resolve(spec):
     if not isinstance(spec, dict) or set(spec) != {"radius", "step"}:
         raise ValueError('density=%r: None or {"radius": r, "step": s}' % (spec,))
     NB._check(np.zeros((1, 2)), None, spec["radius"], 1, None)
-    if not _integer(spec["step"]):
+    if not P.is_integer(spec["step"]):
         raise TypeError("step must be an integer, got %r" % (spec["step"],))
     if int(spec["step"]) < 1:
         raise ValueError("step = %d, below 1" % spec["step"])
@@ -247,7 +207,7 @@ def resolve(spec):
 def raster_of(size_hw, step):
     """The pipeline raster of the module docstring for an image of size_hw = (h, w) processed pixels."""
     h, w = (int(v) for v in size_hw)
-    if not _integer(step) or int(step) < 1:
+    if not P.is_integer(step) or int(step) < 1:
         raise ValueError("step = %r: an integer >= 1" % (step,))
     if h < 1 or w < 1:
         raise ValueError("an image of %d x %d pixels" % (h, w))
@@ -267,17 +227,7 @@ def of_info(info, size_hw, radius, step, nr_types, device=None):
     ra = _check_raster(ra, t)
     if not info:
         return DensityMap(np.zeros((t, ra.H, ra.W), np.int32), (ra.ox, ra.oy), int(step), float(radius))
-    labels = list(info)
-    xy = np.array([np.asarray(info[lab]["centroid"], np.float64).reshape(2) for lab in labels], np.float64).reshape(-1, 2)
-    types = None
-    if nr_types is not None:
-        raw = [info[lab]["type"] for lab in labels]
-        if any(v is None or isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in raw):
-            raise ValueError("nr_types = %r needs an integer type on every entry" % (nr_types,))
-        types = np.array(raw, np.int64)
-        if types.min() < 0 or types.max() >= nr_types:
-            raise ValueError("types outside [0, %d)" % nr_types)
-        types = types.astype(np.int32)
+    _, xy, types = P.from_info(info, nr_types)
     return DensityMap(density(xy, types, radius, ra, nr_types, device), (ra.ox, ra.oy), int(step), float(radius))
 
 
@@ -305,7 +255,7 @@ def fraction(dm, t):
 
 def per_area(dm, mpp):
     """float64 [T, H, W]: nuclei per mm^2 of the disc pi r^2 around every node, for `mpp` microns per processed pixel."""
-    if not _number(mpp) or not (mpp > 0 and np.isfinite(mpp)):
+    if not P.is_number(mpp) or not (mpp > 0 and np.isfinite(mpp)):
         raise ValueError("mpp = %r: microns per pixel, positive and finite" % (mpp,))
     r_mm = float(dm.radius) * float(mpp) / 1000.0
     return dm.count.astype(np.float64) / (math.pi * r_mm * r_mm)
@@ -318,7 +268,7 @@ def hot_spots(plane, n, min_sep):
     plane = np.asarray(plane)
     if plane.ndim != 2 or plane.dtype.kind not in "iu":
         raise ValueError("hot_spots takes an integer plane [H, W], got %s %s" % (plane.dtype, plane.shape))
-    if not _integer(n) or n < 0 or not _integer(min_sep) or min_sep < 0:
+    if not P.is_integer(n) or n < 0 or not P.is_integer(min_sep) or min_sep < 0:
         raise ValueError("n = %r and min_sep = %r must be non-negative integers" % (n, min_sep))
     v, u = np.nonzero(plane > 0)
     c = plane[v, u].astype(np.int64)

@@ -116,6 +116,14 @@ def mat_dict(pred_inst, inst_info, nr_types, raw_map=None):
     return out
 
 
+_POINT_ARGS = ("neighbours", "clusters", "density")     # hover_net_amd/points.py
+
+
+def _given(run_args, *names):
+    """The entries of run_args under `names` that are not None, to forward as keywords."""
+    return {k: run_args[k] for k in names if run_args.get(k) is not None}
+
+
 class InferManager:
     """`InferManager(method={"model_args": {"nr_types": .., "mode": ..}, "model_path": ..}, type_info_path=..)`
     (infer/base.py:22-27 takes the same keywords).  `model=` hands over an already built network instead of a checkpoint
@@ -151,21 +159,16 @@ class InferManager:
         qupath are as without it); tta (default None): a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids) --
         every network step averages the views' outputs on the GPU (`Engine.run_tta`); stain_norm (default None): "macenko" or a
         `stain.StainFit` of a target image -- every image is fitted on itself and Macenko-normalised on the GPU before its patches
-        are cut (hover_net_amd/stain.py); neighbours (default None): {"radius": r, "k": k} in pixels -- every nucleus of `json/` gains
-        "neighbours" (`neighbours.annotate`: typed counts within r, the k nearest nuclei and the nearest of every type, with distances).
-        clusters (default None): {"radius": r, "min_pts": m} with an optional "types": [ints], in pixels -- every nucleus of `json/` gains
-        "cluster" (`clusters.annotate`: the id of its DBSCAN cluster's root nucleus or null, whether it is a core, its degree).
-        density (default None): {"radius": r, "step": s}, in pixels, `step` an integer >= 1 -- rank 0 also writes `density/<name>.npz` with
-        `count` (int32 [T, H, W]: nuclei of every type within r of every node of a raster with one node per step x step pixels), `origin`,
-        `step` and `radius` (`density.of_info` of the image's finished dict and size, on the GPU where the model is on one); `json/` is as
-        without it.
+        are cut (hover_net_amd/stain.py); neighbours, clusters, density (default None): the point-pattern
+        analyses of hover_net_amd/points.py on every image's finished dict -- every nucleus of `json/` gains "neighbours" / "cluster", and
+        with `density` rank 0 also writes `density/<name>.npz` (`density.save`: `count` int32 [T, H, W], `origin`, `step`, `radius`);
+        `json/` is as without it.
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
-        from . import clusters as CL
         from . import density as DN
-        from . import neighbours as NB
+        from . import points as PT
         from . import stain as ST
         from . import tta as TT
 
@@ -179,11 +182,7 @@ class InferManager:
         save_features = bool(run_args.get("save_features", False))
         tta = TT.views(run_args.get("tta"))                 # ValueError before any file is touched
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
-        neighbours = run_args.get("neighbours")
-        NB.resolve(neighbours)                              # likewise
-        clusters = run_args.get("clusters")
-        CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
-        density = DN.resolve(run_args.get("density"))       # likewise
+        specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -192,14 +191,13 @@ class InferManager:
 
         pending = list_files(input_dir)
         if rank == 0:
-            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if density is not None else ()):
+            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
             **({"return_features": True} if save_features else {}), **({"tta": tta} if tta is not None else {}),
             **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-            **({"neighbours": neighbours} if neighbours is not None else {}),
-            **({"clusters": clusters} if clusters is not None else {})))
+            **_given(run_args, "neighbours", "clusters")))
         done = []
         self.rounds = []                                   # files per caching round (inspected by the tests)
         while pending:
@@ -224,17 +222,16 @@ class InferManager:
                 pred_inst, inst_info = res[0], res[1]
                 raw_map = res[2] if save_raw_map else None
                 self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
-                if density is not None:
-                    DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], density))
+                if specs.density is not None:
+                    DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], specs))
                 done.append(name)
         return done
 
-    def _density_of(self, inst_info, size_hw, density):
-        """`density.of_info` of a finished dict for a resolved `density` argument, on the GPU where the model is on one."""
-        from . import density as DN
+    def _density_of(self, inst_info, size_hw, specs):
+        """`points.density_of` of a finished dict, on the device of the model."""
+        from . import points as PT
 
-        dev = self._collective_device()
-        return DN.of_info(inst_info, size_hw, density[0], density[1], self.nr_types, device=dev if dev is not None and dev.type == "cuda" else None)
+        return PT.density_of(inst_info, size_hw, specs, self.nr_types, self._collective_device())
 
     def _collective_device(self):
         try:
@@ -307,28 +304,20 @@ class WsiManager(InferManager):
         gains "features" (`features.derive`, shape features only: colour features on slides are out of scope); tta (default None): a view set of
         hover_net_amd.tta -- every stage-1 network step averages the views' outputs on the GPU (`Engine.run_tta`); stain_norm (default None): "macenko"
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
-        (`WsiInference(stain_norm=...)`); neighbours (default None): {"radius": r, "k": k} in pixels at proc_mag -- every nucleus of the json gains
-        "neighbours" (`neighbours.annotate` of the merged slide dict, in slide coordinates); clusters (default None): {"radius": r, "min_pts": m} with an
-        optional "types": [ints], in pixels at proc_mag -- every nucleus of the json gains "cluster" (`clusters.annotate` of the merged slide dict);
-        density (default None): {"radius": r, "step": s}, in pixels at proc_mag, `step` an integer >= 1 -- rank 0 also writes `density/<name>.npz` with `count`
-        (int32 [T, H, W]), `origin`, `step` and `radius`: `WsiInference(density=...)`'s map of the merged slide dict over the processed slide; the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        (`WsiInference(stain_norm=...)`); neighbours, clusters, density (default None): the point-pattern analyses of hover_net_amd/points.py, in
+        pixels at proc_mag, on the merged slide dict (`WsiInference`) -- every nucleus of the json gains "neighbours" / "cluster", and with `density` rank 0 also
+        writes `density/<name>.npz` (`density.save`); the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
-        from . import clusters as CL
         from . import density as DN
-        from . import neighbours as NB
+        from . import points as PT
         from . import stain as ST
         from . import tta as TT
 
         tta = TT.views(run_args.get("tta"))                 # ValueError before any slide is opened
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
-        neighbours = run_args.get("neighbours")
-        NB.resolve(neighbours)                              # likewise
-        clusters = run_args.get("clusters")
-        CL.resolve(clusters, typed=self.nr_types is not None)   # likewise
-        density = run_args.get("density")
-        density_rs = DN.resolve(density)                    # likewise
+        specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -343,7 +332,7 @@ class WsiManager(InferManager):
                 os.makedirs(output_dir + "/thumb/", exist_ok=True)
             if save_mask:
                 os.makedirs(output_dir + "/mask/", exist_ok=True)
-            if density is not None:
+            if specs.density is not None:
                 os.makedirs(output_dir + "/density/", exist_ok=True)
         status = {}
         for wsi_path in sorted(glob.glob(input_dir + "/*")):
@@ -370,7 +359,7 @@ class WsiManager(InferManager):
                     viz.save_png("%s/thumb/%s.png" % (output_dir, name), slide.thumbnail(32))
                 if self.wsi_fn is not None:
                     _inst_map, inst_info = self.wsi_fn(slide, mask)
-                    dmap = None if density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], density_rs)
+                    dmap = None if specs.density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], specs)
                 else:
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
@@ -378,14 +367,12 @@ class WsiManager(InferManager):
                                                  **({"features": True} if run_args.get("save_features", False) else {}),
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-                                                 **({"neighbours": neighbours} if neighbours is not None else {}),
-                                                 **({"clusters": clusters} if clusters is not None else {}),
-                                                 **({"density": density} if density is not None else {}))
+                                                 **_given(run_args, *_POINT_ARGS))
                     _inst_map, inst_info = wsi.run(slide, mask)
                     dmap = wsi.density
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)
-                    if density is not None:
+                    if specs.density is not None:
                         DN.save("%s/density/%s.npz" % (output_dir, name), dmap)
                 status[name] = "done"
             except Exception:                                 # noqa: BLE001  (the reference logs and moves on to the next slide)

@@ -348,11 +348,8 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     and normalised on the device right after its upload, into a new tensor the patches are cut from (the host-geometry branch uses
     the host forms: the same bytes); the colour features of `return_features` keep reading the image as given; a degenerate image
     (`stain.StainFitError`) passes through unnormalised with one warning.  Composes with `tta` (stain first, then the views).
-    `neighbours`: None or {"radius": r, "k": k} in pixels (implies the instance dict): every entry of every image's dict gains
-    "neighbours" (`neighbours.annotate` of the finished dict, the search on the GPU where the model is on one).  It runs on rank 0,
-    where the dicts already are; no collective is added, and the other ranks' own results stay without the entry.
-    `clusters`: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels; implies the instance dict; "types" needs
-    nr_types): every entry gains "cluster" (`clusters.annotate` of the finished dict), on rank 0 like `neighbours`, no collective.
+    `neighbours` / `clusters`: the point-pattern analyses of hover_net_amd/points.py on every image's finished dict (they imply the
+    instance dict); the other ranks' own results stay without the entries.
     The images are worked off in groups of at most `max_patches` network patches (3.6 GB of uint8 patches + 1.7 GB of maps at the
     default), so that a large cache round of `process_file_list` never has all its overlapping patches in HBM at once; every rank
     forms the same groups (the collectives inside stay matched)."""
@@ -364,16 +361,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         from . import stain as ST
 
         stain_norm = ST.resolve(stain_norm)
-    if neighbours is not None:
-        from . import neighbours as NB
+    from . import points as PT
 
-        neighbours = NB.resolve(neighbours)
-        return_centroids = True
-    if clusters is not None:
-        from . import clusters as CL
-
-        clusters = CL.resolve(clusters, typed=nr_types is not None)
-        return_centroids = True
+    specs = PT.resolve_specs(neighbours, clusters, typed=nr_types is not None)
+    return_centroids = return_centroids or specs.any_annotation
     win = 270 if (model.module if hasattr(model, "module") and not hasattr(model, "engine") else model).mode == "original" else 256
     msk = 80 if win == 270 else 164
     groups, cur, cur_n = [], [], 0
@@ -396,15 +387,12 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
                                                     return_raw, **more)):
             out[i] = res
-    if (neighbours is not None or clusters is not None) and _dist()[1] == 0:
+    if specs.any_annotation and _dist()[1] == 0:
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
         dev = next(net.parameters()).device
         for res in out:
             if res is not None and res[1] is not None:
-                if neighbours is not None:
-                    NB.annotate(res[1], neighbours[0], neighbours[1], nr_types, device=dev if dev.type == "cuda" else None)
-                if clusters is not None:
-                    CL.annotate(res[1], clusters[0], clusters[1], nr_types, clusters[2], device=dev if dev.type == "cuda" else None)
+                PT.annotate(res[1], specs, nr_types, dev)
     return out
 
 

@@ -512,18 +512,10 @@ class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
                  stain_norm=None, neighbours=None, clusters=None, density=None):
-        """density: None or {"radius": r, "step": s} (pixels of the processed slide; `step` an integer >= 1): after the merge, once per
-        slide, `self.density` holds the `density.DensityMap` of the finished dict over the slide's processed size (`density.of_info`:
-        typed nucleus counts within r of every node of a raster with one node per step x step pixels), in slide coordinates, so a
-        node's disc crosses tile seams; on rank 0 (None elsewhere and before the first slide), on the GPU where the model is on one,
-        no collective.  The return value of `run` is unchanged.
-        clusters: None or {"radius": r, "min_pts": m} with an optional "types": [ints] (pixels of the processed slide; "types" needs
-        nr_types): every entry of the instance dict gains "cluster" (`clusters.annotate`), computed ONCE on the final dict after the merge,
-        in slide coordinates, so clusters cross tile seams; on rank 0, no collective.
-        neighbours: None or {"radius": r, "k": k} in pixels of the processed slide: every entry of the instance dict gains
-        "neighbours" (`neighbours.annotate`), computed ONCE on the final dict after the merge, in slide coordinates (the tiles' origins
-        are already in the centroids), so neighbours are found across tile seams.  It runs on rank 0, where the dict lives (on the
-        GPU where the model is on one); no collective is added.
+        """neighbours / clusters / density: the point-pattern analyses of hover_net_amd/points.py, computed ONCE on the final dict after
+        the merge, in slide coordinates (the tiles' origins are already in the centroids).  With `density`, `self.density` holds the
+        slide's `density.DensityMap` over its processed size on rank 0 (None elsewhere and before the first slide); the return value
+        of `run` is unchanged.
         stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
         `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
         (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every
@@ -554,15 +546,10 @@ class WsiInference:
         from . import stain as ST
 
         self.stain_norm = ST.resolve(stain_norm)
-        from . import neighbours as NB
+        from . import points as PT
 
-        self.neighbours = NB.resolve(neighbours)
-        from . import clusters as CL
-
-        self.clusters = CL.resolve(clusters, typed=nr_types is not None)
-        from . import density as DN
-
-        self.density_spec = DN.resolve(density)
+        self.points = PT.resolve_specs(neighbours, clusters, density, typed=nr_types is not None)
+        self.density_spec = self.points.density
         self.density = None                        # the last slide's DensityMap (rank 0), with `density`
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
@@ -917,25 +904,17 @@ class WsiInference:
             out = merger.result()
             if getattr(self, "timing", None) is not None:
                 self.timing["map_d2h_s"] = time.perf_counter() - t0
-            return self._with_neighbours(out)
+            return self._finish(out)
         if rank != 0:
             return None, None
-        return self._with_neighbours((merger.inst_map, merger.inst_info))
+        return self._finish((merger.inst_map, merger.inst_info))
 
-    def _with_neighbours(self, out):
-        """(inst_map, inst_info) of the finished slide on rank 0; with `neighbours` / `clusters`, the dict's entries gain "neighbours" / "cluster"; with
-        `density`, `self.density` is set."""
-        if self.neighbours is not None and out[1]:
-            from . import neighbours as NB
+    def _finish(self, out):
+        """(inst_map, inst_info) of the finished slide on rank 0, after the point-pattern analyses (points.py): the dict's entries are
+        annotated and, with `density`, `self.density` is set."""
+        from . import points as PT
 
-            NB.annotate(out[1], self.neighbours[0], self.neighbours[1], self.nr_types, device=self.device if self.device.type == "cuda" else None)
-        if self.clusters is not None and out[1]:
-            from . import clusters as CL
-
-            CL.annotate(out[1], self.clusters[0], self.clusters[1], self.nr_types, self.clusters[2], device=self.device if self.device.type == "cuda" else None)
-        if self.density_spec is not None:
-            from . import density as DN
-
-            self.density = DN.of_info(out[1], self._shape, self.density_spec[0], self.density_spec[1], self.nr_types,
-                                      device=self.device if self.device.type == "cuda" else None)
+        PT.annotate(out[1], self.points, self.nr_types, self.device)
+        if self.points.density is not None:
+            self.density = PT.density_of(out[1], self._shape, self.points, self.nr_types, self.device)
         return out

@@ -35,17 +35,14 @@ c = 1 they land in cells 0 and 2.  So c = r (1 + 2^-20), or wider.  The argument
 The grid is capped at 4096 cells per axis and 2^22 cells in all; c is widened where the extent needs more.  Wider cells are slower,
 never wrong.
 """
-import collections
-import ctypes
-
 import numpy as np
 
-MARGIN = 1.0 + 2.0 ** -20
-MAX_AXIS, MAX_CELLS, MAX_N, MAX_K, MAX_T = 4096, 1 << 22, 1 << 26, 16, 16
+from . import points as P
+from .points import MARGIN, MAX_AXIS, MAX_CELLS, Grid, cells, d2_of, grid, r2_of, workspace_bytes  # noqa: F401  (clusters.py, density.py and the tests reach them here)
+
+MAX_N, MAX_K, MAX_T = 1 << 26, 16, 16
 MIN_R2 = 2.0 ** -1000
 _PAIRS = 1 << 22                # candidate pairs per round of `query_host`
-
-Grid = collections.namedtuple("Grid", "x0 y0 c ncx ncy")
 
 
 def _check(xy, types, radius, k, nr_types):
@@ -62,16 +59,16 @@ def _check(xy, types, radius, k, nr_types):
     with np.errstate(over="ignore"):
         if not np.isfinite(xy.max(0) - xy.min(0)).all():
             raise ValueError("the extent of xy is not a finite float64")
-    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+    if not P.is_number(radius):
         raise TypeError("radius must be a number, got %r" % (radius,))
     r = float(radius)
     if not (r > 0.0 and np.isfinite(r) and np.isfinite(r * r) and r * r >= MIN_R2):
         raise ValueError("radius = %r: it must be positive and its square a normal, finite float64" % (radius,))
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+    if not P.is_integer(k):
         raise TypeError("k must be an integer, got %r" % (k,))
     if not 1 <= int(k) <= MAX_K:
         raise ValueError("k = %d outside 1..%d" % (k, MAX_K))
-    if nr_types is not None and (isinstance(nr_types, (bool, np.bool_)) or not isinstance(nr_types, (int, np.integer))):
+    if nr_types is not None and not P.is_integer(nr_types):
         raise TypeError("nr_types must be an integer or None, got %r" % (nr_types,))
     if types is None:
         t = 1 if nr_types is None else int(nr_types)
@@ -88,36 +85,6 @@ def _check(xy, types, radius, k, nr_types):
     return np.ascontiguousarray(xy), None if types is None else np.ascontiguousarray(types), r, int(k), t
 
 
-def d2_of(xi, yi, xj, yj):
-    """The docstring's d2(i, j) for coordinates or arrays of them (clusters.py takes it from here)."""
-    dx, dy = xj - xi, yj - yi
-    return (dx * dx) + (dy * dy)
-
-
-def r2_of(r):
-    """The docstring's r2 for a checked radius."""
-    return r * r
-
-
-def grid(xy, radius):
-    """The grid of the module docstring for checked inputs -> Grid(x0, y0, c, ncx, ncy)."""
-    x0, y0 = float(xy[:, 0].min()), float(xy[:, 1].min())
-    ex, ey = float(xy[:, 0].max()) - x0, float(xy[:, 1].max()) - y0
-    c = max(radius * MARGIN, ex / (MAX_AXIS - 1), ey / (MAX_AXIS - 1))
-    while True:
-        ncx, ncy = int(np.floor(ex / c)) + 1, int(np.floor(ey / c)) + 1
-        if ncx <= MAX_AXIS and ncy <= MAX_AXIS and ncx * ncy <= MAX_CELLS:
-            return Grid(x0, y0, c, ncx, ncy)
-        c *= 1.25
-
-
-def cells(xy, g):
-    """(cx, cy) int64 [N] of every point: floor of the float64 quotient, clamped into the grid."""
-    cx = np.clip(np.floor((xy[:, 0] - g.x0) / g.c), 0, g.ncx - 1).astype(np.int64)
-    cy = np.clip(np.floor((xy[:, 1] - g.y0) / g.c), 0, g.ncy - 1).astype(np.int64)
-    return cx, cy
-
-
 def _empty(n, k, t):
     return {"count": np.zeros((n, t), np.int32), "knn": np.full((n, k), -1, np.int32), "nearest_of_type": np.full((n, t), -1, np.int32)}
 
@@ -130,36 +97,12 @@ def query_host(xy, types, radius, k, nr_types=None):
     n = xy.shape[0]
     g = grid(xy, r)
     r2 = r2_of(r)
-    cx, cy = cells(xy, g)
-    cell = cy * g.ncx + cx
-    order = np.argsort(cell, kind="stable")
-    start = np.zeros(g.ncx * g.ncy + 1, np.int64)
-    np.cumsum(np.bincount(cell, minlength=g.ncx * g.ncy), out=start[1:])
+    order, lo, hi, _, _ = P.candidate_runs(xy, g)
     sx, sy = xy[order, 0], xy[order, 1]
     st = np.zeros(n, np.int64) if types is None else types[order].astype(np.int64)
-    scx, scy = cx[order], cy[order]
-    lo, hi = np.empty((3, n), np.int64), np.empty((3, n), np.int64)
-    ca, cb = np.maximum(scx - 1, 0), np.minimum(scx + 1, g.ncx - 1)
-    for row in range(3):
-        yy = scy + (row - 1)
-        ok = (yy >= 0) & (yy < g.ncy)
-        base = np.clip(yy, 0, g.ncy - 1) * g.ncx
-        lo[row] = start[base + ca]
-        hi[row] = np.where(ok, start[base + cb + 1], lo[row])
     out = _empty(n, k, t)
-    ends = np.cumsum((hi - lo).sum(0))
-    a = 0
-    while a < n:
-        b = max(a + 1, int(np.searchsorted(ends, (ends[a - 1] if a else 0) + _PAIRS, side="right")))
-        qi, cand = [], []
-        for row in range(3):
-            lens = hi[row, a:b] - lo[row, a:b]
-            first = np.cumsum(lens) - lens
-            qi.append(np.repeat(np.arange(a, b, dtype=np.int64), lens))
-            cand.append(np.repeat(lo[row, a:b] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64))
-        qi, cand = np.concatenate(qi), np.concatenate(cand)
-        d2 = d2_of(sx[qi], sy[qi], sx[cand], sy[cand])
-        keep = (d2 <= r2) & (cand != qi)
+    for a, b, qi, cand, d2 in P.pair_rounds(sx, sy, lo, hi, r2, _PAIRS):
+        keep = cand != qi
         qi, cand, d2 = qi[keep], cand[keep], d2[keep]
         j, tj = order[cand], st[cand]
         rows = order[a:b]
@@ -175,64 +118,22 @@ def query_host(xy, types, radius, k, nr_types=None):
         head = np.ones(key.shape[0], bool)
         head[1:] = key[1:] != key[:-1]
         out["nearest_of_type"][order[key[head] // t], key[head] % t] = j[o][head]
-        a = b
     return out
 
 
 # ---- the device ----------------------------------------------------------------------------------
-def workspace_bytes(n, n_cells):
-    """Bytes of the one workspace of the two ops (include/hvn.h, NBR_GRID)."""
-    return 24 * n + 4 * (2 * n_cells + 1) + 4096
-
-
-class DeviceQuery:
-    """The tensors and the two ops of one device query; `run_grid` and `run_query` launch on the current stream without
-    synchronising (tools/neighbours_bench.py times them apart), `result` reads the three arrays back."""
+class DeviceQuery(P.DeviceGrid):
+    """One device query (`points.DeviceGrid`): `run_grid` and `run_query` launch on the current stream without synchronising
+    (tools/neighbours_bench.py times them apart), `result` reads the three arrays back."""
 
     def __init__(self, xy, types, radius, k, nr_types=None, device="cuda"):
-        import torch
-
-        from . import lib as L
-        from . import plan as PL
-
         xy, types, r, k, t = _check(xy, types, radius, k, nr_types)     # raises before anything is allocated or launched
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("query_device needs a GPU device, got %r" % (device,))
-        n, g = xy.shape[0], grid(xy, r)
-        self.n, self.k, self.t, self.grid = n, k, t, g
-        with torch.cuda.device(self.device):
-            up = lambda a: torch.from_numpy(a if a.flags.writeable else a.copy()).to(self.device)  # noqa: E731  (torch warns on read-only arrays)
-            self.xy = up(xy)
-            self.types = None if types is None else up(types)
-            self.table = torch.tensor([g.x0, g.y0, g.c, r * r], dtype=torch.float64, device=self.device)
-            nbytes = workspace_bytes(n, g.ncx * g.ncy)
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.count = torch.empty((n, t), dtype=torch.int32, device=self.device)
-            self.knn = torch.empty((n, k), dtype=torch.int32, device=self.device)
-            self.nearest = torch.empty((n, t), dtype=torch.int32, device=self.device)
-        ops = []
-        for kind in (PL.OP_NBR_GRID, PL.OP_NBR_QUERY):
-            op = L.hvn_op()
-            op.kind, op.kh, op.kw, op.x.h = kind, g.ncy, g.ncx, n
-            op.w, op.x2.base, op.x2.sn = self.table.data_ptr(), self.ws.data_ptr(), nbytes
-            ops.append(op)
-        ops[0].x.base = self.xy.data_ptr()
-        ops[0].res.base = None if self.types is None else self.types.data_ptr()
-        ops[1].cout, ops[1]._rsv = t, k
-        ops[1].y.base, ops[1].y2.base, ops[1].res.base = self.count.data_ptr(), self.knn.data_ptr(), self.nearest.data_ptr()
-        self._ops = ops
-
-    def _run(self, i):
-        import torch
-
-        from . import lib as L
-
-        with torch.cuda.device(self.device):
-            L.call("hvn_run_op", ctypes.addressof(self._ops[i]), 1, L.stream_ptr(self.device))
-
-    def run_grid(self):
-        self._run(0)
+        super().__init__(xy, types, r, device, "query_device", "OP_NBR_QUERY")
+        self.k, self.t = k, t
+        self.count, self.knn, self.nearest = self.empty((self.n, t)), self.empty((self.n, k)), self.empty((self.n, t))
+        op = self._ops[1]
+        op.cout, op._rsv = t, k
+        op.y.base, op.y2.base, op.res.base = self.count.data_ptr(), self.knn.data_ptr(), self.nearest.data_ptr()
 
     def run_query(self):
         self._run(1)
@@ -298,17 +199,7 @@ def annotate(info, radius, k, nr_types, device=None):
     (JSON-serialisable as they are).  An empty dict is returned unchanged.  device=None: `query_host`."""
     if not info:
         return info
-    labels = list(info)
-    xy = np.array([np.asarray(info[lab]["centroid"], np.float64).reshape(2) for lab in labels], np.float64).reshape(-1, 2)
-    types = None
-    if nr_types is not None:
-        raw = [info[lab]["type"] for lab in labels]
-        if any(v is None or isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in raw):
-            raise ValueError("nr_types = %r needs an integer type on every entry" % (nr_types,))
-        types = np.array(raw, np.int64)
-        if types.min() < 0 or types.max() >= nr_types:
-            raise ValueError("types outside [0, %d)" % nr_types)
-        types = types.astype(np.int32)
+    labels, xy, types = P.from_info(info, nr_types)
     res = query(xy, types, radius, k, nr_types, device)
     kd, nd = distances(xy, res["knn"]), distances(xy, res["nearest_of_type"])
     count, knn, near = res["count"].tolist(), res["knn"].tolist(), res["nearest_of_type"].tolist()

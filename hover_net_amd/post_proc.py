@@ -314,17 +314,16 @@ def process(pred_map, nr_types=None, return_centroids=False, contours="host", *,
     """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32.  contours="device" traces the contours on
     the GPU (`trace_contours_device`) instead of on the host; the result is the same.  features=True adds "features" to every
     entry of the dict (`features.derive`; it implies return_centroids); `image` (host uint8 [H,W,3], RGB) adds mean_rgb / std_rgb.
-    neighbours={"radius": r, "k": k} (pixels; it implies return_centroids) adds "neighbours" to every entry: `neighbours.annotate` of
-    the finished dict, the search on the GPU.  clusters={"radius": r, "min_pts": m} with an optional "types": [ints] (pixels; it implies
-    return_centroids; "types" needs nr_types) adds "cluster" to every entry: `clusters.annotate` of the finished dict, on the GPU."""
+    neighbours / clusters: the point-pattern analyses of hover_net_amd/points.py on the finished dict, on the GPU (they imply
+    return_centroids)."""
+    from . import points as PT
     from . import clusters as CL
     from . import neighbours as NB
 
     if contours not in ("host", "device"):
         raise ValueError('contours must be "host" or "device", got %r' % (contours,))
-    nbr = NB.resolve(neighbours)
-    clu = CL.resolve(clusters, typed=nr_types is not None)
-    return_centroids = return_centroids or nbr is not None or clu is not None
+    specs = PT.resolve_specs(neighbours, clusters, typed=nr_types is not None)
+    return_centroids = return_centroids or specs.any_annotation
     img_dev = None
     if image is not None:
         if not features:
@@ -344,8 +343,5 @@ def process(pred_map, nr_types=None, return_centroids=False, contours="host", *,
     if rec is not None:
         info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat,
                                feat_host=None if feat is None else feat[0].cpu().numpy(), with_colour=image is not None)
-        if nbr is not None:
-            NB.annotate(info, nbr[0], nbr[1], nr_types, device=pred.device)
-        if clu is not None:
-            CL.annotate(info, clu[0], clu[1], nr_types, clu[2], device=pred.device)
+        PT.annotate(info, specs, nr_types, pred.device)
     return pred_inst, info

@@ -246,3 +246,26 @@ def run_train_ops(tops, batch, stored_parts=False):
     assert rc == 0, lib.hvn_train_last_error().decode()
     torch.cuda.synchronize()
     return need
+
+
+# -- the pipeline tests of the point-pattern analyses (test_gpu_neighbours.py, test_gpu_clusters.py, test_gpu_density.py) --
+def synth_net():
+    """One synthetic five-type model on the GPU."""
+    from hover_net_amd import net_desc
+    from hover_net_amd.synth import synth_state_dict
+
+    model = net_desc.create_model(mode="original", nr_types=5, input_ch=3)
+    model.load_state_dict(synth_state_dict("original", 5, seed=51), strict=True)
+    return model.to("cuda").eval()
+
+
+def _tile_images():
+    from hover_net_amd.synth import synth_tiles
+
+    return [synth_tiles(1, 270, seed=52)[0], synth_tiles(1, 270, seed=53)[0][:170, :121]]
+
+
+def _maps(h, w, seed):
+    from hover_net_amd.synth import synth_pred_maps
+
+    return synth_pred_maps(1, h, w, 5, seed=seed, k_lo=4, k_hi=12)[0][0]

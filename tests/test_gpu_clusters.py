@@ -10,6 +10,7 @@ import torch
 
 import clusters_ref as R
 from golden_util import assert_same_info
+from gpu_util import _maps, _tile_images, synth_net
 
 pytestmark = pytest.mark.gpu
 
@@ -135,24 +136,7 @@ def test_bad_arguments_raise_before_any_launch(monkeypatch):
 # -- 2: the public path --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def net():
-    from hover_net_amd import net_desc
-    from hover_net_amd.synth import synth_state_dict
-
-    model = net_desc.create_model(mode="original", nr_types=5, input_ch=3)
-    model.load_state_dict(synth_state_dict("original", 5, seed=51), strict=True)
-    return model.to("cuda").eval()
-
-
-def _tile_images():
-    from hover_net_amd.synth import synth_tiles
-
-    return [synth_tiles(1, 270, seed=52)[0], synth_tiles(1, 270, seed=53)[0][:170, :121]]
-
-
-def _maps(h, w, seed):
-    from hover_net_amd.synth import synth_pred_maps
-
-    return synth_pred_maps(1, h, w, 5, seed=seed, k_lo=4, k_hi=12)[0][0]
+    return synth_net()
 
 
 def _assert_annotated(info1, info0, nr_types, spec=SPEC):

@@ -3,7 +3,7 @@
 
     python tools/clusters_bench.py [--reps 10] [--sizes 100000,1000000] [--params 100:10,25:10] [--out profiles/clusters_bench.txt]
 
-Input: the synthetic slide of tools/neighbours_bench.py (about one nucleus per 20 x 20 px, 70 % uniform, 30 % in Gaussian clusters).
+Input: the synthetic slide of tools/nbr_bench_util.py (about one nucleus per 20 x 20 px, 70 % uniform, 30 % in Gaussian clusters).
 Parameters: radius 100 px, min_pts 10 (at 125 neighbours per point nearly every point is a core and the slide is ONE cluster: every
 union ends on one root, the most contended case of the union-find), and radius 25 px, min_pts 10 (only the Gaussian clusters are dense
 enough: thousands of clusters, borders and noise).  Per size and parameter set, `cluster_device` is first checked against `cluster_host`
@@ -17,7 +17,6 @@ legs (warm; one sample = the launches of one op between two HIP events on the cu
     sklearn   sklearn.cluster.DBSCAN(eps, min_samples).fit, wall clock, once, where the library is installed and N <= --sklearn-max
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -29,9 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-
-def stat(xs):
-    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+from nbr_bench_util import candidates, points, stat, timed, write_out  # noqa: E402
 
 
 def main():
@@ -42,10 +39,6 @@ def main():
     ap.add_argument("--sklearn-max", type=int, default=100000)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    import torch
-
-    from neighbours_bench import candidates, points
-
     from hover_net_amd import clusters as CL
     from hover_net_amd import lib as L
 
@@ -54,15 +47,6 @@ def main():
         from sklearn.cluster import DBSCAN
     except ImportError:
         DBSCAN = None
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
 
     out, lines = {"reps": a.reps}, []
     lines.append("Nucleus clusters (DBSCAN) on one GPU: ms, median [min .. max] of %d samples; host = cluster_host once, wall clock" % a.reps)
@@ -115,13 +99,7 @@ def main():
             if sk_s is not None:
                 lines.append("    %-8s %10.1f   sklearn DBSCAN.fit (once); the same core set: %s" % ("sklearn", sk_s * 1e3, "yes" if census["sklearn_same_cores"] else "NO"))
             del q
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(json.dumps({"clusters_bench": out}))
+    write_out("clusters_bench", lines, out, a.out)
 
 
 if __name__ == "__main__":

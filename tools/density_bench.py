@@ -3,7 +3,7 @@
 
     python tools/density_bench.py [--reps 10] [--sizes 100000,1000000] [--params 100:32,150:64] [--out profiles/density_bench.txt]
 
-Input: the synthetic slide of tools/neighbours_bench.py (about one nucleus per 20 x 20 px, 70 % uniform, 30 % in Gaussian clusters, five
+Input: the synthetic slide of tools/nbr_bench_util.py (about one nucleus per 20 x 20 px, 70 % uniform, 30 % in Gaussian clusters, five
 types) and the pipeline raster over it (`density.raster_of`: one node per step x step pixels).  Parameters radius:step in pixels.  Per
 size and parameter set, `density_device` is first checked against `density_host` with == on the whole array (the host path is the one
 tests/test_density_host.py holds to the all-pairs oracle); a difference ends the run.
@@ -16,7 +16,6 @@ legs (warm; one sample = the launches of one op between two HIP events on the cu
     host      `density_host`, wall clock, once (numpy on the same box)
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -28,9 +27,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-
-def stat(xs):
-    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+from nbr_bench_util import candidates, points, stat, timed, write_out  # noqa: E402
 
 
 def node_tests(xy, g, raster):
@@ -55,24 +52,11 @@ def main():
     ap.add_argument("--params", default="100:32,150:64", help="radius:step, comma separated")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    import torch
-
-    from neighbours_bench import candidates, points
-
     from hover_net_amd import density as DN
     from hover_net_amd import lib as L
     from hover_net_amd import neighbours as NB
 
     L.require_gpu()
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
 
     out, lines = {"reps": a.reps}, []
     lines.append("Nucleus density maps on one GPU: ms, median [min .. max] of %d samples; host = density_host once, wall clock" % a.reps)
@@ -115,13 +99,7 @@ def main():
                          % ("query", med["query"], min(samp["query"]), max(samp["query"]), qtests, qtests / med["query"] * 1e3))
             lines.append("    %-8s %10.1f   density_host, numpy (once): %.0f times grid + density" % ("host", host_s * 1e3, host_s * 1e3 / (med["grid"] + med["density"])))
             del q, nq
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(json.dumps({"density_bench": out}))
+    write_out("density_bench", lines, out, a.out)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ legs (warm; one sample = the launches of one op between two HIP events on the cu
     host      `query_host`, wall clock, once (numpy on the same box)
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -24,33 +23,11 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
 
-RADIUS, K, TYPES = 100.0, 5, 5
+from nbr_bench_util import TYPES, candidates, points, stat, timed, write_out  # noqa: E402
 
-
-def points(n, seed):
-    rng = np.random.default_rng(seed)
-    side = 20.0 * np.sqrt(n)
-    n_cl = int(0.3 * n)
-    centres = rng.random((max(1, n_cl // 200), 2)) * side
-    cl = centres[rng.integers(0, centres.shape[0], n_cl)] + rng.normal(0.0, 40.0, (n_cl, 2))
-    xy = np.concatenate([rng.random((n - n_cl, 2)) * side, np.clip(cl, 0.0, side)])
-    return np.ascontiguousarray(xy[rng.permutation(n)]), rng.integers(0, TYPES, n).astype(np.int32), side
-
-
-def candidates(xy, g):
-    """Distance tests a 3 x 3 search needs: per point, the points in the nine cells around it (itself included)."""
-    from hover_net_amd import neighbours as NB
-
-    cx, cy = NB.cells(xy, g)
-    per = np.zeros((g.ncy + 2, g.ncx + 2), np.int64)
-    np.add.at(per, (cy + 1, cx + 1), 1)
-    box = sum(per[1 + dy:g.ncy + 1 + dy, 1 + dx:g.ncx + 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1))
-    return int((box * per[1:-1, 1:-1]).sum())
-
-
-def stat(xs):
-    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+RADIUS, K = 100.0, 5
 
 
 def main():
@@ -59,21 +36,10 @@ def main():
     ap.add_argument("--sizes", default="100000,1000000")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    import torch
-
     from hover_net_amd import lib as L
     from hover_net_amd import neighbours as NB
 
     L.require_gpu()
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
 
     out, lines = {"reps": a.reps, "radius": RADIUS, "k": K, "types": TYPES}, []
     lines.append("Neighbour search on one GPU, radius %g px, k = %d, %d types: ms, median [min .. max] of %d samples; host = query_host once, wall clock"
@@ -112,13 +78,7 @@ def main():
                      % ("query", med["query"], min(samp["query"]), max(samp["query"]), n / med["query"] * 1e3, tests / med["query"] * 1e3, tests))
         lines.append("    %-6s %10.1f   query_host, numpy (once): %.0f times grid + query" % ("host", host_s * 1e3, host_s * 1e3 / (med["grid"] + med["query"])))
         del q
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(json.dumps({"neighbours_bench": out}))
+    write_out("neighbours_bench", lines, out, a.out)
 
 
 if __name__ == "__main__":
