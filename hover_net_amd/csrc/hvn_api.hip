@@ -495,6 +495,22 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.raster & 7) return hvn_fail(HVN_E_ARG, "nbr_density: misaligned raster table (8)");
         return hvn_launch_status(hvn_launch_nbr_density(a, s), "nbr_density");
     }
+    case HVN_OP_NBR_PAIRS: {
+        NbrPairsArgs a;
+        a.table = (const double *)op->w;
+        a.rt = (const double *)op->bias;
+        a.workspace = op->x2.base;
+        a.acc = (long long *)op->y.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.R = op->_rsv;
+        if (!a.workspace || !a.acc || !a.rt) return hvn_fail(HVN_E_ARG, "nbr_pairs: null pointer");
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_pairs: %d types outside 1..16", a.T);
+        if (a.R < 1 || a.R > HVN_NBR_PAIRS_MAX_R) return hvn_fail(HVN_E_ARG, "nbr_pairs: %d radii outside 1..32", a.R);
+        if (a.T * a.T * a.R > HVN_NBR_PAIRS_MAX_BINS) return hvn_fail(HVN_E_SIZE, "nbr_pairs: %d x %d types and %d radii, more than 4096 bins", a.T, a.T, a.R);
+        if (int rc = nbr_common("nbr_pairs", op, batch)) return rc;
+        if ((uintptr_t)a.acc & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs: misaligned acc (8)");
+        if ((uintptr_t)a.rt & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs: misaligned window and radius table (8)");
+        return hvn_launch_status(hvn_launch_nbr_pairs(a, s), "nbr_pairs");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

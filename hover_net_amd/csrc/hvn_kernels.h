@@ -292,6 +292,17 @@ struct NbrDensityArgs {
     int N, ncy, ncx, T, H, W;
 };
 int hvn_launch_nbr_density(const NbrDensityArgs &a, hipStream_t stream);
+// hvn_pairs.hip: typed pair counts by distance bin, the integers under Ripley's cross-type K (hover_net_amd/ripley.py)
+#define HVN_NBR_PAIRS_MAX_R 32
+#define HVN_NBR_PAIRS_MAX_BINS 4096              // T * T * R
+struct NbrPairsArgs {
+    const double *table;        // {x0, y0, c, r2_{R-1}}, as for the grid
+    const double *rt;           // {wx0, wy0, wx1, wy1, r_0 .. r_{R-1}, r2_0 .. r2_{R-1}}: 4 + 2 R doubles
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    long long *acc;             // [2][T][T][R]; cleared in stream order, then every element is written
+    int N, ncy, ncx, T, R;
+};
+int hvn_launch_nbr_pairs(const NbrPairsArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

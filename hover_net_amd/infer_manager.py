@@ -162,13 +162,16 @@ class InferManager:
         are cut (hover_net_amd/stain.py); neighbours, clusters, density (default None): the point-pattern
         analyses of hover_net_amd/points.py on every image's finished dict -- every nucleus of `json/` gains "neighbours" / "cluster", and
         with `density` rank 0 also writes `density/<name>.npz` (`density.save`: `count` int32 [T, H, W], `origin`, `step`, `radius`);
-        `json/` is as without it.
+        `json/` is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py) -- rank 0
+        also writes `ripley/<name>.npz` (`ripley.save`: the typed pair counts under the cross-type K function, of every image's finished
+        dict over the image); `json/` is as without it.
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
         from . import density as DN
         from . import points as PT
+        from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
 
@@ -183,6 +186,7 @@ class InferManager:
         tta = TT.views(run_args.get("tta"))                 # ValueError before any file is touched
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
+        ripley = RP.resolve(run_args.get("ripley"))          # likewise
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -191,7 +195,7 @@ class InferManager:
 
         pending = list_files(input_dir)
         if rank == 0:
-            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()):
+            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()) + (("ripley",) if ripley is not None else ()):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
@@ -224,6 +228,8 @@ class InferManager:
                 self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
                 if specs.density is not None:
                     DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], specs))
+                if ripley is not None:
+                    RP.save("%s/ripley/%s.npz" % (output_dir, name), PT.ripley_of(inst_info, img.shape[:2], ripley, self.nr_types, self._collective_device()))
                 done.append(name)
         return done
 
@@ -306,18 +312,22 @@ class WsiManager(InferManager):
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
         (`WsiInference(stain_norm=...)`); neighbours, clusters, density (default None): the point-pattern analyses of hover_net_amd/points.py, in
         pixels at proc_mag, on the merged slide dict (`WsiInference`) -- every nucleus of the json gains "neighbours" / "cluster", and with `density` rank 0 also
-        writes `density/<name>.npz` (`density.save`); the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        writes `density/<name>.npz` (`density.save`); the json is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window"
+        (hover_net_amd/ripley.py), in pixels at proc_mag -- rank 0 also writes `ripley/<name>.npz` (`ripley.save`), the pair counts of the merged slide
+        dict (`WsiInference(ripley=...)`); the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
         from . import density as DN
         from . import points as PT
+        from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
 
         tta = TT.views(run_args.get("tta"))                 # ValueError before any slide is opened
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
+        ripley = RP.resolve(run_args.get("ripley"))          # likewise
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -334,6 +344,8 @@ class WsiManager(InferManager):
                 os.makedirs(output_dir + "/mask/", exist_ok=True)
             if specs.density is not None:
                 os.makedirs(output_dir + "/density/", exist_ok=True)
+            if ripley is not None:
+                os.makedirs(output_dir + "/ripley/", exist_ok=True)
         status = {}
         for wsi_path in sorted(glob.glob(input_dir + "/*")):
             if os.path.isdir(wsi_path):
@@ -360,6 +372,7 @@ class WsiManager(InferManager):
                 if self.wsi_fn is not None:
                     _inst_map, inst_info = self.wsi_fn(slide, mask)
                     dmap = None if specs.density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], specs)
+                    pcs = None if ripley is None or rank != 0 else PT.ripley_of(inst_info, slide.shape[:2], ripley, self.nr_types, self._collective_device())
                 else:
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
@@ -367,13 +380,15 @@ class WsiManager(InferManager):
                                                  **({"features": True} if run_args.get("save_features", False) else {}),
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-                                                 **_given(run_args, *_POINT_ARGS))
+                                                 **_given(run_args, *_POINT_ARGS, "ripley"))
                     _inst_map, inst_info = wsi.run(slide, mask)
-                    dmap = wsi.density
+                    dmap, pcs = wsi.density, wsi.ripley
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)
                     if specs.density is not None:
                         DN.save("%s/density/%s.npz" % (output_dir, name), dmap)
+                    if ripley is not None:
+                        RP.save("%s/ripley/%s.npz" % (output_dir, name), pcs)
                 status[name] = "done"
             except Exception:                                 # noqa: BLE001  (the reference logs and moves on to the next slide)
                 logging.exception("Crash")

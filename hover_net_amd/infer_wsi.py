@@ -511,11 +511,14 @@ class DeviceMerger:
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
-                 stain_norm=None, neighbours=None, clusters=None, density=None):
+                 stain_norm=None, neighbours=None, clusters=None, density=None, ripley=None):
         """neighbours / clusters / density: the point-pattern analyses of hover_net_amd/points.py, computed ONCE on the final dict after
         the merge, in slide coordinates (the tiles' origins are already in the centroids).  With `density`, `self.density` holds the
         slide's `density.DensityMap` over its processed size on rank 0 (None elsewhere and before the first slide); the return value
         of `run` is unchanged.
+        ripley: None or {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py): `self.ripley` holds the slide's
+        `ripley.PairCounts` -- the typed pair counts under the cross-type K function, of the merged dict over the processed slide -- on
+        rank 0 (None elsewhere and before the first slide), computed once after the merge as the others are; nothing else changes.
         stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
         `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
         (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every
@@ -551,6 +554,10 @@ class WsiInference:
         self.points = PT.resolve_specs(neighbours, clusters, density, typed=nr_types is not None)
         self.density_spec = self.points.density
         self.density = None                        # the last slide's DensityMap (rank 0), with `density`
+        from . import ripley as RP
+
+        self.ripley_spec = RP.resolve(ripley)      # the fourth analysis, carried beside `self.points`
+        self.ripley = None                         # the last slide's PairCounts (rank 0), with `ripley`
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -911,10 +918,12 @@ class WsiInference:
 
     def _finish(self, out):
         """(inst_map, inst_info) of the finished slide on rank 0, after the point-pattern analyses (points.py): the dict's entries are
-        annotated and, with `density`, `self.density` is set."""
+        annotated and, with `density` / `ripley`, `self.density` / `self.ripley` are set."""
         from . import points as PT
 
         PT.annotate(out[1], self.points, self.nr_types, self.device)
         if self.points.density is not None:
             self.density = PT.density_of(out[1], self._shape, self.points, self.nr_types, self.device)
+        if self.ripley_spec is not None:
+            self.ripley = PT.ripley_of(out[1], self._shape, self.ripley_spec, self.nr_types, self.device)
         return out

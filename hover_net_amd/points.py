@@ -1,5 +1,5 @@
-"""The point-pattern layer under neighbours.py, clusters.py and density.py: what the three analyses of nucleus centroids share on the
-host, on the device and in the pipeline.  numpy only; imports without a GPU.
+"""The point-pattern layer under neighbours.py, clusters.py, density.py and ripley.py: what the four analyses of nucleus centroids share
+on the host, on the device and in the pipeline.  numpy only; imports without a GPU.
 
 The arithmetic (`d2_of`, `r2_of`) and the grid (`grid`, `cells`) are defined in the docstring of neighbours.py, which re-exports them.
 
@@ -12,7 +12,7 @@ The device (`DeviceGrid`).  Every analysis is HVN_OP_NBR_GRID, which builds the 
 followed by a second op of its own kind that reads them.  `DeviceGrid` uploads the points, chooses the grid, owns that workspace and
 fills both ops' common fields; a subclass allocates its outputs and sets its own fields of the second op.
 
-The pipeline (`resolve_specs`, `annotate`, `density_of`).  `post_proc.process`, `infer_tile.process_images`, `WsiInference` and the two
+The pipeline (`resolve_specs`, `annotate`, `density_of`, `ripley_of`).  `post_proc.process`, `infer_tile.process_images`, `WsiInference` and the two
 managers of infer_manager.py take `neighbours`, `clusters` and, where a map can be returned or written, `density`:
     neighbours  None or {"radius": r, "k": k}: every entry of the instance dict gains "neighbours" (`neighbours.annotate`)
     clusters    None or {"radius": r, "min_pts": m} with an optional "types": [ints], which needs nr_types: every entry gains
@@ -23,6 +23,10 @@ Radii and steps are pixels of the processed image.  A bad spec is refused by `re
 `clusters` imply the instance dict.  The analyses run on the FINISHED dict -- on a slide once, on the merged dict in slide
 coordinates, so they cross tile seams -- in the order neighbours, clusters, density; on rank 0, where the dict lives, with no
 collective; on the GPU where the model is on one, on the host otherwise.
+A fourth argument, `ripley` (None or {"radii": [r, ..]} with an optional "window"), is taken by `WsiInference` and the two managers
+only: the `ripley.PairCounts` of the finished dict over the image (`ripley.of_info`, here `ripley_of`), made after the other three.  It
+is about the slide, not about a nucleus or a place, so it annotates nothing; `PointSpecs` stays the three above, and `ripley.resolve`
+resolves the fourth spec, which its users carry beside their PointSpecs.
 """
 import collections
 import ctypes
@@ -242,3 +246,11 @@ def density_of(info, size_hw, specs, nr_types, device):
     from . import density as DN
 
     return DN.of_info(info, size_hw, specs.density[0], specs.density[1], nr_types, device=_device(device))
+
+
+def ripley_of(info, size_hw, spec, nr_types, device):
+    """The `ripley.PairCounts` of a finished instance dict over an image of size_hw = (h, w) processed pixels for a resolved `ripley`
+    spec (`ripley.resolve`, not None); `device` as in `annotate`."""
+    from . import ripley as RP
+
+    return RP.of_info(info, size_hw, spec[0], nr_types, device=_device(device), window=spec[1])

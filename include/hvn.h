@@ -40,7 +40,7 @@ typedef struct hvn_view {
 
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
-       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17 };
+       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -175,6 +175,24 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: a null pointer, count not 4-byte or a table / workspace not 8-byte aligned, batch != 1, N < 1, T outside
  *           1..16, H or W < 1, kh or kw < 1.  HVN_E_SIZE: H or W > 16384, T H W > 2^28, N > 2^26, kh or kw > 4096 or kh * kw > 2^22,
  *           x2.sn too small.
+ *     NBR_PAIRS      typed pair counts by distance bin over the same grid: the integers under Ripley's cross-type K function
+ *           (hover_net_amd/ripley.py holds the definition; csrc/hvn_pairs.hip).  Runs after NBR_GRID on the same stream and reads the
+ *           workspace as that op left it for the same N, kh, kw and table (x.base is not read); x.h, kh, kw, w, x2.base and x2.sn are
+ *           the shared fields above, and table[3] is r2 of the LARGEST radius.  cout = T in 1..16, `_rsv` = R in 1..32, T T R <= 4096;
+ *           y.base = int64 acc [2][T][T][R], contiguous (8-byte aligned); bias = float64 table {wx0, wy0, wx1, wy1, r_0 .. r_{R-1},
+ *           r2_0 .. r2_{R-1}} of 4 + 2 R doubles on the device (8-byte aligned; read as doubles whatever the pointer's declared type, as
+ *           w is): the window, the ascending radii and their squares r2_k = r_k * r_k as the caller rounded them.  With d2 as in
+ *           NBR_QUERY, kmin = the smallest k with d2 <= r2_k (none: the pair is not counted), b_i = min(x_i - wx0, wx1 - x_i, y_i -
+ *           wy0, wy1 - y_i), each term one subtraction, and m_i = the number of k with r_k <= b_i, every ordered pair (i, j), j != i,
+ *           of types (a, b) adds 1 to acc[0][a][b][kmin] and, only if kmin < m_i, 1 to acc[1][a][b][kmin] and -1 to acc[1][a][b][m_i]
+ *           (the latter where m_i < R).  The running sums over the last axis are the pair counts within r_k, of all i (plane 0) and of
+ *           the i that lie at least r_k inside the window (plane 1, the border method).  A type outside [0, T) lands in no bin, as i or
+ *           as j.  EVERY element of acc is written, whatever it held before: the op clears it itself, in stream order.  Integer sums
+ *           (32-bit in LDS, flushed into 64-bit global atomics before a word could pass 2^23): a function of the inputs alone.  Loops
+ *           are bounded by cell_start values clamped to [0, N]: a workspace NBR_GRID did not fill gives wrong numbers, no access
+ *           outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer, acc or a table / workspace not 8-byte aligned, batch != 1, N < 1, T outside 1..16, R outside
+ *           1..32, kh or kw < 1.  HVN_E_SIZE: T T R > 4096, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
