@@ -511,6 +511,30 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.rt & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs: misaligned window and radius table (8)");
         return hvn_launch_status(hvn_launch_nbr_pairs(a, s), "nbr_pairs");
     }
+    case HVN_OP_NBR_REGIONS: {
+        NbrRegionsArgs a;
+        a.table = (const double *)op->w;
+        a.edges = (const double *)op->bias;
+        a.edge_region = (const int *)op->res.base;
+        a.rows = (const int *)op->y2.base;
+        a.workspace = op->x2.base;
+        a.out = (int *)op->y.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.G = op->_rsv; a.E = op->res.h;
+        if (!a.workspace || !a.out || !a.edges || !a.edge_region || !a.rows) return hvn_fail(HVN_E_ARG, "nbr_regions: null pointer");
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_regions: %d types outside 1..16", a.T);
+        if (a.G < 1) return hvn_fail(HVN_E_ARG, "nbr_regions: %d regions, fewer than one", a.G);
+        if (a.E < 1) return hvn_fail(HVN_E_ARG, "nbr_regions: %d edges, fewer than one", a.E);
+        if (op->y2.sn < 1) return hvn_fail(HVN_E_ARG, "nbr_regions: row lists of %ld entries, fewer than one", (long)op->y2.sn);
+        if (a.G > HVN_NBR_REGIONS_MAX_G) return hvn_fail(HVN_E_SIZE, "nbr_regions: %d regions above 4096", a.G);
+        if (a.E > HVN_NBR_REGIONS_MAX_E) return hvn_fail(HVN_E_SIZE, "nbr_regions: %d edges above 2^22", a.E);
+        if (int rc = nbr_common("nbr_regions", op, batch)) return rc;
+        if ((long)op->y2.sn > HVN_NBR_REGIONS_MAX_ENTRIES(a.E, a.ncy))
+            return hvn_fail(HVN_E_SIZE, "nbr_regions: row lists of %ld entries, more than 8 E + kh = %ld", (long)op->y2.sn, HVN_NBR_REGIONS_MAX_ENTRIES(a.E, a.ncy));
+        a.M = (int)op->y2.sn;
+        if (((uintptr_t)a.out | (uintptr_t)a.edge_region | (uintptr_t)a.rows) & 3) return hvn_fail(HVN_E_ARG, "nbr_regions: misaligned out, edge_region or rows (4)");
+        if ((uintptr_t)a.edges & 7) return hvn_fail(HVN_E_ARG, "nbr_regions: misaligned edge table (8)");
+        return hvn_launch_status(hvn_launch_nbr_regions(a, s), "nbr_regions");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

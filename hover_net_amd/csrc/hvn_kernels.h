@@ -303,6 +303,20 @@ struct NbrPairsArgs {
     int N, ncy, ncx, T, R;
 };
 int hvn_launch_nbr_pairs(const NbrPairsArgs &a, hipStream_t stream);
+// hvn_regions.hip: exact point-in-polygon of the points against the canonical edges of G regions (hover_net_amd/regions.py)
+#define HVN_NBR_REGIONS_MAX_G 4096
+#define HVN_NBR_REGIONS_MAX_E (1 << 22)
+#define HVN_NBR_REGIONS_MAX_ENTRIES(E, ncy) (8L * (E) + (ncy))      // the row lists' total length
+struct NbrRegionsArgs {
+    const double *table;        // {x0, y0, c, r2}, as for the grid (r2 is not read)
+    const double *edges;        // [E][4] = (ax, ay, bx, by), ay < by
+    const int *edge_region;     // [E], ascending
+    const int *rows;            // row_start [ncy + 1], then the edge numbers of the row lists [M]
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    int *out;                   // first [N], hits [N], count [G][T]; count is cleared in stream order, then every element is written
+    int N, ncy, ncx, T, G, E, M;
+};
+int hvn_launch_nbr_regions(const NbrRegionsArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

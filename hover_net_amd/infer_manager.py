@@ -124,6 +124,31 @@ def _given(run_args, *names):
     return {k: run_args[k] for k in names if run_args.get(k) is not None}
 
 
+def _regions_dir(spec):
+    """run_args["regions"]: None -> None, {"dir": d} with an optional "scale" -> (d, scale); ValueError / TypeError otherwise."""
+    from . import regions as RG
+
+    if spec is None:
+        return None
+    if not isinstance(spec, dict) or not isinstance(spec.get("dir"), (str, os.PathLike)) or not set(spec) <= {"dir", "scale"}:
+        raise ValueError('regions=%r: None or {"dir": directory of <name>.geojson files} with an optional "scale"' % (spec,))
+    return os.fspath(spec["dir"]), RG._check_scale(spec.get("scale", 1.0))
+
+
+def _regions_spec(regions, name):
+    """The `regions` argument of one image or slide: {"regions": <dir>/<name>.geojson, "scale": s}, or None (logged) where that file is
+    missing: the image is then processed without regions."""
+    import logging
+
+    if regions is None:
+        return None
+    path = os.path.join(regions[0], name + ".geojson")
+    if not os.path.isfile(path):
+        logging.warning("regions: %s is missing; %s is processed without regions", path, name)
+        return None
+    return {"regions": path, "scale": regions[1]}
+
+
 class InferManager:
     """`InferManager(method={"model_args": {"nr_types": .., "mode": ..}, "model_path": ..}, type_info_path=..)`
     (infer/base.py:22-27 takes the same keywords).  `model=` hands over an already built network instead of a checkpoint
@@ -164,13 +189,17 @@ class InferManager:
         with `density` rank 0 also writes `density/<name>.npz` (`density.save`: `count` int32 [T, H, W], `origin`, `step`, `radius`);
         `json/` is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py) -- rank 0
         also writes `ripley/<name>.npz` (`ripley.save`: the typed pair counts under the cross-type K function, of every image's finished
-        dict over the image); `json/` is as without it.
+        dict over the image); `json/` is as without it; regions (default None): {"dir": d} with an optional "scale"
+        (hover_net_amd/regions.py) -- an image with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels
+        of the image) gets "region" on every nucleus of `json/` and rank 0 writes `regions/<name>.npz` (`regions.save`: which region
+        holds which nucleus, typed counts per region); an image without that file is logged and processed as without the argument.
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
         from . import infer_tile
         from . import density as DN
         from . import points as PT
+        from . import regions as RG
         from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
@@ -187,6 +216,7 @@ class InferManager:
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
         ripley = RP.resolve(run_args.get("ripley"))          # likewise
+        regions = _regions_dir(run_args.get("regions"))      # likewise
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -195,7 +225,7 @@ class InferManager:
 
         pending = list_files(input_dir)
         if rank == 0:
-            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()) + (("ripley",) if ripley is not None else ()):
+            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()) + (("ripley",) if ripley is not None else ()) + (("regions",) if regions is not None else ()):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
@@ -225,6 +255,9 @@ class InferManager:
                 name = pathlib.Path(path).stem
                 pred_inst, inst_info = res[0], res[1]
                 raw_map = res[2] if save_raw_map else None
+                rspec = RG.resolve(_regions_spec(regions, name))
+                if rspec is not None:
+                    RG.save("%s/regions/%s.npz" % (output_dir, name), PT.regions_of(inst_info, rspec, self.nr_types, self._collective_device()))
                 self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
                 if specs.density is not None:
                     DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], specs))
@@ -314,12 +347,16 @@ class WsiManager(InferManager):
         pixels at proc_mag, on the merged slide dict (`WsiInference`) -- every nucleus of the json gains "neighbours" / "cluster", and with `density` rank 0 also
         writes `density/<name>.npz` (`density.save`); the json is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window"
         (hover_net_amd/ripley.py), in pixels at proc_mag -- rank 0 also writes `ripley/<name>.npz` (`ripley.save`), the pair counts of the merged slide
-        dict (`WsiInference(ripley=...)`); the json is as without it.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        dict (`WsiInference(ripley=...)`); the json is as without it; regions (default None): {"dir": d} with an optional "scale"
+        (hover_net_amd/regions.py) -- a slide with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels at proc_mag) gets
+        "region" on every nucleus of the json and rank 0 writes `regions/<name>.npz` (`regions.save`) from the merged slide dict
+        (`WsiInference(regions=...)`); a slide without that file is logged and processed as without the argument.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
         from . import density as DN
         from . import points as PT
+        from . import regions as RG
         from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
@@ -328,6 +365,7 @@ class WsiManager(InferManager):
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
         ripley = RP.resolve(run_args.get("ripley"))          # likewise
+        regions = _regions_dir(run_args.get("regions"))      # likewise
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -346,6 +384,8 @@ class WsiManager(InferManager):
                 os.makedirs(output_dir + "/density/", exist_ok=True)
             if ripley is not None:
                 os.makedirs(output_dir + "/ripley/", exist_ok=True)
+            if regions is not None:
+                os.makedirs(output_dir + "/regions/", exist_ok=True)
         status = {}
         for wsi_path in sorted(glob.glob(input_dir + "/*")):
             if os.path.isdir(wsi_path):
@@ -369,8 +409,10 @@ class WsiManager(InferManager):
                     viz.save_png("%s/mask/%s.png" % (output_dir, name), np.repeat((mask * 255).astype(np.uint8)[..., None], 3, -1))
                 if rank == 0 and save_thumb:
                     viz.save_png("%s/thumb/%s.png" % (output_dir, name), slide.thumbnail(32))
+                rspec = _regions_spec(regions, name)
                 if self.wsi_fn is not None:
                     _inst_map, inst_info = self.wsi_fn(slide, mask)
+                    rcs = None if rspec is None or rank != 0 else PT.regions_of(inst_info, RG.resolve(rspec), self.nr_types, self._collective_device())
                     dmap = None if specs.density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], specs)
                     pcs = None if ripley is None or rank != 0 else PT.ripley_of(inst_info, slide.shape[:2], ripley, self.nr_types, self._collective_device())
                 else:
@@ -380,15 +422,17 @@ class WsiManager(InferManager):
                                                  **({"features": True} if run_args.get("save_features", False) else {}),
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-                                                 **_given(run_args, *_POINT_ARGS, "ripley"))
+                                                 **_given(run_args, *_POINT_ARGS, "ripley"), **_given({"regions": rspec}, "regions"))
                     _inst_map, inst_info = wsi.run(slide, mask)
-                    dmap, pcs = wsi.density, wsi.ripley
+                    dmap, pcs, rcs = wsi.density, wsi.ripley, wsi.regions
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)
                     if specs.density is not None:
                         DN.save("%s/density/%s.npz" % (output_dir, name), dmap)
                     if ripley is not None:
                         RP.save("%s/ripley/%s.npz" % (output_dir, name), pcs)
+                    if rspec is not None:
+                        RG.save("%s/regions/%s.npz" % (output_dir, name), rcs)
                 status[name] = "done"
             except Exception:                                 # noqa: BLE001  (the reference logs and moves on to the next slide)
                 logging.exception("Crash")

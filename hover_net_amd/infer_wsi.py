@@ -511,7 +511,7 @@ class DeviceMerger:
 class WsiInference:
     def __init__(self, model, nr_types=None, batch_size=32, chunk_shape=10000, tile_shape=2048, ambiguous_size=128,
                  patch_input_shape=None, patch_output_shape=None, device_contours=False, device_mask=False, *, features=False, tta=None,
-                 stain_norm=None, neighbours=None, clusters=None, density=None, ripley=None):
+                 stain_norm=None, neighbours=None, clusters=None, density=None, ripley=None, regions=None):
         """neighbours / clusters / density: the point-pattern analyses of hover_net_amd/points.py, computed ONCE on the final dict after
         the merge, in slide coordinates (the tiles' origins are already in the centroids).  With `density`, `self.density` holds the
         slide's `density.DensityMap` over its processed size on rank 0 (None elsewhere and before the first slide); the return value
@@ -519,6 +519,10 @@ class WsiInference:
         ripley: None or {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py): `self.ripley` holds the slide's
         `ripley.PairCounts` -- the typed pair counts under the cross-type K function, of the merged dict over the processed slide -- on
         rank 0 (None elsewhere and before the first slide), computed once after the merge as the others are; nothing else changes.
+        regions: None or {"regions": RegionSet | list of regions | GeoJSON path or dict} with an optional "scale" (hover_net_amd/regions.py),
+        in pixels of the processed slide after the scale: `self.regions` holds the slide's `regions.RegionCounts` -- which annotated region
+        holds which nucleus of the merged dict, and the typed counts per region -- on rank 0 (None elsewhere and before the first slide),
+        computed last, once after the merge; every entry of the dict gains "region" (the smallest region that holds it, or -1).
         stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
         `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
         (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every
@@ -558,6 +562,10 @@ class WsiInference:
 
         self.ripley_spec = RP.resolve(ripley)      # the fourth analysis, carried beside `self.points`
         self.ripley = None                         # the last slide's PairCounts (rank 0), with `ripley`
+        from . import regions as RG
+
+        self.regions_spec = RG.resolve(regions)    # the fifth, a RegionSet, carried the same way
+        self.regions = None                        # the last slide's RegionCounts (rank 0), with `regions`
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -918,7 +926,7 @@ class WsiInference:
 
     def _finish(self, out):
         """(inst_map, inst_info) of the finished slide on rank 0, after the point-pattern analyses (points.py): the dict's entries are
-        annotated and, with `density` / `ripley`, `self.density` / `self.ripley` are set."""
+        annotated and, with `density` / `ripley` / `regions`, `self.density` / `self.ripley` / `self.regions` are set."""
         from . import points as PT
 
         PT.annotate(out[1], self.points, self.nr_types, self.device)
@@ -926,4 +934,6 @@ class WsiInference:
             self.density = PT.density_of(out[1], self._shape, self.points, self.nr_types, self.device)
         if self.ripley_spec is not None:
             self.ripley = PT.ripley_of(out[1], self._shape, self.ripley_spec, self.nr_types, self.device)
+        if self.regions_spec is not None:
+            self.regions = PT.regions_of(out[1], self.regions_spec, self.nr_types, self.device)
         return out

@@ -42,6 +42,7 @@ OP_NBR_GRID, OP_NBR_QUERY = 14, 15     # nucleus neighbourhoods (neighbours.py):
 OP_NBR_CLUSTER = 16     # nucleus clusters over the same grid (clusters.py): never part of a plan
 OP_NBR_DENSITY = 17     # nucleus density maps over the same grid (density.py): never part of a plan
 OP_NBR_PAIRS = 18       # typed pair counts by distance bin over the same grid (ripley.py): never part of a plan
+OP_NBR_REGIONS = 19     # point-in-polygon against annotated regions over the same grid (regions.py): never part of a plan
 
 
 @dataclass

@@ -27,6 +27,9 @@ A fourth argument, `ripley` (None or {"radii": [r, ..]} with an optional "window
 only: the `ripley.PairCounts` of the finished dict over the image (`ripley.of_info`, here `ripley_of`), made after the other three.  It
 is about the slide, not about a nucleus or a place, so it annotates nothing; `PointSpecs` stays the three above, and `ripley.resolve`
 resolves the fourth spec, which its users carry beside their PointSpecs.
+A fifth, `regions` (None or {"regions": RegionSet | list | GeoJSON path} with an optional "scale"; the managers take {"dir": d} and read
+`<d>/<name>.geojson`), is carried the same way: the `regions.RegionCounts` of the finished dict against annotated polygons
+(`regions.of_info`, here `regions_of`), made last; every entry gains "region" (`regions.annotate`).
 """
 import collections
 import ctypes
@@ -254,3 +257,13 @@ def ripley_of(info, size_hw, spec, nr_types, device):
     from . import ripley as RP
 
     return RP.of_info(info, size_hw, spec[0], nr_types, device=_device(device), window=spec[1])
+
+
+def regions_of(info, rs, nr_types, device):
+    """The `regions.RegionCounts` of a finished instance dict for a resolved `regions` spec (`regions.resolve`, not None), with every
+    entry annotated ("region"); `device` as in `annotate`."""
+    from . import regions as RG
+
+    rc = RG.of_info(info, rs, nr_types, device=_device(device))
+    RG.annotate(info, rc)
+    return rc

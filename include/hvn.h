@@ -40,7 +40,7 @@ typedef struct hvn_view {
 
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
-       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18 };
+       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -193,6 +193,29 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           outside the arrays and no loop without an end.
  *           HVN_E_ARG: a null pointer, acc or a table / workspace not 8-byte aligned, batch != 1, N < 1, T outside 1..16, R outside
  *           1..32, kh or kw < 1.  HVN_E_SIZE: T T R > 4096, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn too small.
+ *     NBR_REGIONS    exact point-in-polygon of the points against the canonical edges of G annotated regions: which regions hold which
+ *           point, and the typed counts per region (hover_net_amd/regions.py holds the definition; csrc/hvn_regions.hip).  Runs after
+ *           NBR_GRID on the same stream and reads the workspace as that op left it for the same N, kh, kw and table (x.base is not read;
+ *           table[3] is not read either); x.h, kh, kw, w, x2.base and x2.sn are the shared fields above.  The extra tables take fields the
+ *           family leaves free: cout = T in 1..16; `_rsv` = G in 1..4096; bias = float64 edges [E][4] = (ax, ay, bx, by) with ay < by on
+ *           the device (8-byte aligned; read as doubles whatever the pointer's declared type, as w is); res.base = int32 edge_region [E]
+ *           (4-byte aligned), ascending, and res.h = E in 1..2^22; y2.base = int32 rows (4-byte aligned): row_start [kh + 1] followed by
+ *           the edge numbers of the row lists, and y2.sn = M, the lists' total length, in 1..8 E + kh: the edges of grid row k are
+ *           rows[kh + 1 + j] for row_start[k] <= j < row_start[k + 1], and the caller lists an edge in every row from that of ay to that
+ *           of by (NBR_GRID's row formula, which is monotone; an edge that no point can cross may be left out), the edges of one region
+ *           adjacent and the regions ascending (the library
+ *           does not check that); y.base = int32 out [2 N + G T], contiguous (4-byte aligned): first [N], hits [N], count [G][T].
+ *           Point (px, py) crosses an edge when ay <= py, py < by and (px - ax) * (by - ay) < (bx - ax) * (py - ay), in float64, one
+ *           rounding per operation, no fused multiply-add, the two products compared; it is inside region g when it crosses an odd
+ *           number of g's edges.  first[i] = the smallest g with point i inside or -1, hits[i] = the number of such g, count[g][t] =
+ *           the points of type t inside g; i is a position in NBR_GRID's x.  A type outside [0, T) is counted nowhere and the point
+ *           still gets first / hits; a region id outside [0, G) is counted nowhere.  EVERY element of out is written, whatever it held
+ *           before: the op clears count itself, in stream order.  Integer sums (wave ballots, summed per workgroup, global atomics): a function of the inputs
+ *           alone.  Row starts are clamped to [0, M], edge numbers to [0, E), the walk of a workgroup's rows ends after 256 rounds:
+ *           tables or a workspace the caller did not fill give wrong numbers, no access outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer, out / edge_region / rows not 4-byte or edges / table / workspace not 8-byte aligned, batch != 1,
+ *           N < 1, T outside 1..16, G < 1, E < 1, M < 1, kh or kw < 1.  HVN_E_SIZE: G > 4096, E > 2^22, M > 8 E + kh, N > 2^26, kh or
+ *           kw > 4096 or kh * kw > 2^22, x2.sn too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
