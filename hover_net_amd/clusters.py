@@ -38,12 +38,17 @@ MAX_MIN_PTS, MAX_T = 1 << 26, NB.MAX_T
 
 def _check(xy, types, radius, min_pts, of_types):
     """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, m, of_types tuple | None)."""
-    xy, types, r, _, _ = NB._check(xy, types, radius, 1, None)
+    xy, r = P.check_xy(xy), P.check_radius(radius)
+    types, _ = P.check_types(types, xy.shape[0], None)
+    return xy, types, r, _check_min_pts(min_pts), _of_types(of_types, types is not None)
+
+
+def _check_min_pts(min_pts):
     if not P.is_integer(min_pts):
         raise TypeError("min_pts must be an integer, got %r" % (min_pts,))
     if not 1 <= int(min_pts) <= MAX_MIN_PTS:
         raise ValueError("min_pts = %d outside 1..2^26" % min_pts)
-    return xy, types, r, int(min_pts), _of_types(of_types, types is not None)
+    return int(min_pts)
 
 
 def _of_types(of_types, typed):
@@ -137,8 +142,7 @@ def cluster_workspace_bytes(n):
 
 
 class DeviceClusters(P.DeviceGrid):
-    """One device clustering (`points.DeviceGrid`): `run_grid` and `run_cluster` launch on the current stream without synchronising
-    (tools/clusters_bench.py times them apart), `result` reads the two arrays back."""
+    """One device clustering (`points.DeviceGrid`: `run_grid`, `run_op`, `run`); `result` reads the two arrays back."""
 
     def __init__(self, xy, types, radius, min_pts, of_types=None, device="cuda"):
         import torch
@@ -154,9 +158,6 @@ class DeviceClusters(P.DeviceGrid):
         op.y.base, op.y2.base = self.label.data_ptr(), self.degree.data_ptr()
         op.res.base, op.res.sn = self.ws2.data_ptr(), nbytes2
 
-    def run_cluster(self):
-        self._run(1)
-
     def result(self):
         return {"label": self.label.cpu().numpy(), "degree": self.degree.cpu().numpy()}
 
@@ -164,17 +165,12 @@ class DeviceClusters(P.DeviceGrid):
 def cluster_device(xy, types, radius, min_pts, of_types=None, device="cuda"):
     """`cluster_host` on the GPU: the same two arrays.  The grid is chosen here on the host; the device builds it and clusters (two
     ops on the current stream); the one synchronisation is the readback."""
-    q = DeviceClusters(xy, types, radius, min_pts, of_types, device)
-    q.run_grid()
-    q.run_cluster()
-    return q.result()
+    return DeviceClusters(xy, types, radius, min_pts, of_types, device).run().result()
 
 
 def cluster(xy, types, radius, min_pts, of_types=None, device=None):
     """`cluster_host` with device=None, `cluster_device` on `device` otherwise."""
-    if device is None:
-        return cluster_host(xy, types, radius, min_pts, of_types)
-    return cluster_device(xy, types, radius, min_pts, of_types, device)
+    return cluster_host(xy, types, radius, min_pts, of_types) if device is None else cluster_device(xy, types, radius, min_pts, of_types, device)
 
 
 # ---- what a user reads ---------------------------------------------------------------------------
@@ -186,11 +182,11 @@ def resolve(spec, typed=True):
         return None
     if not isinstance(spec, dict) or not {"radius", "min_pts"} <= set(spec) <= {"radius", "min_pts", "types"}:
         raise ValueError('clusters=%r: None or {"radius": r, "min_pts": m} with an optional "types": [ints]' % (spec,))
-    _check(np.zeros((1, 2)), None, spec["radius"], spec["min_pts"], None)
+    r, m = P.check_radius(spec["radius"]), _check_min_pts(spec["min_pts"])
     of = None if spec.get("types") is None else _of_types(spec["types"], True)
     if of is not None and not typed:
         raise ValueError('clusters=%r: "types" needs a model with a type branch' % (spec,))
-    return float(spec["radius"]), int(spec["min_pts"]), of
+    return r, m, of
 
 
 def annotate(info, radius, min_pts, nr_types, of_types=None, device=None):

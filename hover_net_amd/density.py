@@ -89,7 +89,8 @@ def _check_raster(raster, t):
 
 def _check(xy, types, radius, raster, nr_types):
     """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, Raster, T)."""
-    xy, types, r, _, t = NB._check(xy, types, radius, 1, nr_types)
+    xy, r = P.check_xy(xy), P.check_radius(radius)
+    types, t = P.check_types(types, xy.shape[0], nr_types)
     return xy, types, r, _check_raster(raster, t), t
 
 
@@ -148,9 +149,8 @@ def density_host(xy, types, radius, raster, nr_types=None):
 
 # ---- the device ----------------------------------------------------------------------------------
 class DeviceDensity(P.DeviceGrid):
-    """One device density map (`points.DeviceGrid`, the grid being that of the points): `run_grid` and `run_density` launch on the
-    current stream without synchronising (tools/density_bench.py times them apart), `result` reads the map back.  The op writes
-    every element of `count`: nothing is cleared here."""
+    """One device density map (`points.DeviceGrid`: `run_grid`, `run_op`, `run`; the grid is that of the points); `result` reads the
+    map back.  The op writes every element of `count`: nothing is cleared here."""
 
     def __init__(self, xy, types, radius, raster, nr_types=None, device="cuda"):
         import torch
@@ -164,9 +164,6 @@ class DeviceDensity(P.DeviceGrid):
         op.cout, op.bias = t, self.raster_table.data_ptr()
         op.y.base, op.y.h, op.y.w = self.count.data_ptr(), ra.H, ra.W
 
-    def run_density(self):
-        self._run(1)
-
     def result(self):
         return self.count.cpu().numpy()
 
@@ -174,17 +171,12 @@ class DeviceDensity(P.DeviceGrid):
 def density_device(xy, types, radius, raster, nr_types=None, device="cuda"):
     """`density_host` on the GPU: the same array.  The grid is chosen here on the host; the device builds it and counts (two ops on
     the current stream); the one synchronisation is the readback."""
-    q = DeviceDensity(xy, types, radius, raster, nr_types, device)
-    q.run_grid()
-    q.run_density()
-    return q.result()
+    return DeviceDensity(xy, types, radius, raster, nr_types, device).run().result()
 
 
 def density(xy, types, radius, raster, nr_types=None, device=None):
     """`density_host` with device=None, `density_device` on `device` otherwise."""
-    if device is None:
-        return density_host(xy, types, radius, raster, nr_types)
-    return density_device(xy, types, radius, raster, nr_types, device)
+    return density_host(xy, types, radius, raster, nr_types) if device is None else density_device(xy, types, radius, raster, nr_types, device)
 
 
 # ---- what a user reads ---------------------------------------------------------------------------
@@ -196,12 +188,12 @@ def resolve(spec):
         return None
     if not isinstance(spec, dict) or set(spec) != {"radius", "step"}:
         raise ValueError('density=%r: None or {"radius": r, "step": s}' % (spec,))
-    NB._check(np.zeros((1, 2)), None, spec["radius"], 1, None)
+    r = P.check_radius(spec["radius"])
     if not P.is_integer(spec["step"]):
         raise TypeError("step must be an integer, got %r" % (spec["step"],))
     if int(spec["step"]) < 1:
         raise ValueError("step = %d, below 1" % spec["step"])
-    return float(spec["radius"]), int(spec["step"])
+    return r, int(spec["step"])
 
 
 def raster_of(size_hw, step):
@@ -222,8 +214,8 @@ def of_info(info, size_hw, radius, step, nr_types, device=None):
     The centroids are the points, entry["type"] the types, as in `neighbours.annotate` (nr_types=None: untyped, T = 1).  An empty dict
     gives an all-zero map.  device=None: `density_host`."""
     ra = raster_of(size_hw, step)
-    NB._check(np.zeros((1, 2)), None, radius, 1, nr_types)
-    t = 1 if nr_types is None else int(nr_types)
+    P.check_radius(radius)
+    _, t = P.check_types(None, 0, nr_types)
     ra = _check_raster(ra, t)
     if not info:
         return DensityMap(np.zeros((t, ra.H, ra.W), np.int32), (ra.ox, ra.oy), int(step), float(radius))

@@ -116,9 +116,6 @@ def mat_dict(pred_inst, inst_info, nr_types, raw_map=None):
     return out
 
 
-_POINT_ARGS = ("neighbours", "clusters", "density")     # hover_net_amd/points.py
-
-
 def _given(run_args, *names):
     """The entries of run_args under `names` that are not None, to forward as keywords."""
     return {k: run_args[k] for k in names if run_args.get(k) is not None}
@@ -197,10 +194,8 @@ class InferManager:
         import psutil
 
         from . import infer_tile
-        from . import density as DN
         from . import points as PT
         from . import regions as RG
-        from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
 
@@ -214,9 +209,9 @@ class InferManager:
         save_features = bool(run_args.get("save_features", False))
         tta = TT.views(run_args.get("tta"))                 # ValueError before any file is touched
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
-        specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
-        ripley = RP.resolve(run_args.get("ripley"))          # likewise
-        regions = _regions_dir(run_args.get("regions"))      # likewise
+        point_args = {k: run_args.get(k) for k in PT.ARGS}
+        specs = PT.resolve_specs(**dict(point_args, regions=None), typed=self.nr_types is not None)   # likewise
+        regions = _regions_dir(point_args["regions"])        # likewise; the directory, resolved per image by `_regions_spec`
         overlay_device = (self._collective_device() or "cuda") if run_args.get("device_overlay", False) else None
         win = int(run_args.get("patch_input_shape", 270 if self.mode == "original" else 256))
         msk = int(run_args.get("patch_output_shape", 80 if self.mode == "original" else 164))
@@ -225,7 +220,7 @@ class InferManager:
 
         pending = list_files(input_dir)
         if rank == 0:
-            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + (("density",) if specs.density is not None else ()) + (("ripley",) if ripley is not None else ()) + (("regions",) if regions is not None else ()):
+            for sub in ("json", "mat", "overlay") + (("qupath",) if save_qupath else ()) + PT.output_dirs(specs._replace(regions=regions)):
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
@@ -255,22 +250,12 @@ class InferManager:
                 name = pathlib.Path(path).stem
                 pred_inst, inst_info = res[0], res[1]
                 raw_map = res[2] if save_raw_map else None
-                rspec = RG.resolve(_regions_spec(regions, name))
-                if rspec is not None:
-                    RG.save("%s/regions/%s.npz" % (output_dir, name), PT.regions_of(inst_info, rspec, self.nr_types, self._collective_device()))
+                results = PT.summaries(inst_info, img.shape[:2], specs._replace(regions=RG.resolve(_regions_spec(regions, name))),
+                                       self.nr_types, self._collective_device())        # `process` has annotated; "region" is added here
                 self._write(output_dir, name, img, pred_inst, inst_info, raw_map, draw_dot, save_qupath, overlay_device=overlay_device)
-                if specs.density is not None:
-                    DN.save("%s/density/%s.npz" % (output_dir, name), self._density_of(inst_info, img.shape[:2], specs))
-                if ripley is not None:
-                    RP.save("%s/ripley/%s.npz" % (output_dir, name), PT.ripley_of(inst_info, img.shape[:2], ripley, self.nr_types, self._collective_device()))
+                PT.save_results(output_dir, name, results)
                 done.append(name)
         return done
-
-    def _density_of(self, inst_info, size_hw, specs):
-        """`points.density_of` of a finished dict, on the device of the model."""
-        from . import points as PT
-
-        return PT.density_of(inst_info, size_hw, specs, self.nr_types, self._collective_device())
 
     def _collective_device(self):
         try:
@@ -354,18 +339,16 @@ class WsiManager(InferManager):
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask
-        from . import density as DN
         from . import points as PT
         from . import regions as RG
-        from . import ripley as RP
         from . import stain as ST
         from . import tta as TT
 
         tta = TT.views(run_args.get("tta"))                 # ValueError before any slide is opened
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
-        specs = PT.resolve_specs(*(run_args.get(k) for k in _POINT_ARGS), typed=self.nr_types is not None)   # likewise
-        ripley = RP.resolve(run_args.get("ripley"))          # likewise
-        regions = _regions_dir(run_args.get("regions"))      # likewise
+        point_args = {k: run_args.get(k) for k in PT.ARGS}
+        specs = PT.resolve_specs(**dict(point_args, regions=None), typed=self.nr_types is not None)   # likewise
+        regions = _regions_dir(point_args["regions"])        # likewise; the directory, resolved per image by `_regions_spec`
         input_dir, output_dir = run_args["input_dir"], run_args["output_dir"]
         mask_dir = run_args.get("input_mask_dir") or ""
         save_thumb, save_mask = bool(run_args.get("save_thumb", False)), bool(run_args.get("save_mask", False))
@@ -380,12 +363,8 @@ class WsiManager(InferManager):
                 os.makedirs(output_dir + "/thumb/", exist_ok=True)
             if save_mask:
                 os.makedirs(output_dir + "/mask/", exist_ok=True)
-            if specs.density is not None:
-                os.makedirs(output_dir + "/density/", exist_ok=True)
-            if ripley is not None:
-                os.makedirs(output_dir + "/ripley/", exist_ok=True)
-            if regions is not None:
-                os.makedirs(output_dir + "/regions/", exist_ok=True)
+            for sub in PT.output_dirs(specs._replace(regions=regions)):
+                os.makedirs("%s/%s/" % (output_dir, sub), exist_ok=True)
         status = {}
         for wsi_path in sorted(glob.glob(input_dir + "/*")):
             if os.path.isdir(wsi_path):
@@ -409,12 +388,11 @@ class WsiManager(InferManager):
                     viz.save_png("%s/mask/%s.png" % (output_dir, name), np.repeat((mask * 255).astype(np.uint8)[..., None], 3, -1))
                 if rank == 0 and save_thumb:
                     viz.save_png("%s/thumb/%s.png" % (output_dir, name), slide.thumbnail(32))
-                rspec = _regions_spec(regions, name)
+                rspec, results = _regions_spec(regions, name), None
                 if self.wsi_fn is not None:
                     _inst_map, inst_info = self.wsi_fn(slide, mask)
-                    rcs = None if rspec is None or rank != 0 else PT.regions_of(inst_info, RG.resolve(rspec), self.nr_types, self._collective_device())
-                    dmap = None if specs.density is None or rank != 0 else self._density_of(inst_info, slide.shape[:2], specs)
-                    pcs = None if ripley is None or rank != 0 else PT.ripley_of(inst_info, slide.shape[:2], ripley, self.nr_types, self._collective_device())
+                    if rank == 0:
+                        results = PT.summaries(inst_info, slide.shape[:2], specs._replace(regions=RG.resolve(rspec)), self.nr_types, self._collective_device())
                 else:
                     wsi = infer_wsi.WsiInference(self.model, nr_types=self.nr_types, batch_size=int(run_args.get("batch_size", 32)),
                                                  chunk_shape=int(run_args.get("chunk_shape", 10000)), tile_shape=int(run_args.get("tile_shape", 2048)),
@@ -422,17 +400,12 @@ class WsiManager(InferManager):
                                                  **({"features": True} if run_args.get("save_features", False) else {}),
                                                  **({"tta": tta} if tta is not None else {}),
                                                  **({"stain_norm": stain_norm} if stain_norm is not None else {}),
-                                                 **_given(run_args, *_POINT_ARGS, "ripley"), **_given({"regions": rspec}, "regions"))
+                                                 **_given(dict(point_args, regions=rspec), *PT.ARGS))
                     _inst_map, inst_info = wsi.run(slide, mask)
-                    dmap, pcs, rcs = wsi.density, wsi.ripley, wsi.regions
+                    results = PT.PointResults(wsi.density, wsi.ripley, wsi.regions)
                 if rank == 0:
                     io_utils.save_json(json_path, inst_info, mag=proc_mag)
-                    if specs.density is not None:
-                        DN.save("%s/density/%s.npz" % (output_dir, name), dmap)
-                    if ripley is not None:
-                        RP.save("%s/ripley/%s.npz" % (output_dir, name), pcs)
-                    if rspec is not None:
-                        RG.save("%s/regions/%s.npz" % (output_dir, name), rcs)
+                    PT.save_results(output_dir, name, results)
                 status[name] = "done"
             except Exception:                                 # noqa: BLE001  (the reference logs and moves on to the next slide)
                 logging.exception("Crash")

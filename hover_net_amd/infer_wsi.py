@@ -555,17 +555,8 @@ class WsiInference:
         self.stain_norm = ST.resolve(stain_norm)
         from . import points as PT
 
-        self.points = PT.resolve_specs(neighbours, clusters, density, typed=nr_types is not None)
-        self.density_spec = self.points.density
-        self.density = None                        # the last slide's DensityMap (rank 0), with `density`
-        from . import ripley as RP
-
-        self.ripley_spec = RP.resolve(ripley)      # the fourth analysis, carried beside `self.points`
-        self.ripley = None                         # the last slide's PairCounts (rank 0), with `ripley`
-        from . import regions as RG
-
-        self.regions_spec = RG.resolve(regions)    # the fifth, a RegionSet, carried the same way
-        self.regions = None                        # the last slide's RegionCounts (rank 0), with `regions`
+        self.points = PT.resolve_specs(neighbours, clusters, density, ripley, regions, typed=nr_types is not None)
+        self.density = self.ripley = self.regions = None     # the last slide's DensityMap, PairCounts, RegionCounts (rank 0), where asked for
         self._stain_tables = None                  # the current slide's tables (`fit_stain`): numpy [3, 3, 256], or None
         self._sat = (None, None, None)
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -887,10 +878,10 @@ class WsiInference:
             shape = pred_map.shape[:2]
         shape = np.array([int(shape[0]), int(shape[1])])
         self._shape = shape
-        if self.density_spec is not None:          # a raster the op would refuse raises here, before any tile is processed
+        if self.points.density is not None:        # a raster the op would refuse raises here, before any tile is processed
             from . import density as DN
 
-            DN._check_raster(DN.raster_of(shape, self.density_spec[1]), 1 if self.nr_types is None else int(self.nr_types))
+            DN._check_raster(DN.raster_of(shape, self.points.density[1]), 1 if self.nr_types is None else int(self.nr_types))
         if mask is None:
             mask = np.ones((max(1, int(shape[0]) // 32), max(1, int(shape[1]) // 32)), np.uint8)
 
@@ -930,10 +921,5 @@ class WsiInference:
         from . import points as PT
 
         PT.annotate(out[1], self.points, self.nr_types, self.device)
-        if self.points.density is not None:
-            self.density = PT.density_of(out[1], self._shape, self.points, self.nr_types, self.device)
-        if self.ripley_spec is not None:
-            self.ripley = PT.ripley_of(out[1], self._shape, self.ripley_spec, self.nr_types, self.device)
-        if self.regions_spec is not None:
-            self.regions = PT.regions_of(out[1], self.regions_spec, self.nr_types, self.device)
+        self.density, self.ripley, self.regions = PT.summaries(out[1], self._shape, self.points, self.nr_types, self.device)
         return out

@@ -38,51 +38,25 @@ never wrong.
 import numpy as np
 
 from . import points as P
-from .points import MARGIN, MAX_AXIS, MAX_CELLS, Grid, cells, d2_of, grid, r2_of, workspace_bytes  # noqa: F401  (clusters.py, density.py and the tests reach them here)
+from .points import MARGIN, MAX_AXIS, MAX_CELLS, MAX_N, MAX_T, MIN_R2, Grid, cells, d2_of, grid, r2_of, workspace_bytes  # noqa: F401  (clusters.py, density.py and the tests reach them here)
 
-MAX_N, MAX_K, MAX_T = 1 << 26, 16, 16
-MIN_R2 = 2.0 ** -1000
+MAX_K = 16
 _PAIRS = 1 << 22                # candidate pairs per round of `query_host`
 
 
-def _check(xy, types, radius, k, nr_types):
-    """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, k, T)."""
-    if not isinstance(xy, np.ndarray) or xy.dtype != np.float64:
-        raise TypeError("xy must be a float64 numpy array [N, 2], got %s" % (getattr(xy, "dtype", type(xy).__name__),))
-    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
-        raise ValueError("xy must be [N, 2] with N >= 1, got %s" % (xy.shape,))
-    n = xy.shape[0]
-    if n > MAX_N:
-        raise ValueError("%d points, more than 2^26" % n)
-    if not np.isfinite(xy).all():
-        raise ValueError("xy holds a coordinate that is not finite")
-    with np.errstate(over="ignore"):
-        if not np.isfinite(xy.max(0) - xy.min(0)).all():
-            raise ValueError("the extent of xy is not a finite float64")
-    if not P.is_number(radius):
-        raise TypeError("radius must be a number, got %r" % (radius,))
-    r = float(radius)
-    if not (r > 0.0 and np.isfinite(r) and np.isfinite(r * r) and r * r >= MIN_R2):
-        raise ValueError("radius = %r: it must be positive and its square a normal, finite float64" % (radius,))
+def _check_k(k):
     if not P.is_integer(k):
         raise TypeError("k must be an integer, got %r" % (k,))
     if not 1 <= int(k) <= MAX_K:
         raise ValueError("k = %d outside 1..%d" % (k, MAX_K))
-    if nr_types is not None and not P.is_integer(nr_types):
-        raise TypeError("nr_types must be an integer or None, got %r" % (nr_types,))
-    if types is None:
-        t = 1 if nr_types is None else int(nr_types)
-    else:
-        if not isinstance(types, np.ndarray) or types.dtype != np.int32:
-            raise TypeError("types must be an int32 numpy array [N] or None, got %s" % (getattr(types, "dtype", type(types).__name__),))
-        if types.shape != (n,):
-            raise ValueError("types %s is not parallel to xy %s" % (types.shape, xy.shape))
-        t = int(types.max()) + 1 if nr_types is None else int(nr_types)
-    if not 1 <= t <= MAX_T:
-        raise ValueError("%d types outside 1..%d" % (t, MAX_T))
-    if types is not None and (int(types.min()) < 0 or int(types.max()) >= t):
-        raise ValueError("types outside [0, %d)" % t)
-    return np.ascontiguousarray(xy), None if types is None else np.ascontiguousarray(types), r, int(k), t
+    return int(k)
+
+
+def _check(xy, types, radius, k, nr_types):
+    """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, r, k, T)."""
+    xy, r, k = P.check_xy(xy), P.check_radius(radius), _check_k(k)
+    types, t = P.check_types(types, xy.shape[0], nr_types)
+    return xy, types, r, k, t
 
 
 def _empty(n, k, t):
@@ -123,8 +97,7 @@ def query_host(xy, types, radius, k, nr_types=None):
 
 # ---- the device ----------------------------------------------------------------------------------
 class DeviceQuery(P.DeviceGrid):
-    """One device query (`points.DeviceGrid`): `run_grid` and `run_query` launch on the current stream without synchronising
-    (tools/neighbours_bench.py times them apart), `result` reads the three arrays back."""
+    """One device query (`points.DeviceGrid`: `run_grid`, `run_op`, `run`); `result` reads the three arrays back."""
 
     def __init__(self, xy, types, radius, k, nr_types=None, device="cuda"):
         xy, types, r, k, t = _check(xy, types, radius, k, nr_types)     # raises before anything is allocated or launched
@@ -135,9 +108,6 @@ class DeviceQuery(P.DeviceGrid):
         op.cout, op._rsv = t, k
         op.y.base, op.y2.base, op.res.base = self.count.data_ptr(), self.knn.data_ptr(), self.nearest.data_ptr()
 
-    def run_query(self):
-        self._run(1)
-
     def result(self):
         return {"count": self.count.cpu().numpy(), "knn": self.knn.cpu().numpy(), "nearest_of_type": self.nearest.cpu().numpy()}
 
@@ -145,17 +115,12 @@ class DeviceQuery(P.DeviceGrid):
 def query_device(xy, types, radius, k, nr_types=None, device="cuda"):
     """`query_host` on the GPU: the same three arrays.  The grid is chosen here on the host; the device builds it and answers the
     query (two ops on the current stream); the one synchronisation is the readback."""
-    q = DeviceQuery(xy, types, radius, k, nr_types, device)
-    q.run_grid()
-    q.run_query()
-    return q.result()
+    return DeviceQuery(xy, types, radius, k, nr_types, device).run().result()
 
 
 def query(xy, types, radius, k, nr_types=None, device=None):
     """`query_host` with device=None, `query_device` on `device` otherwise."""
-    if device is None:
-        return query_host(xy, types, radius, k, nr_types)
-    return query_device(xy, types, radius, k, nr_types, device)
+    return query_host(xy, types, radius, k, nr_types) if device is None else query_device(xy, types, radius, k, nr_types, device)
 
 
 # ---- what a user reads ---------------------------------------------------------------------------
@@ -187,8 +152,7 @@ def resolve(spec):
         return None
     if not isinstance(spec, dict) or set(spec) != {"radius", "k"}:
         raise ValueError('neighbours=%r: None or {"radius": r, "k": k}' % (spec,))
-    _check(np.zeros((1, 2)), None, spec["radius"], spec["k"], None)
-    return float(spec["radius"]), int(spec["k"])
+    return P.check_radius(spec["radius"]), _check_k(spec["k"])
 
 
 def annotate(info, radius, k, nr_types, device=None):

@@ -1,7 +1,10 @@
-"""The point-pattern layer under neighbours.py, clusters.py, density.py and ripley.py: what the four analyses of nucleus centroids share
-on the host, on the device and in the pipeline.  numpy only; imports without a GPU.
+"""The point-pattern layer under neighbours.py, clusters.py, density.py, ripley.py and regions.py: what the five analyses of nucleus
+centroids share on the host, on the device and in the pipeline.  numpy only; imports without a GPU.
 
 The arithmetic (`d2_of`, `r2_of`) and the grid (`grid`, `cells`) are defined in the docstring of neighbours.py, which re-exports them.
+
+The inputs (`check_xy`, `check_radius`, `check_types`).  What every analysis admits as points, as a radius and as types; each module's
+`_check` calls the ones it needs and adds its own.
 
 Candidates (`candidate_runs`, `pair_rounds`, `round_end`).  Points are put in cell order (a stable sort by cell: a SLOT is a position
 in that order).  Cells of one grid row are adjacent there, so the 3 x 3 cells around a slot are three contiguous runs of slots, one per
@@ -9,35 +12,38 @@ grid row.  The candidate pairs are tested in rounds of about `pairs` pairs, all 
 caller's own module-level `_PAIRS`, passed at call time.
 
 The device (`DeviceGrid`).  Every analysis is HVN_OP_NBR_GRID, which builds the cell-ordered copies and cell_start in one workspace,
-followed by a second op of its own kind that reads them.  `DeviceGrid` uploads the points, chooses the grid, owns that workspace and
-fills both ops' common fields; a subclass allocates its outputs and sets its own fields of the second op.
+followed by a second op of its own kind that reads them.  `DeviceGrid` uploads the points, chooses the grid, owns that workspace,
+fills both ops' common fields and launches them (`run_grid`, `run_op`, `run`); a subclass allocates its outputs, sets its own fields of
+the second op and reads them back (`result`).
 
-The pipeline (`resolve_specs`, `annotate`, `density_of`, `ripley_of`).  `post_proc.process`, `infer_tile.process_images`, `WsiInference` and the two
-managers of infer_manager.py take `neighbours`, `clusters` and, where a map can be returned or written, `density`:
-    neighbours  None or {"radius": r, "k": k}: every entry of the instance dict gains "neighbours" (`neighbours.annotate`)
-    clusters    None or {"radius": r, "min_pts": m} with an optional "types": [ints], which needs nr_types: every entry gains
-                "cluster" (`clusters.annotate`)
-    density     None or {"radius": r, "step": s}, `step` an integer >= 1: a `density.DensityMap` of the dict over the image
-                (`density.of_info`)
-Radii and steps are pixels of the processed image.  A bad spec is refused by `resolve_specs` before any work.  `neighbours` and
-`clusters` imply the instance dict.  The analyses run on the FINISHED dict -- on a slide once, on the merged dict in slide
-coordinates, so they cross tile seams -- in the order neighbours, clusters, density; on rank 0, where the dict lives, with no
-collective; on the GPU where the model is on one, on the host otherwise.
-A fourth argument, `ripley` (None or {"radii": [r, ..]} with an optional "window"), is taken by `WsiInference` and the two managers
-only: the `ripley.PairCounts` of the finished dict over the image (`ripley.of_info`, here `ripley_of`), made after the other three.  It
-is about the slide, not about a nucleus or a place, so it annotates nothing; `PointSpecs` stays the three above, and `ripley.resolve`
-resolves the fourth spec, which its users carry beside their PointSpecs.
-A fifth, `regions` (None or {"regions": RegionSet | list | GeoJSON path} with an optional "scale"; the managers take {"dir": d} and read
-`<d>/<name>.geojson`), is carried the same way: the `regions.RegionCounts` of the finished dict against annotated polygons
-(`regions.of_info`, here `regions_of`), made last; every entry gains "region" (`regions.annotate`).
+The pipeline (`ARGS`, `resolve_specs`, `annotate`, `summaries`, `save_results`, `output_dirs`).  Five arguments, None = off, resolved
+into one `PointSpecs` by each module's own `resolve`, in this order; a bad spec is refused there, before any work:
+    neighbours  {"radius": r, "k": k}: every entry of the instance dict gains "neighbours" (`neighbours.annotate`)
+    clusters    {"radius": r, "min_pts": m} with an optional "types": [ints], which needs nr_types: every entry gains "cluster"
+                (`clusters.annotate`)
+    density     {"radius": r, "step": s}, `step` an integer >= 1: a `density.DensityMap` of the dict over the image (`density.of_info`)
+    ripley      {"radii": [r, ..]} with an optional "window": the `ripley.PairCounts` of the dict over the image (`ripley.of_info`)
+    regions     {"regions": RegionSet | list | GeoJSON path} with an optional "scale" (the managers take {"dir": d} and read
+                `<d>/<name>.geojson`): the `regions.RegionCounts` of the dict against annotated polygons (`regions.of_info`); every
+                entry gains "region" (`regions.annotate`)
+Radii, steps and windows are pixels of the processed image.  The first two ANNOTATE (`annotate`) and imply the instance dict;
+`post_proc.process` and `infer_tile.process_images` take only them.  The last three are SUMMARIES, one row each of the table
+`_SUMMARIES`: the name (which is the field of PointSpecs and of PointResults, the output sub-directory and the module that saves it) and
+how to compute it.  `summaries` walks the table into a `PointResults`, `save_results` walks it to write `<sub>/<name>.npz`, `output_dirs`
+names the sub-directories that are on; `WsiInference` and the two managers of infer_manager.py use those three and nothing per
+analysis.  Everything runs on the FINISHED dict -- on a slide once, on the merged dict in slide coordinates, so it crosses tile seams --
+in the order above; on rank 0, where the dict lives, with no collective; on the GPU where the model is on one, on the host otherwise.
 """
 import collections
 import ctypes
+import importlib
 
 import numpy as np
 
 MARGIN = 1.0 + 2.0 ** -20
 MAX_AXIS, MAX_CELLS = 4096, 1 << 22
+MAX_N, MAX_T = 1 << 26, 16
+MIN_R2 = 2.0 ** -1000
 
 Grid = collections.namedtuple("Grid", "x0 y0 c ncx ncy")
 
@@ -50,6 +56,52 @@ def is_number(v):
 def is_integer(v):
     """An int, numpy's included, that is not a bool."""
     return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+
+
+def check_xy(xy):
+    """Points as neighbours.py's docstring names them, or TypeError / ValueError: -> xy, contiguous."""
+    if not isinstance(xy, np.ndarray) or xy.dtype != np.float64:
+        raise TypeError("xy must be a float64 numpy array [N, 2], got %s" % (getattr(xy, "dtype", type(xy).__name__),))
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+        raise ValueError("xy must be [N, 2] with N >= 1, got %s" % (xy.shape,))
+    if xy.shape[0] > MAX_N:
+        raise ValueError("%d points, more than 2^26" % xy.shape[0])
+    if not np.isfinite(xy).all():
+        raise ValueError("xy holds a coordinate that is not finite")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(xy.max(0) - xy.min(0)).all():
+            raise ValueError("the extent of xy is not a finite float64")
+    return np.ascontiguousarray(xy)
+
+
+def check_radius(radius):
+    """A radius as neighbours.py's docstring names it, or TypeError / ValueError: -> float."""
+    if not is_number(radius):
+        raise TypeError("radius must be a number, got %r" % (radius,))
+    r = float(radius)
+    if not (r > 0.0 and np.isfinite(r) and np.isfinite(r * r) and r * r >= MIN_R2):
+        raise ValueError("radius = %r: it must be positive and its square a normal, finite float64" % (radius,))
+    return r
+
+
+def check_types(types, n, nr_types):
+    """The types of n points (None: untyped) and `nr_types` (None: as many as `types` holds) as neighbours.py's docstring names them, or
+    TypeError / ValueError: -> (types | None, contiguous; T)."""
+    if nr_types is not None and not is_integer(nr_types):
+        raise TypeError("nr_types must be an integer or None, got %r" % (nr_types,))
+    if types is None:
+        t = 1 if nr_types is None else int(nr_types)
+    else:
+        if not isinstance(types, np.ndarray) or types.dtype != np.int32:
+            raise TypeError("types must be an int32 numpy array [N] or None, got %s" % (getattr(types, "dtype", type(types).__name__),))
+        if types.shape != (n,):
+            raise ValueError("types %s is not parallel to xy %s" % (types.shape, (n, 2)))
+        t = int(types.max()) + 1 if nr_types is None else int(nr_types)
+    if not 1 <= t <= MAX_T:
+        raise ValueError("%d types outside 1..%d" % (t, MAX_T))
+    if types is not None and (int(types.min()) < 0 or int(types.max()) >= t):
+        raise ValueError("types outside [0, %d)" % t)
+    return None if types is None else np.ascontiguousarray(types), t
 
 
 def d2_of(xi, yi, xj, yj):
@@ -158,8 +210,9 @@ def workspace_bytes(n, n_cells):
 class DeviceGrid:
     """The uploaded points, the grid workspace and the two ops of one device analysis, for CHECKED xy, types and r: `_ops[0]` is
     HVN_OP_NBR_GRID, `_ops[1]` the op of `kind` (a name of plan.py) with the fields filled that every such op shares.  `name` is the
-    caller's function, for the refusal of a device that is no GPU.  `run_grid` and `_run(1)` launch on the current stream without
-    synchronising."""
+    caller's function, for the refusal of a device that is no GPU.  `run_grid` and `run_op` launch on the current stream without
+    synchronising (the tools/*_bench.py time them apart); `run` is both, and `run().result()` a whole analysis, `result` being the
+    subclass's readback."""
 
     def __init__(self, xy, types, r, device, name, kind):
         import torch
@@ -204,10 +257,22 @@ class DeviceGrid:
     def run_grid(self):
         self._run(0)
 
+    def run_op(self):
+        self._run(1)
+
+    def run(self):
+        self.run_grid()
+        self.run_op()
+        return self
+
 
 # ---- the pipeline --------------------------------------------------------------------------------
-class PointSpecs(collections.namedtuple("PointSpecs", "neighbours clusters density")):
-    """The three resolved arguments of the module docstring, None where off: (r, k), (r, m, types tuple | None), (r, step)."""
+ARGS = ("neighbours", "clusters", "density", "ripley", "regions")
+
+
+class PointSpecs(collections.namedtuple("PointSpecs", ARGS)):
+    """The five resolved arguments of the module docstring, None where off: (r, k), (r, m, types tuple | None), (r, step),
+    (radii tuple, window tuple | None), a `regions.RegionSet`."""
     __slots__ = ()
 
     @property
@@ -216,14 +281,19 @@ class PointSpecs(collections.namedtuple("PointSpecs", "neighbours clusters densi
         return self.neighbours is not None or self.clusters is not None
 
 
-def resolve_specs(neighbours=None, clusters=None, density=None, typed=True):
-    """The three arguments as a caller gave them -> PointSpecs, or the ValueError / TypeError of the module's own `resolve`.
+PointResults = collections.namedtuple("PointResults", ARGS[2:])        # what `summaries` returns: None where off
+
+
+def resolve_specs(neighbours=None, clusters=None, density=None, ripley=None, regions=None, typed=True):
+    """The five arguments as a caller gave them -> PointSpecs, or the ValueError / TypeError of the module's own `resolve`.
     typed=False (a model without a type branch) refuses "types" in `clusters`."""
     from . import clusters as CL
     from . import density as DN
     from . import neighbours as NB
+    from . import regions as RG
+    from . import ripley as RP
 
-    return PointSpecs(NB.resolve(neighbours), CL.resolve(clusters, typed=typed), DN.resolve(density))
+    return PointSpecs(NB.resolve(neighbours), CL.resolve(clusters, typed=typed), DN.resolve(density), RP.resolve(ripley), RG.resolve(regions))
 
 
 def _device(device):
@@ -243,27 +313,45 @@ def annotate(info, specs, nr_types, device):
     return info
 
 
-def density_of(info, size_hw, specs, nr_types, device):
-    """The `density.DensityMap` of a finished instance dict over an image of size_hw = (h, w) processed pixels for `specs.density`
-    (not None); `device` as in `annotate`."""
+def _density(info, size_hw, spec, nr_types, device):
     from . import density as DN
 
-    return DN.of_info(info, size_hw, specs.density[0], specs.density[1], nr_types, device=_device(device))
+    return DN.of_info(info, size_hw, spec[0], spec[1], nr_types, device=device)
 
 
-def ripley_of(info, size_hw, spec, nr_types, device):
-    """The `ripley.PairCounts` of a finished instance dict over an image of size_hw = (h, w) processed pixels for a resolved `ripley`
-    spec (`ripley.resolve`, not None); `device` as in `annotate`."""
+def _ripley(info, size_hw, spec, nr_types, device):
     from . import ripley as RP
 
-    return RP.of_info(info, size_hw, spec[0], nr_types, device=_device(device), window=spec[1])
+    return RP.of_info(info, size_hw, spec[0], nr_types, device=device, window=spec[1])
 
 
-def regions_of(info, rs, nr_types, device):
-    """The `regions.RegionCounts` of a finished instance dict for a resolved `regions` spec (`regions.resolve`, not None), with every
-    entry annotated ("region"); `device` as in `annotate`."""
+def _regions(info, _size_hw, rs, nr_types, device):
     from . import regions as RG
 
-    rc = RG.of_info(info, rs, nr_types, device=_device(device))
+    rc = RG.of_info(info, rs, nr_types, device=device)
     RG.annotate(info, rc)
     return rc
+
+
+# The summaries in the order they are computed and written.  The name is the field of PointSpecs and of PointResults, the output
+# sub-directory, and the module whose `save(path, result)` writes the result.
+_SUMMARIES = (("density", _density), ("ripley", _ripley), ("regions", _regions))
+
+
+def summaries(info, size_hw, specs, nr_types, device):
+    """PointResults(density, ripley, regions) of a finished instance dict over an image of size_hw = (h, w) processed pixels, as
+    `specs` asks and None where it does not; with regions every entry gains "region".  `device` as in `annotate`."""
+    return PointResults(*(None if getattr(specs, name) is None else of(info, size_hw, getattr(specs, name), nr_types, _device(device))
+                          for name, of in _SUMMARIES))
+
+
+def save_results(output_dir, name, results):
+    """Writes `<output_dir>/<sub>/<name>.npz` for every result of a PointResults that is not None, with its module's `save`."""
+    for sub, _ in _SUMMARIES:
+        if getattr(results, sub) is not None:
+            importlib.import_module("." + sub, __package__).save("%s/%s/%s.npz" % (output_dir, sub, name), getattr(results, sub))
+
+
+def output_dirs(specs):
+    """The sub-directories `save_results` writes into for `specs`: the summaries that are on."""
+    return tuple(sub for sub, _ in _SUMMARIES if getattr(specs, sub) is not None)

@@ -69,10 +69,9 @@ import os
 
 import numpy as np
 
-from . import neighbours as NB
 from . import points as P
 
-MAX_G, MAX_E, MAX_T = 4096, 1 << 22, NB.MAX_T
+MAX_G, MAX_E, MAX_T = 4096, 1 << 22, P.MAX_T
 ROW_POINTS = 256                # points per grid row that `cell_side` aims at: the kernel's workgroup
 _PAIRS = 1 << 22                # point-edge pairs per round of `regions_host`
 
@@ -236,16 +235,26 @@ def as_regions(rs, scale=1.0):
     return RegionSet.from_polygons(rs, None, scale)
 
 
-def _check(xy, types, rs, nr_types, cell=None):
-    """The inputs as the definition names them, or TypeError / ValueError, before any work: -> (xy, types | None, rs, T, cell | None)."""
+def _check_set(rs):
     if not isinstance(rs, RegionSet):
         raise TypeError("rs must be a RegionSet (RegionSet.from_polygons / from_geojson), got %r" % (type(rs).__name__,))
-    if cell is not None:
-        NB._check(np.zeros((1, 2)), None, cell, 1, None)            # a cell side is admissible where a radius is
-        cell = float(cell)
-    xy, types, _, _, t = NB._check(xy, types, 1.0, 1, nr_types)
+
+
+def _check_counts(rs, types, n, nr_types):
+    """The types of n points and the size of a RegionSet, or TypeError / ValueError: -> (types | None, T)."""
+    types, t = P.check_types(types, n, nr_types)
     if len(rs) > MAX_G or rs.edges.shape[0] > MAX_E:
         raise ValueError("%d regions of %d edges, more than %d or 2^22" % (len(rs), rs.edges.shape[0], MAX_G))
+    return types, t
+
+
+def _check(xy, types, rs, nr_types, cell=None):
+    """The inputs as the definition names them, or TypeError / ValueError, before any work: -> (xy, types | None, rs, T, cell | None)."""
+    _check_set(rs)
+    if cell is not None:
+        cell = P.check_radius(cell)                                 # a cell side is admissible where a radius is
+    xy = P.check_xy(xy)
+    types, t = _check_counts(rs, types, xy.shape[0], nr_types)
     return xy, types, rs, t, cell
 
 
@@ -269,7 +278,7 @@ def cell_side(xy, rs, cell=None):
     ey = float(xy[:, 1].max()) - float(xy[:, 1].min())
     ex = float(xy[:, 0].max()) - float(xy[:, 0].min())
     r = cell if cell is not None else ey / max(1.0, min(float(P.MAX_AXIS - 1), n / float(ROW_POINTS)))
-    if not (r * r >= NB.MIN_R2 and np.isfinite(r * r)):               # all points on one scanline, or an absurd extent: one row
+    if not (r * r >= P.MIN_R2 and np.isfinite(r * r)):               # all points on one scanline, or an absurd extent: one row
         r = max(1.0, ex, ey)
     e = rs.edges[listed(xy, rs)]
     while True:
@@ -349,9 +358,8 @@ class NothingToTest(ValueError):
 
 
 class DeviceRegions(P.DeviceGrid):
-    """One device membership count (`points.DeviceGrid` on the grid of `cell_side`): `run_grid` and `run_regions` launch on the current
-    stream without synchronising (tools/regions_bench.py times them apart), `result` reads the one output buffer back.  The op writes
-    every element of it: nothing is cleared here.  Regions without a single listed edge are refused with `NothingToTest`
+    """One device membership count (`points.DeviceGrid`: `run_grid`, `run_op`, `run`; on the grid of `cell_side`); `result` reads the one
+    output buffer back.  The op writes every element of it: nothing is cleared here.  Regions without a single listed edge are refused with `NothingToTest`
     (`regions_device` launches nothing for them)."""
 
     def __init__(self, xy, types, rs, nr_types=None, device="cuda", cell=None):
@@ -378,9 +386,6 @@ class DeviceRegions(P.DeviceGrid):
         op.y2.base, op.y2.sn = self.rows.data_ptr(), self.entries
         op.y.base = self.out.data_ptr()
 
-    def run_regions(self):
-        self._run(1)
-
     def result(self):
         out = self.out.cpu().numpy()
         n = self.n
@@ -391,20 +396,15 @@ def regions_device(xy, types, rs, nr_types=None, device="cuda", cell=None):
     """`regions_host` on the GPU: the same integers.  The grid and the row lists are made here on the host; the device builds the grid
     and tests (two ops on the current stream); the one synchronisation is the readback.  Regions without a listed edge launch nothing."""
     try:
-        q = DeviceRegions(xy, types, rs, nr_types, device, cell)
+        return DeviceRegions(xy, types, rs, nr_types, device, cell).run().result()
     except NothingToTest:
         xy, types, rs, t, _ = _check(xy, types, rs, nr_types, cell)
         return _zero(xy.shape[0], len(rs), t, rs)
-    q.run_grid()
-    q.run_regions()
-    return q.result()
 
 
 def regions(xy, types, rs, nr_types=None, device=None, cell=None):
     """`regions_host` with device=None, `regions_device` on `device` otherwise."""
-    if device is None:
-        return regions_host(xy, types, rs, nr_types, cell)
-    return regions_device(xy, types, rs, nr_types, device, cell)
+    return regions_host(xy, types, rs, nr_types, cell) if device is None else regions_device(xy, types, rs, nr_types, device, cell)
 
 
 # ---- what a user reads ---------------------------------------------------------------------------
@@ -422,7 +422,8 @@ def of_info(info, rs, nr_types, device=None):
     """The RegionCounts of an instance dict (`post_proc.process` / `process_images` / `WsiInference.run`): the centroids are the points,
     entry["type"] the types, as in `neighbours.annotate` (nr_types=None: untyped, T = 1); first / hits follow dict order.  An empty dict
     gives zero counts.  device=None: `regions_host`."""
-    _, _, rs, t, _ = _check(np.zeros((1, 2)), None, rs, nr_types)
+    _check_set(rs)
+    _, t = _check_counts(rs, None, 0, nr_types)
     if not info:
         return _zero(0, len(rs), t, rs)
     _, xy, types = P.from_info(info, nr_types)

@@ -49,10 +49,9 @@ import math
 
 import numpy as np
 
-from . import neighbours as NB
 from . import points as P
 
-MAX_R, MAX_BINS, MAX_T = 32, 4096, NB.MAX_T
+MAX_R, MAX_BINS, MAX_T = 32, 4096, P.MAX_T
 _PAIRS = 1 << 22                # candidate pairs per round of `pairs_host`
 
 PairCounts = collections.namedtuple("PairCounts", "pairs pairs_in n n_in radii window")
@@ -65,9 +64,7 @@ def _check_radii(radii):
     radii = list(radii)
     if not 1 <= len(radii) <= MAX_R:
         raise ValueError("%d radii outside 1..%d" % (len(radii), MAX_R))
-    for r in radii:
-        NB._check(np.zeros((1, 2)), None, r, 1, None)
-    out = np.array([float(r) for r in radii], np.float64)
+    out = np.array([P.check_radius(r) for r in radii], np.float64)
     if not (np.diff(out) > 0.0).all():
         raise ValueError("radii %r are not strictly ascending" % (radii,))
     return out
@@ -89,12 +86,17 @@ def _check_window(window):
 
 def _check(xy, types, radii, window, nr_types):
     """The inputs as the definition names them, or TypeError / ValueError: -> (xy, types | None, radii float64 [R], window, T)."""
-    rr = _check_radii(radii)
-    xy, types, _, _, t = NB._check(xy, types, float(rr[-1]), 1, nr_types)
+    rr, xy = _check_radii(radii), P.check_xy(xy)
+    types, t = P.check_types(types, xy.shape[0], nr_types)
+    return xy, types, rr, _check_bins(window, t, rr), t
+
+
+def _check_bins(window, t, rr):
+    """A checked window, for t types and the checked radii rr whose bins are not too many."""
     win = _check_window(window)
     if t * t * rr.shape[0] > MAX_BINS:
         raise ValueError("%d x %d types and %d radii, more than %d bins" % (t, t, rr.shape[0], MAX_BINS))
-    return xy, types, rr, win, t
+    return win
 
 
 def border(xy, window):
@@ -149,9 +151,8 @@ def pairs_host(xy, types, radii, window, nr_types=None):
 
 # ---- the device ----------------------------------------------------------------------------------
 class DeviceRipley(P.DeviceGrid):
-    """One device pair count (`points.DeviceGrid` on the grid of the largest radius): `run_grid` and `run_pairs` launch on the
-    current stream without synchronising (tools/ripley_bench.py times them apart), `result` reads the accumulator back and finishes
-    it on the host.  The op writes every element of `acc`: nothing is cleared here."""
+    """One device pair count (`points.DeviceGrid`: `run_grid`, `run_op`, `run`; on the grid of the largest radius); `result` reads the
+    accumulator back and finishes it on the host.  The op writes every element of `acc`: nothing is cleared here."""
 
     def __init__(self, xy, types, radii, window, nr_types=None, device="cuda"):
         import torch
@@ -165,9 +166,6 @@ class DeviceRipley(P.DeviceGrid):
         op.cout, op._rsv, op.bias = t, rr.shape[0], self.rt.data_ptr()
         op.y.base = self.acc.data_ptr()
 
-    def run_pairs(self):
-        self._run(1)
-
     def result(self):
         return _finish(self.acc.cpu().numpy(), self._xy, self._types, self.radii, self.window, self.t)
 
@@ -175,17 +173,12 @@ class DeviceRipley(P.DeviceGrid):
 def pairs_device(xy, types, radii, window, nr_types=None, device="cuda"):
     """`pairs_host` on the GPU: the same integers.  The grid is chosen here on the host; the device builds it and counts (two ops on
     the current stream); the one synchronisation is the readback of the accumulator."""
-    q = DeviceRipley(xy, types, radii, window, nr_types, device)
-    q.run_grid()
-    q.run_pairs()
-    return q.result()
+    return DeviceRipley(xy, types, radii, window, nr_types, device).run().result()
 
 
 def pairs(xy, types, radii, window, nr_types=None, device=None):
     """`pairs_host` with device=None, `pairs_device` on `device` otherwise."""
-    if device is None:
-        return pairs_host(xy, types, radii, window, nr_types)
-    return pairs_device(xy, types, radii, window, nr_types, device)
+    return pairs_host(xy, types, radii, window, nr_types) if device is None else pairs_device(xy, types, radii, window, nr_types, device)
 
 
 # ---- what a user reads ---------------------------------------------------------------------------
@@ -215,7 +208,8 @@ def of_info(info, size_hw, radii, nr_types, device=None, window=None):
     (h, w) processed pixels, with `window_of(size_hw)` unless a window is given.  The centroids are the points, entry["type"] the
     types, as in `neighbours.annotate` (nr_types=None: untyped, T = 1).  An empty dict gives zeros.  device=None: `pairs_host`."""
     win = window_of(size_hw) if window is None else window
-    _, _, rr, win, t = _check(np.zeros((1, 2)), None, radii, win, nr_types)
+    rr, (_, t) = _check_radii(radii), P.check_types(None, 0, nr_types)
+    win = _check_bins(win, t, rr)
     if not info:
         z = np.zeros((t, t, rr.shape[0]), np.int64)
         return PairCounts(z, z.copy(), np.zeros(t, np.int64), np.zeros((t, rr.shape[0]), np.int64), rr, win)

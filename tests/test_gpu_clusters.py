@@ -65,9 +65,9 @@ def test_the_op_initialises_the_second_workspace(name):
     q.ws2.fill_(0xFF)
     q.label.fill_(-7)
     q.degree.fill_(-7)
-    q.run_cluster()
+    q.run_op()
     R.assert_same(q.result(), want, name)
-    q.run_cluster()                                  # and again on its own leftovers
+    q.run_op()                                  # and again on its own leftovers
     R.assert_same(q.result(), want, name)
 
 
@@ -83,12 +83,12 @@ def test_a_type_outside_the_mask_range_is_unselected():
     q = CL.DeviceClusters(xy, types, r, m, of)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_cluster()
+    q.run_op()
     R.assert_same(q.result(), R.cluster(xy, bad, r, m, of), "masked")
     q = CL.DeviceClusters(xy, types, r, m, None)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_cluster()
+    q.run_op()
     R.assert_same(q.result(), R.cluster(xy, None, r, m, None), "every point")
 
 

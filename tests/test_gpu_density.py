@@ -56,9 +56,9 @@ def test_the_op_writes_every_element(name):
     q = _dn().DeviceDensity(*args)
     q.run_grid()
     q.count.fill_(-7)
-    q.run_density()
+    q.run_op()
     R.assert_same(q.result(), want, name)
-    q.run_density()
+    q.run_op()
     R.assert_same(q.result(), want, name)
 
 
@@ -78,7 +78,7 @@ def test_a_type_outside_the_range_is_counted_in_no_channel(name):
     q = _dn().DeviceDensity(xy, types, r, raster, t)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_density()
+    q.run_op()
     got = q.result()
     expect = R.density(xy, bad, r, raster, t)
     R.assert_same(got, expect, name)
@@ -176,7 +176,7 @@ def test_wsi_density_crosses_tile_seams(net):
     kw = dict(nr_types=5, batch_size=8, tile_shape=512, ambiguous_size=64)
     plain = infer_wsi.WsiInference(net, **kw)
     inst0, info0 = plain.stitch_instances(maps)
-    assert plain.density is None and plain.density_spec is None
+    assert plain.density is None and plain.points.density is None
     wsi = infer_wsi.WsiInference(net, density=SLIDE_SPEC, **kw)
     assert wsi.density is None                                   # nothing before the first slide
     inst1, info1 = wsi.stitch_instances(maps)

@@ -62,7 +62,7 @@ def test_a_type_outside_the_columns_counts_nowhere_and_stays_in_knn():
     q = NB.DeviceQuery(xy, types, r, k, t)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_query()
+    q.run_op()
     got = q.result()
     outside = (bad < 0) | (bad >= t)
     wide = R.query(xy, np.where(outside, t, bad), r, k, t + 1)      # the oracle with one more column for them
@@ -85,7 +85,7 @@ def test_coordinates_that_are_not_finite_stay_inside_the_grid():
     q = NB.DeviceQuery(xy, types, r, k, t)
     q.xy.copy_(torch.from_numpy(poisoned))
     q.run_grid()
-    q.run_query()
+    q.run_op()
     got = q.result()
     keep = np.setdiff1d(np.arange(n), rows)
     want = R.query(xy[keep], None, r, k, t)

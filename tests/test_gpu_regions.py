@@ -77,9 +77,9 @@ def test_the_op_writes_every_element(name):
     q = _rg().DeviceRegions(*args[:4], cell=args[4])
     q.run_grid()
     q.out.fill_(-7)
-    q.run_regions()
+    q.run_op()
     R.assert_same(q.result(), want, name)
-    q.run_regions()
+    q.run_op()
     R.assert_same(q.result(), want, name)
 
 
@@ -98,7 +98,7 @@ def test_a_type_outside_the_range_is_counted_nowhere(name):
     q = _rg().DeviceRegions(xy, types, rs, t, cell=cell)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_regions()
+    q.run_op()
     got = q.result()
     expect = R.regions(xy, bad, rs.polygons, t)
     inside = (bad >= 0) & (bad < t)
@@ -214,7 +214,7 @@ def test_wsi_regions_cross_tile_seams(net):
     kw = dict(nr_types=5, batch_size=8, tile_shape=512, ambiguous_size=64)
     plain = infer_wsi.WsiInference(net, **kw)
     inst0, info0 = plain.stitch_instances(maps)
-    assert plain.regions is None and plain.regions_spec is None and not any("region" in e for e in info0.values())
+    assert plain.regions is None and plain.points.regions is None and not any("region" in e for e in info0.values())
     wsi = infer_wsi.WsiInference(net, regions={"regions": geo}, **kw)
     assert wsi.regions is None                                   # nothing before the first slide
     inst1, info1 = wsi.stitch_instances(maps)

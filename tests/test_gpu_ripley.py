@@ -57,9 +57,9 @@ def test_the_op_writes_every_element(name):
     q = _rp().DeviceRipley(*args)
     q.run_grid()
     q.acc.fill_(-7)
-    q.run_pairs()
+    q.run_op()
     R.assert_same(q.result(), want, name)
-    q.run_pairs()
+    q.run_op()
     R.assert_same(q.result(), want, name)
 
 
@@ -78,7 +78,7 @@ def test_a_type_outside_the_range_lands_in_no_bin(name):
     q = _rp().DeviceRipley(xy, types, radii, window, t)
     q.types.copy_(torch.from_numpy(bad))
     q.run_grid()
-    q.run_pairs()
+    q.run_op()
     got = q.result()
     expect = R.pairs(xy, bad, radii, window, t)
     inside = (bad >= 0) & (bad < t)
@@ -191,7 +191,7 @@ def test_wsi_ripley_crosses_tile_seams(net):
     kw = dict(nr_types=5, batch_size=8, tile_shape=512, ambiguous_size=64)
     plain = infer_wsi.WsiInference(net, **kw)
     inst0, info0 = plain.stitch_instances(maps)
-    assert plain.ripley is None and plain.ripley_spec is None
+    assert plain.ripley is None and plain.points.ripley is None
     wsi = infer_wsi.WsiInference(net, ripley=SLIDE_SPEC, **kw)
     assert wsi.ripley is None                                    # nothing before the first slide
     inst1, info1 = wsi.stitch_instances(maps)

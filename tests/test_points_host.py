@@ -1,6 +1,9 @@
-"""CPU: hover_net_amd/points.py, the layer under neighbours.py, clusters.py and density.py -- the points of an instance dict, the
-candidate runs and rounds against the all-pairs set, the round boundary, and the pipeline's one resolver."""
+"""CPU: hover_net_amd/points.py, the layer under neighbours.py, clusters.py, density.py, ripley.py and regions.py -- the points of an
+instance dict, the shared validators, the candidate runs and rounds against the all-pairs set, the round boundary, and the pipeline's one
+resolver and one table of summaries, alone and through the two managers."""
 import copy
+import json
+import os
 
 import numpy as np
 import pytest
@@ -12,6 +15,8 @@ from hover_net_amd import clusters as CL
 from hover_net_amd import density as DN
 from hover_net_amd import neighbours as NB
 from hover_net_amd import points as P
+from hover_net_amd import regions as RG
+from hover_net_amd import ripley as RP
 
 
 # -- from_info -------------------------------------------------------------------------------------------------
@@ -119,16 +124,25 @@ def test_round_end():
 
 # -- resolve_specs ---------------------------------------------------------------------------------------------
 def test_resolve_specs():
-    s = P.resolve_specs(None, None, None, typed=False)
-    assert s == (None, None, None) and not s.any_annotation
+    s = P.resolve_specs(None, None, None, None, None, typed=False)
+    assert s == (None, None, None, None, None) and s._fields == P.ARGS and not s.any_annotation
     s = P.resolve_specs({"radius": 50, "k": 5}, {"radius": 30.0, "min_pts": 4, "types": [2, 0]}, {"radius": 80, "step": 16}, typed=True)
     assert s.neighbours == (50.0, 5) and s.clusters == (30.0, 4, (0, 2)) and s.density == (80.0, 16) and s.any_annotation
     assert not P.resolve_specs(density={"radius": 80, "step": 16}).any_annotation
     assert P.resolve_specs(clusters={"radius": 3, "min_pts": 2}, typed=False).any_annotation
-    for kw, mod in (("neighbours", NB), ("clusters", CL), ("density", DN)):
-        good = {"neighbours": {"radius": 5, "k": 2}, "clusters": {"radius": 5, "min_pts": 2}, "density": {"radius": 5, "step": 2}}[kw]
-        second = [k for k in good if k != "radius"][0]
-        for bad in ({"radius": 5}, (5, 2), dict(good, radius=0), dict(good, radius="5"), dict(good, **{second: 2.5}), dict(good, **{second: 0})):
+    rect = [[[(0, 0), (8, 0), (8, 8), (0, 8)]]]
+    s = P.resolve_specs(ripley={"radii": [4, 6.0], "window": (0, 0, 9, 9)}, regions={"regions": [rect]})
+    assert s.ripley == ((4.0, 6.0), (0.0, 0.0, 9.0, 9.0)) and isinstance(s.regions, RG.RegionSet) and len(s.regions) == 1 and not s.any_annotation
+    assert s[:3] == (None, None, None)
+    for kw, mod in (("neighbours", NB), ("clusters", CL), ("density", DN), ("ripley", RP), ("regions", RG)):
+        good = {"neighbours": {"radius": 5, "k": 2}, "clusters": {"radius": 5, "min_pts": 2}, "density": {"radius": 5, "step": 2}}.get(kw)
+        if good is None:
+            bads = {"ripley": ({"radius": 5}, (5, 2), {"radii": [0]}, {"radii": ["5"]}, {"radii": [5, 5]}, {"radii": [5], "window": (0, 0, 0, 9)}),
+                    "regions": ({"region": [rect]}, [rect], {"regions": 5}, {"regions": [rect], "scale": 0}, {"regions": [rect], "scale": "2"}, {"regions": []})}[kw]
+        else:
+            second = [k for k in good if k != "radius"][0]
+            bads = ({"radius": 5}, (5, 2), dict(good, radius=0), dict(good, radius="5"), dict(good, **{second: 2.5}), dict(good, **{second: 0}))
+        for bad in bads:
             with pytest.raises((ValueError, TypeError)) as own:
                 mod.resolve(bad)
             with pytest.raises(own.type) as ours:
@@ -136,3 +150,227 @@ def test_resolve_specs():
             assert str(ours.value) == str(own.value)
     with pytest.raises(ValueError, match="needs a model with a type branch"):
         P.resolve_specs(clusters={"radius": 5, "min_pts": 2, "types": [1]}, typed=False)
+
+
+# -- the five at once ------------------------------------------------------------------------------------------
+SIZE = (64, 96)
+SPECS = {"neighbours": {"radius": 14.0, "k": 3}, "clusters": {"radius": 9.0, "min_pts": 3, "types": [0, 2]}, "density": {"radius": 12.0, "step": 8},
+         "ripley": {"radii": [5.0, 11.0, 20.0]}}
+GEOJSON = {"type": "FeatureCollection", "features": [          # two rectangles that overlap in [30, 50] x [20, 40]
+    {"type": "Feature", "properties": {"name": "left"}, "geometry": {"type": "Polygon", "coordinates": [[[4, 6], [50, 6], [50, 40], [4, 40], [4, 6]]]}},
+    {"type": "Feature", "properties": {"name": "right"}, "geometry": {"type": "Polygon", "coordinates": [[[30, 20], [90, 20], [90, 60], [30, 60]]]}}]}
+
+
+def _typed_stub():
+    """40 nuclei of 3 types on a 64 x 96 image, as `post_proc.process` shapes its entries; labels not contiguous."""
+    rng = np.random.default_rng(11)
+    info = {}
+    for i in range(40):
+        x, y = int(rng.integers(3, SIZE[1] - 4)), int(rng.integers(3, SIZE[0] - 4))
+        box = np.array([[x - 2, y - 2], [x + 2, y - 2], [x + 2, y + 2], [x - 2, y + 2]], np.int32)
+        info[3 * i + 1] = {"bbox": np.array([[y - 2, x - 2], [y + 3, x + 3]]), "centroid": np.array([x + 0.25 * (i % 3), y + 0.5]), "contour": box,
+                           "type_prob": 0.5 + 0.01 * i, "type": int(rng.integers(0, 3))}
+    return info
+
+
+def _all_specs(regions={"regions": GEOJSON}):
+    return P.resolve_specs(**SPECS, regions=regions, typed=True)
+
+
+def _same(a, b, where=""):
+    """== for the nested dicts, tuples, lists and arrays of entries and results."""
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), where
+        for k in a:
+            _same(a[k], b[k], "%s[%r]" % (where, k))
+    elif isinstance(a, (tuple, list)) and not isinstance(a, str):
+        assert type(a) is type(b) and len(a) == len(b), where
+        for i, (u, v) in enumerate(zip(a, b)):
+            _same(u, v, "%s[%d]" % (where, i))
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), where
+    else:
+        assert type(a) is type(b) and a == b, where
+
+
+def _each_alone(info, t=3):
+    """What every module gives for the stub when it is called alone, each on a fresh copy: the three annotations by label, the three
+    summaries."""
+    rs = RG.RegionSet.from_geojson(GEOJSON)
+    nb = NB.annotate(copy.deepcopy(info), 14.0, 3, t)
+    cl = CL.annotate(copy.deepcopy(info), 9.0, 3, t, (0, 2))
+    rg = copy.deepcopy(info)
+    rc = RG.of_info(rg, rs, t)
+    RG.annotate(rg, rc)
+    notes = {lab: {"neighbours": nb[lab]["neighbours"], "cluster": cl[lab]["cluster"], "region": rg[lab]["region"]} for lab in info}
+    return notes, P.PointResults(DN.of_info(copy.deepcopy(info), SIZE, 12.0, 8, t), RP.of_info(copy.deepcopy(info), SIZE, [5.0, 11.0, 20.0], t), rc)
+
+
+def _expected_entries(info):
+    notes, _ = _each_alone(info)
+    return {lab: dict(copy.deepcopy(e), **notes[lab]) for lab, e in info.items()}
+
+
+def test_all_five_at_once_equal_each_alone():
+    info = _typed_stub()
+    assert len(info) == 40 and sorted({e["type"] for e in info.values()}) == [0, 1, 2]
+    notes, want = _each_alone(info)
+    specs = _all_specs()
+    got = copy.deepcopy(info)
+    assert P.annotate(got, specs, 3, None) is got
+    res = P.summaries(got, SIZE, specs, 3, None)
+    assert type(res) is P.PointResults and res._fields == ("density", "ripley", "regions")
+    for name in res._fields:
+        _same(tuple(getattr(res, name)), tuple(getattr(want, name)), name)
+    for lab, e in got.items():
+        assert list(e) == list(info[lab]) + ["neighbours", "cluster", "region"]
+        _same({k: e[k] for k in info[lab]}, info[lab], "entry %d" % lab)
+        _same({k: e[k] for k in notes[lab]}, notes[lab], "entry %d" % lab)
+    # the cases are not empty ones: neighbours, clusters, both regions and their overlap, counts at every radius
+    assert any(e["neighbours"]["knn"] for e in got.values()) and any(e["cluster"]["id"] is not None for e in got.values())
+    assert set(res.regions.first.tolist()) == {-1, 0, 1} and res.regions.hits.max() == 2
+    assert res.density.count.shape == (3, 8, 12) and res.density.count.sum() > 0 and (res.ripley.pairs.sum((0, 1)) > 0).all()
+    off = P.resolve_specs()
+    plain = copy.deepcopy(info)
+    assert P.annotate(plain, off, 3, None) is plain and P.summaries(plain, SIZE, off, 3, None) == P.PointResults(None, None, None)
+    _same(plain, info, "all off")
+    assert P.output_dirs(off) == () and P.output_dirs(specs) == ("density", "ripley", "regions") and P.output_dirs(specs._replace(ripley=None)) == ("density", "regions")
+
+
+def _load_npz(path):
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _tree(root):
+    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs + [""])
+
+
+def test_managers_write_all_five(tmp_path):
+    """Both managers with the GPU call replaced by a stub that annotates as `process_images` / `WsiInference` do."""
+    for which in ("tile", "wsi"):
+        (tmp_path / which).mkdir()
+        _managers_write_all_five(which, tmp_path / which)
+
+
+def _managers_write_all_five(which, tmp_path):
+    from hover_net_amd import infer_manager as im
+    from hover_net_amd import io_utils
+
+    inp, ann = tmp_path / "in", tmp_path / "ann"
+    inp.mkdir()
+    ann.mkdir()
+    np.save(inp / "a.npy", np.random.default_rng(1).integers(30, 120, SIZE + (3,), dtype=np.uint8))
+    (ann / "a.geojson").write_text(json.dumps(GEOJSON))
+    on = [False]
+
+    def stub():
+        return P.annotate(_typed_stub(), _all_specs(None) if on[0] else P.resolve_specs(), 3, None)
+
+    method = {"model_args": {"nr_types": 3, "mode": "fast"}, "model_path": None}
+    if which == "tile":
+        mgr = im.InferManager(method, process_fn=lambda images: [(np.zeros(i.shape[:2], np.int32), stub()) for i in images])
+        run, done, json_at = mgr.process_file_list, ["a"], "json/a.json"
+    else:
+        mgr = im.WsiManager(method, wsi_fn=lambda slide, mask: (None, stub()))
+        run, done, json_at = mgr.process_wsi_list, {"a": "done"}, "a.json"
+    base = {"input_dir": str(inp)}
+    five = dict(SPECS, regions={"dir": str(ann)})
+    assert run(dict(base, output_dir=str(tmp_path / "absent"))) == done
+    assert run(dict(base, output_dir=str(tmp_path / "none"), **{k: None for k in P.ARGS})) == done
+    on[0] = True
+    assert run(dict(base, output_dir=str(tmp_path / "five"), **five)) == done
+    # all five off: the tree and the json are those of a run that never heard of them
+    assert _tree(tmp_path / "none") == _tree(tmp_path / "absent") and (tmp_path / "none" / json_at).read_bytes() == (tmp_path / "absent" / json_at).read_bytes()
+    # all five on: exactly the three sub-directories beside what was there, each .npz the module's own of_info, the json the annotated stub
+    top = lambda d: set(os.listdir(tmp_path / d))                    # noqa: E731
+    assert top("five") - top("absent") == {"density", "ripley", "regions"} and top("absent") <= top("five")
+    _, want = _each_alone(_typed_stub())
+    assert [os.listdir(tmp_path / "five" / sub) for sub in ("density", "ripley", "regions")] == [["a.npz"]] * 3
+    for sub, save in (("density", DN.save), ("ripley", RP.save), ("regions", RG.save)):
+        save(tmp_path / ("want_%s.npz" % sub), getattr(want, sub))
+        _same(_load_npz(tmp_path / "five" / sub / "a.npz"), _load_npz(tmp_path / ("want_%s.npz" % sub)), sub)
+    io_utils.save_json(str(tmp_path / "want.json"), _expected_entries(_typed_stub()), **({"mag": 40} if which == "wsi" else {"mag": None}))
+    assert (tmp_path / "five" / json_at).read_bytes() == (tmp_path / "want.json").read_bytes()
+    nuc = json.loads((tmp_path / "five" / json_at).read_text())["nuc"]
+    assert all(list(e)[-3:] == ["neighbours", "cluster", "region"] for e in nuc.values()) and len(nuc) == 40
+    # a bad spec for any one of the five: refused before the output directory exists
+    bad = {"neighbours": {"radius": 0, "k": 3}, "clusters": {"radius": 9.0, "min_pts": 2.5}, "density": {"radius": 12.0, "step": 0},
+           "ripley": {"radii": [5.0, 5.0]}, "regions": {"dir": str(ann), "scale": 0}}
+    assert sorted(bad) == sorted(P.ARGS)
+    for k in P.ARGS:
+        with pytest.raises((ValueError, TypeError)):
+            run(dict(base, output_dir=str(tmp_path / "bad"), **dict(five, **{k: bad[k]})))
+        assert not (tmp_path / "bad").exists()
+
+
+# -- the validators --------------------------------------------------------------------------------------------
+def _new_check(xy, types, radius, k, nr_types):
+    """The validators of points.py in the order of `neighbours._check`: xy, radius, k, types."""
+    xy, r, k = P.check_xy(xy), P.check_radius(radius), NB._check_k(k)
+    types, t = P.check_types(types, xy.shape[0], nr_types)
+    return xy, types, r, k, t
+
+
+def test_validators_report_what_check_reported():
+    xy = np.array([[1.0, 2.0], [3.0, 4.0], [5.0, 6.5], [7.0, 1.0], [2.0, 9.0]])
+    ty = np.array([0, 1, 2, 1, 0], np.int32)
+    far, nan = xy.copy(), xy.copy()
+    far[0, 0], far[1, 0], nan[2, 1] = 1e308, -1e308, np.nan
+    R0 = "radius = 0: it must be positive and its square a normal, finite float64"
+    RS = "radius must be a number, got '5'"
+    # (xy, types, radius, k, nr_types) -> the exception of `neighbours._check`, literally
+    rows = [((xy.astype(np.float32), ty, 3.0, 2, 3), TypeError, "xy must be a float64 numpy array [N, 2], got float32"),
+            ((xy.tolist(), ty, 3.0, 2, 3), TypeError, "xy must be a float64 numpy array [N, 2], got list"),
+            ((xy.reshape(2, 5), ty, 3.0, 2, 3), ValueError, "xy must be [N, 2] with N >= 1, got (2, 5)"),
+            ((xy[:0], ty[:0], 3.0, 2, 3), ValueError, "xy must be [N, 2] with N >= 1, got (0, 2)"),
+            ((nan, ty, 3.0, 2, 3), ValueError, "xy holds a coordinate that is not finite"),
+            ((far, ty, 3.0, 2, 3), ValueError, "the extent of xy is not a finite float64"),
+            ((xy, ty, 0, 2, 3), ValueError, R0),
+            ((xy, ty, "5", 2, 3), TypeError, RS),
+            ((xy, ty, True, 2, 3), TypeError, "radius must be a number, got True"),
+            ((xy, ty, 1e-200, 2, 3), ValueError, "radius = 1e-200: it must be positive and its square a normal, finite float64"),
+            ((xy, ty, 3.0, 2.0, 3), TypeError, "k must be an integer, got 2.0"),
+            ((xy, ty, 3.0, 17, 3), ValueError, "k = 17 outside 1..16"),
+            ((xy, ty[:3], 3.0, 2, 3), ValueError, "types (3,) is not parallel to xy (5, 2)"),
+            ((xy, ty.astype(np.int64), 3.0, 2, 3), TypeError, "types must be an int32 numpy array [N] or None, got int64"),
+            ((xy, ty + 5, 3.0, 2, 3), ValueError, "types outside [0, 3)"),
+            ((xy, ty - 1, 3.0, 2, None), ValueError, "types outside [0, 2)"),
+            ((xy, ty, 3.0, 2, 2.0), TypeError, "nr_types must be an integer or None, got 2.0"),
+            ((xy, None, 3.0, 2, 17), ValueError, "17 types outside 1..16"),
+            ((xy, ty + 5, 0, 2, 3), ValueError, R0),                 # two faults: the radius is reported, not the types
+            ((xy, ty[:3], "5", 2, 3), TypeError, RS),
+            ((nan, ty, 0, 2, 3), ValueError, "xy holds a coordinate that is not finite"),   # two faults: the points are reported, not the radius
+            ((xy, ty + 5, 3.0, 0, 3), ValueError, "k = 0 outside 1..16")]
+    for args, exc, text in rows:
+        with pytest.raises(exc) as old:
+            NB._check(*args)
+        with pytest.raises(exc) as new:
+            _new_check(*args)
+        assert type(old.value) is type(new.value) is exc and str(old.value) == str(new.value) == text, text
+    good = NB._check(xy[::-1], ty, 3, 2, None)                        # and what passes comes back the same: contiguous, converted
+    _same(tuple(_new_check(xy[::-1], ty, 3, 2, None)), tuple(good))
+    assert good[0].flags.c_contiguous and type(good[2]) is float and good[2:] == (3.0, 2, 3)
+    _same(P.check_types(None, 5, None), (None, 1))
+    # the four other modules: their first fault for the two-fault rows, as they reported it before the validators moved
+    rs = RG.RegionSet.from_polygons([[[[(0, 0), (8, 0), (8, 8), (0, 8)]]]])
+    raster, window = (0.0, 0.0, 1.0, 4, 4), (0, 0, 10, 10)
+    for (r, types), exc, text, text_rg in (((0, ty + 5), ValueError, R0, "types outside [0, 3)"),
+                                           (("5", ty[:3]), TypeError, RS, "types (3,) is not parallel to xy (5, 2)")):
+        for call in (lambda: DN._check(xy, types, r, raster, 3), lambda: CL._check(xy, types, r, 3, None), lambda: RP._check(xy, types, [r], window, 3),
+                     lambda: RP._check(xy, types, [2.0, r], window, 3), lambda: RG._check(xy, types, rs, 3, cell=r)):
+            with pytest.raises(exc) as got:
+                call()
+            assert type(got.value) is exc and str(got.value) == text
+        with pytest.raises(ValueError) as got:
+            RG._check(xy, types, rs, 3)                              # no cell: nothing but the types is wrong
+        assert str(got.value) == text_rg
+    for call, text in ((lambda: DN._check(nan, ty, 0, raster, 3), "xy holds a coordinate that is not finite"),
+                       (lambda: CL._check(nan, ty, 0, 3, None), "xy holds a coordinate that is not finite"),
+                       (lambda: CL._check(xy, ty + 20, 3.0, 0, None), "23 types outside 1..16"),     # types before min_pts
+                       (lambda: RP._check(nan, ty, [0], window, 3), R0),                             # radii before the points
+                       (lambda: RG._check(nan, ty, rs, 3, cell=0), R0),                              # the cell before the points
+                       (lambda: RG._check(nan, ty, [rs], 3, cell=0), "rs must be a RegionSet (RegionSet.from_polygons / from_geojson), got 'list'")):
+        with pytest.raises((ValueError, TypeError)) as got:
+            call()
+        assert str(got.value) == text

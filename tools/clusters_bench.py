@@ -56,7 +56,7 @@ def main():
             q = CL.DeviceClusters(xy, None, radius, min_pts)
             g = q.grid
             q.run_grid()
-            q.run_cluster()
+            q.run_op()
             dev = q.result()
             print("%d points, r = %g, m = %d: device done, host running" % (n, radius, min_pts), flush=True)
             t0 = time.perf_counter()
@@ -66,7 +66,7 @@ def main():
                 assert np.array_equal(dev[name], host[name]), "%d points: the device's %s differs from cluster_host's" % (n, name)
             samp = {"grid": [], "cluster": []}
             for it in range(a.reps + 2):
-                for name, fn in (("grid", q.run_grid), ("cluster", q.run_cluster)):
+                for name, fn in (("grid", q.run_grid), ("cluster", q.run_op)):
                     ms = timed(fn)
                     if it >= 2:
                         samp[name].append(ms)

@@ -67,7 +67,7 @@ def main():
             q = DN.DeviceDensity(xy, types, radius, raster, 5)
             g, raster = q.grid, q.raster
             q.run_grid()
-            q.run_density()
+            q.run_op()
             dev = q.result()
             print("%d points, r = %g, step = %d: device done, host running" % (n, radius, step), flush=True)
             t0 = time.perf_counter()
@@ -76,10 +76,10 @@ def main():
             assert dev.dtype == host.dtype and np.array_equal(dev, host), "%d points: the device's count differs from density_host's" % n
             nq = NB.DeviceQuery(xy, types, radius, 5, 5)
             nq.run_grid()
-            nq.run_query()
+            nq.run_op()
             samp = {"grid": [], "density": [], "query": []}
             for it in range(a.reps + 2):
-                for name, fn in (("grid", q.run_grid), ("density", q.run_density), ("query", nq.run_query)):
+                for name, fn in (("grid", q.run_grid), ("density", q.run_op), ("query", nq.run_op)):
                     ms = timed(fn)
                     if it >= 2:
                         samp[name].append(ms)

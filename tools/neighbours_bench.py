@@ -49,7 +49,7 @@ def main():
         q = NB.DeviceQuery(xy, types, RADIUS, K, TYPES)
         g = q.grid
         q.run_grid()
-        q.run_query()
+        q.run_op()
         dev = q.result()
         print("%d points: device done, host running" % n, flush=True)
         t0 = time.perf_counter()
@@ -59,7 +59,7 @@ def main():
             assert np.array_equal(dev[name], host[name]), "%d points: the device's %s differs from query_host's" % (n, name)
         samp = {"grid": [], "query": []}
         for it in range(a.reps + 2):
-            for name, fn in (("grid", q.run_grid), ("query", q.run_query)):
+            for name, fn in (("grid", q.run_grid), ("query", q.run_op)):
                 ms = timed(fn)
                 if it >= 2:
                     samp[name].append(ms)

@@ -92,7 +92,7 @@ def main():
         q = RG.DeviceRegions(xy, types, rs, 5)
         g = q.grid
         q.run_grid()
-        q.run_regions()
+        q.run_op()
         dev = q.result()
         print("%d points, %d edges: device done, host running" % (n, ne), flush=True)
         t0 = time.perf_counter()
@@ -102,8 +102,8 @@ def main():
         radii = [150.0 * (k + 1) / 16 for k in range(16)]
         pq = RP.DeviceRipley(xy, types, radii, RP.window_of((int(np.ceil(side)) + 1, int(np.ceil(side)) + 1)), 5)
         pq.run_grid()
-        pq.run_pairs()
-        samp = sample([("grid", q.run_grid), ("regions", q.run_regions), ("pairs", pq.run_pairs)], a.reps)
+        pq.run_op()
+        samp = sample([("grid", q.run_grid), ("regions", q.run_op), ("pairs", pq.run_op)], a.reps)
         assert same(q.result(), host), "the timed launches changed the result"
         med = {name: statistics.median(v) for name, v in samp.items()}
         tests, ptests = edge_tests(xy, q, RG), candidates(xy, pq.grid)
@@ -123,9 +123,9 @@ def main():
         for label, cell in forms:
             f = RG.DeviceRegions(xy, types, rs, 5, cell=cell)
             f.run_grid()
-            f.run_regions()
+            f.run_op()
             assert same(f.result(), host), "%s: the result differs" % label
-            ms = sample([("regions", f.run_regions)], 3 if label == "one row" else a.reps)["regions"]
+            ms = sample([("regions", f.run_op)], 3 if label == "one row" else a.reps)["regions"]
             ft = edge_tests(xy, f, RG)
             out[key][label] = {"rows": f.grid.ncy, "cell_side": f.grid.c, "entries": f.entries, "edge_tests": ft, "regions_ms": stat(ms)}
             lines.append("    %-8s %10.4f  [%10.4f .. %10.4f]   %s: %d rows of %.4f px, %d entries, %d edge tests, %.3g per second; same integers: yes"

@@ -70,7 +70,7 @@ def main():
             q = RP.DeviceRipley(xy, types, radii, window, 5)
             g = q.grid
             q.run_grid()
-            q.run_pairs()
+            q.run_op()
             dev = q.result()
             print("%d points, r_max = %g: device done, host running" % (n, rmax), flush=True)
             t0 = time.perf_counter()
@@ -79,8 +79,8 @@ def main():
             assert same(dev, host), "%d points, r_max %g: the device's counts differ from pairs_host's" % (n, rmax)
             nq = NB.DeviceQuery(xy, types, rmax, 5, 5)
             nq.run_grid()
-            nq.run_query()
-            samp = sample([("grid", q.run_grid), ("pairs", q.run_pairs), ("query", nq.run_query)], a.reps)
+            nq.run_op()
+            samp = sample([("grid", q.run_grid), ("pairs", q.run_op), ("query", nq.run_op)], a.reps)
             assert same(q.result(), host), "the timed launches changed the result"
             med = {name: statistics.median(v) for name, v in samp.items()}
             tests = candidates(xy, g)
@@ -101,9 +101,9 @@ def main():
     xy = np.tile([[40.0, 30.0]], (n, 1))
     q = RP.DeviceRipley(xy, None, [2.0, 5.0], (0.0, 0.0, 100.0, 50.0))
     q.run_grid()
-    q.run_pairs()
+    q.run_op()
     assert q.result().pairs.tolist() == [[[n * (n - 1)] * 2]], "coincident points: not N (N - 1)"
-    samp = sample([("pairs", q.run_pairs)], a.reps)["pairs"]
+    samp = sample([("pairs", q.run_op)], a.reps)["pairs"]
     out["coincident,%d" % n] = {"pairs_ms": stat(samp)}
     lines.append("%d coincident points of one type: %d candidate tests, every add on one bin; == N (N - 1): yes" % (n, n * n))
     lines.append("    %-8s %10.4f  [%10.4f .. %10.4f]   %.3g candidate tests per second" % ("pairs", statistics.median(samp), min(samp), max(samp), n * n / statistics.median(samp) * 1e3))
