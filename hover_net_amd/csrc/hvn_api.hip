@@ -511,6 +511,34 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.rt & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs: misaligned window and radius table (8)");
         return hvn_launch_status(hvn_launch_nbr_pairs(a, s), "nbr_pairs");
     }
+    case HVN_OP_NBR_PAIRS_SIM: {
+        NbrPairsSimArgs a;
+        a.table = (const double *)op->w;
+        a.rt = (const double *)op->bias;
+        a.workspace = op->x2.base;
+        a.types = (const int *)op->res.base;
+        a.keys = (const unsigned long long *)op->w2;
+        a.labels = (unsigned *)op->y2.base;
+        a.out = (long long *)op->y.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.R = op->_rsv; a.SB = op->nbatch; a.phase = op->stride;
+        if (!a.workspace || !a.out || !a.rt || !a.keys || !a.labels) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: null pointer");
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: %d types outside 1..16", a.T);
+        if (a.R < 1 || a.R > HVN_NBR_PAIRS_MAX_R) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: %d radii outside 1..32", a.R);
+        if (a.SB < 1 || a.SB > HVN_NBR_PAIRS_SIM_MAX_SB) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: a batch of %d simulations outside 1..32", a.SB);
+        if (a.phase < 0 || a.phase > 2) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: stride = %d is no phase (0: both, 1: labels, 2: pairs)", a.phase);
+        if (a.T * a.T * a.R > HVN_NBR_PAIRS_MAX_BINS)
+            return hvn_fail(HVN_E_SIZE, "nbr_pairs_sim: %d x %d types and %d radii, more than 4096 bins", a.T, a.T, a.R);
+        if (HVN_NBR_PAIRS_SIM_LDS_BYTES(a.SB, a.T * a.T * a.R) > HVN_NBR_PAIRS_SIM_MAX_LDS)
+            return hvn_fail(HVN_E_SIZE, "nbr_pairs_sim: %d histograms of %d bins need %ld bytes of LDS, more than %ld", a.SB, a.T * a.T * a.R,
+                            HVN_NBR_PAIRS_SIM_LDS_BYTES(a.SB, a.T * a.T * a.R), HVN_NBR_PAIRS_SIM_MAX_LDS);
+        if (int rc = nbr_common("nbr_pairs_sim", op, batch)) return rc;
+        if ((long)op->y2.sn < HVN_NBR_PAIRS_SIM_LABEL_BYTES(a.N, a.SB))
+            return hvn_fail(HVN_E_SIZE, "nbr_pairs_sim: label workspace of %ld bytes, %ld needed", (long)op->y2.sn, HVN_NBR_PAIRS_SIM_LABEL_BYTES(a.N, a.SB));
+        if (((uintptr_t)a.out | (uintptr_t)a.keys) & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: misaligned out or key table (8)");
+        if ((uintptr_t)a.rt & 7) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: misaligned window and radius table (8)");
+        if (((uintptr_t)a.types | (uintptr_t)a.labels) & 3) return hvn_fail(HVN_E_ARG, "nbr_pairs_sim: misaligned types or label workspace (4)");
+        return hvn_launch_status(hvn_launch_nbr_pairs_sim(a, s), "nbr_pairs_sim");
+    }
     case HVN_OP_NBR_REGIONS: {
         NbrRegionsArgs a;
         a.table = (const double *)op->w;

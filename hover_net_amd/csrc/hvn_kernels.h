@@ -303,6 +303,38 @@ struct NbrPairsArgs {
     int N, ncy, ncx, T, R;
 };
 int hvn_launch_nbr_pairs(const NbrPairsArgs &a, hipStream_t stream);
+// what hvn_pairs.hip and hvn_pairs_sim.hip share: the workgroup, the staging tile and the flush interval
+#define RP_T 256
+#define RP_TILE 1024          // candidates per staging tile, as nb_query's NB_TILE
+#define RP_FLUSH 32           // tiles between two flushes: 32 * 1024 * 256 = 2^23 tests
+#define RP_NONE 0x7FFFFFFF
+#ifdef __HIPCC__
+// The wave's LDS adds have been carried out, not merely issued (lgkmcnt(0); the other counters are left alone).  It stands before every
+// barrier that a flush follows: the compiler's own wait was missing in front of the barrier at the top of the tile loop, and a wave that
+// passed it read and cleared the histogram while another wave's last adds -- 64 lanes on one word take the LDS a while -- were still on
+// their way: 70 000 coincident points of one type lost 84 wave-adds of hx that way.
+__device__ __forceinline__ void rp_adds_done() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+#endif
+// hvn_pairs_sim.hip: the same counts under SB random relabellings of the points, the border-corrected plane only (ripley.py: `sims_host`)
+#define HVN_NBR_PAIRS_SIM_MAX_SB 32
+#define HVN_NBR_PAIRS_SIM_WORDS(SB) (((SB) + 3) / 4)        // 32-bit words of one point's labels, a byte per simulation
+// dynamic LDS of the pair kernel: SB histograms of T T R words, and W label words per staged candidate and per lane; with its static
+// arrays (the staged coordinates, 16672 bytes) a workgroup then stays within the 160 KiB of a CU
+#define HVN_NBR_PAIRS_SIM_LDS_BYTES(SB, bins) (4L * (SB) * (bins) + 4L * (RP_TILE + RP_T) * HVN_NBR_PAIRS_SIM_WORDS(SB))
+#define HVN_NBR_PAIRS_SIM_MAX_LDS (140L * 1024)
+#define HVN_NBR_PAIRS_SIM_LABEL_BYTES(N, SB) (4L * (N) * HVN_NBR_PAIRS_SIM_WORDS(SB))
+struct NbrPairsSimArgs {
+    const double *table;        // {x0, y0, c, r2_{R-1}}, as for the grid
+    const double *rt;           // as NbrPairsArgs::rt
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    const int *types;           // [N] by POSITION (the grid op's input) or NULL (all 0)
+    const unsigned long long *keys;     // [SB][8] round keys
+    unsigned *labels;           // HVN_NBR_PAIRS_SIM_LABEL_BYTES(N, SB): [N][W] words by slot; every word read is written first
+    long long *out;             // [SB][T T R + T (R + 1)]: per simulation acc [T][T][R], then cnt [T][R + 1]; cleared in stream order
+    int N, ncy, ncx, T, R, SB;
+    int phase;                  // 0: both launches; 1: out cleared and the labels made only; 2: the pairs only, on the labels as they are
+};
+int hvn_launch_nbr_pairs_sim(const NbrPairsSimArgs &a, hipStream_t stream);
 // hvn_regions.hip: exact point-in-polygon of the points against the canonical edges of G regions (hover_net_amd/regions.py)
 #define HVN_NBR_REGIONS_MAX_G 4096
 #define HVN_NBR_REGIONS_MAX_E (1 << 22)

@@ -43,23 +43,12 @@
 
 #include "hvn_kernels.h"
 
-#define RP_T 256
-#define RP_TILE 1024          // candidates per staging tile, as nb_query's NB_TILE
-#define RP_FLUSH 32           // tiles between two flushes: 32 * 1024 * 256 = 2^23 tests
-#define RP_NONE 0x7FFFFFFF
-
 struct PairsDev {
     const double *sx, *sy, *table, *rt;
     const int *stype, *cell_start;
     unsigned long long *acc;
     int N, ncy, ncx, T, R;
 };
-
-// The wave's LDS adds have been carried out, not merely issued (lgkmcnt(0); the other counters are left alone).  It stands before every
-// barrier that a flush follows: the compiler's own wait was missing in front of the barrier at the top of the tile loop, and a wave that
-// passed it read and cleared the histogram while another wave's last adds -- 64 lanes on one word take the LDS a while -- were still on
-// their way: 70 000 coincident points of one type lost 84 wave-adds of hx that way.
-__device__ __forceinline__ void rp_adds_done() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 // h0 and hx into acc, non-zero words only, and both planes cleared; the caller puts a barrier before and after
 __device__ __forceinline__ void rp_flush(unsigned *hist, unsigned long long *acc, int bins, int tid)

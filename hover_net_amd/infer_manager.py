@@ -184,7 +184,8 @@ class InferManager:
         are cut (hover_net_amd/stain.py); neighbours, clusters, density (default None): the point-pattern
         analyses of hover_net_amd/points.py on every image's finished dict -- every nucleus of `json/` gains "neighbours" / "cluster", and
         with `density` rank 0 also writes `density/<name>.npz` (`density.save`: `count` int32 [T, H, W], `origin`, `step`, `radius`);
-        `json/` is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py) -- rank 0
+        `json/` is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window", and "sims" / "seed" for the random-labelling test
+        (hover_net_amd/ripley.py) -- rank 0
         also writes `ripley/<name>.npz` (`ripley.save`: the typed pair counts under the cross-type K function, of every image's finished
         dict over the image); `json/` is as without it; regions (default None): {"dir": d} with an optional "scale"
         (hover_net_amd/regions.py) -- an image with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels
@@ -330,8 +331,8 @@ class WsiManager(InferManager):
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
         (`WsiInference(stain_norm=...)`); neighbours, clusters, density (default None): the point-pattern analyses of hover_net_amd/points.py, in
         pixels at proc_mag, on the merged slide dict (`WsiInference`) -- every nucleus of the json gains "neighbours" / "cluster", and with `density` rank 0 also
-        writes `density/<name>.npz` (`density.save`); the json is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window"
-        (hover_net_amd/ripley.py), in pixels at proc_mag -- rank 0 also writes `ripley/<name>.npz` (`ripley.save`), the pair counts of the merged slide
+        writes `density/<name>.npz` (`density.save`); the json is as without it; ripley (default None): {"radii": [r, ..]} with an optional "window", and "sims" / "seed" for the
+        random-labelling test (hover_net_amd/ripley.py), in pixels at proc_mag -- rank 0 also writes `ripley/<name>.npz` (`ripley.save`), the pair counts of the merged slide
         dict (`WsiInference(ripley=...)`); the json is as without it; regions (default None): {"dir": d} with an optional "scale"
         (hover_net_amd/regions.py) -- a slide with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels at proc_mag) gets
         "region" on every nucleus of the json and rank 0 writes `regions/<name>.npz` (`regions.save`) from the merged slide dict

@@ -519,6 +519,7 @@ class WsiInference:
         ripley: None or {"radii": [r, ..]} with an optional "window" (hover_net_amd/ripley.py): `self.ripley` holds the slide's
         `ripley.PairCounts` -- the typed pair counts under the cross-type K function, of the merged dict over the processed slide -- on
         rank 0 (None elsewhere and before the first slide), computed once after the merge as the others are; nothing else changes.
+        With "sims": S and an optional "seed" it holds the `ripley.LabelSims` of the random-labelling test instead.
         regions: None or {"regions": RegionSet | list of regions | GeoJSON path or dict} with an optional "scale" (hover_net_amd/regions.py),
         in pixels of the processed slide after the scale: `self.regions` holds the slide's `regions.RegionCounts` -- which annotated region
         holds which nucleus of the merged dict, and the typed counts per region -- on rank 0 (None elsewhere and before the first slide),

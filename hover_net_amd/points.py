@@ -22,7 +22,8 @@ into one `PointSpecs` by each module's own `resolve`, in this order; a bad spec 
     clusters    {"radius": r, "min_pts": m} with an optional "types": [ints], which needs nr_types: every entry gains "cluster"
                 (`clusters.annotate`)
     density     {"radius": r, "step": s}, `step` an integer >= 1: a `density.DensityMap` of the dict over the image (`density.of_info`)
-    ripley      {"radii": [r, ..]} with an optional "window": the `ripley.PairCounts` of the dict over the image (`ripley.of_info`)
+    ripley      {"radii": [r, ..]} with an optional "window": the `ripley.PairCounts` of the dict over the image (`ripley.of_info`);
+                with "sims": S and an optional "seed" the `ripley.LabelSims` of the random-labelling test
     regions     {"regions": RegionSet | list | GeoJSON path} with an optional "scale" (the managers take {"dir": d} and read
                 `<d>/<name>.geojson`): the `regions.RegionCounts` of the dict against annotated polygons (`regions.of_info`); every
                 entry gains "region" (`regions.annotate`)
@@ -272,7 +273,7 @@ ARGS = ("neighbours", "clusters", "density", "ripley", "regions")
 
 class PointSpecs(collections.namedtuple("PointSpecs", ARGS)):
     """The five resolved arguments of the module docstring, None where off: (r, k), (r, m, types tuple | None), (r, step),
-    (radii tuple, window tuple | None), a `regions.RegionSet`."""
+    (radii tuple, window tuple | None) or (radii, window, sims, seed), a `regions.RegionSet`."""
     __slots__ = ()
 
     @property
@@ -322,7 +323,8 @@ def _density(info, size_hw, spec, nr_types, device):
 def _ripley(info, size_hw, spec, nr_types, device):
     from . import ripley as RP
 
-    return RP.of_info(info, size_hw, spec[0], nr_types, device=device, window=spec[1])
+    sims, seed = spec[2:] if len(spec) == 4 else (None, 0)
+    return RP.of_info(info, size_hw, spec[0], nr_types, device=device, window=spec[1], sims=sims, seed=seed)
 
 
 def _regions(info, _size_hw, rs, nr_types, device):

@@ -40,7 +40,8 @@ typedef struct hvn_view {
 
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
-       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19 };
+       HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19,
+       HVN_OP_NBR_PAIRS_SIM = 20 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -216,6 +217,37 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: a null pointer, out / edge_region / rows not 4-byte or edges / table / workspace not 8-byte aligned, batch != 1,
  *           N < 1, T outside 1..16, G < 1, E < 1, M < 1, kh or kw < 1.  HVN_E_SIZE: G > 4096, E > 2^22, M > 8 E + kh, N > 2^26, kh or
  *           kw > 4096 or kh * kw > 2^22, x2.sn too small.
+ *     NBR_PAIRS_SIM  the border-corrected counts of NBR_PAIRS under a BATCH of SB random relabellings of the points: the integers behind
+ *           the random-labelling envelopes of Ripley's cross-type K (hover_net_amd/ripley.py holds the definition, `sims_host`;
+ *           csrc/hvn_pairs_sim.hip).  Runs after NBR_GRID on the same stream and reads the workspace as that op left it for the same N,
+ *           kh, kw and table (x.base is not read); x.h, kh, kw, w, x2.base and x2.sn are the shared fields above, table[3] is r2 of
+ *           the LARGEST radius, and cout = T, `_rsv` = R and bias = the window and radius table are those of NBR_PAIRS.  The rest takes
+ *           fields the family leaves free: nbatch = SB in 1..32 with 4 SB T T R + 5120 ceil(SB / 4) <= 143360, the bytes of LDS that a
+ *           workgroup's SB histograms and staged labels take; res.base = the int32 types [N] in ORIGINAL order, as NBR_GRID's (4-byte
+ *           aligned) or NULL = all 0; w2 = uint64 round keys [SB][8] on the device (8-byte aligned; read as 64-bit integers whatever the
+ *           pointer's declared type), formed by the caller; y2.base = a label workspace of the op's own (4-byte aligned) of y2.sn
+ *           BYTES >= 4 N ceil(SB / 4), which is at least N SB: per slot one byte per simulation in words of four.  The op writes every
+ *           word of it that it reads.  y.base = int64 out [SB][T T R + T (R + 1)], contiguous (8-byte aligned): per simulation
+ *           acc [T][T][R], then cnt [T][R + 1].  Simulation s labels the point at position p with types[pi_s(p)], where pi_s(p) is the
+ *           first of F_s(p), F_s(F_s(p)), .. below N and F_s is the Feistel bijection of [0, 2^b), b = max(2, bit_length(N - 1)),
+ *           hl = b / 2 low and hh = b - hl high bits, of eight rounds: hi ^= mix(lo + key[s][r]) & (2^hh - 1) for even r, lo ^=
+ *           mix(hi + key[s][r]) & (2^hl - 1) for odd r, mix the splitmix64 finaliser, uint64 with wrap-around.  The walk ends after at
+ *           most 2^b - N + 1 steps and the loop is bounded by that count.  With kmin and m_i as in NBR_PAIRS, every ordered pair (i, j),
+ *           j != i, with kmin < m_i and labels (a, b) in simulation s adds 1 to acc[s][a][b][kmin] and -1 to acc[s][a][b][m_i] (the
+ *           latter where m_i < R): plane 1 of NBR_PAIRS, whose running sum over the last axis the caller forms; every point i adds 1
+ *           to cnt[s][a][m_i], and the points of type a at least r_k inside the window are the sum of cnt[s][a][m] over m > k.  A type
+ *           outside [0, T) lands in no bin, as i or as j, wherever the permutation puts it.  The geometry of a pair is tested once for
+ *           the whole batch.  EVERY element of out is written, whatever it held before: the op clears it itself, in stream order.
+ *           stride = 0 is that op; 1 and 2 are its two halves, so that they can be timed apart (tools/ripley_sims_bench.py): 1 clears
+ *           out and makes the labels and cnt only, 2 only adds the pairs into out, from the labels as the workspace holds them.
+ *           Integer sums (signed 32-bit in LDS, flushed into 64-bit global atomics before a word could pass 2^23 in magnitude): a
+ *           function of the inputs alone.  Loops are bounded by cell_start values clamped to [0, N], by SB and by the walk's count, and
+ *           a position read from the workspace is clamped to [0, N): a workspace NBR_GRID did not fill gives wrong numbers, no access
+ *           outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer (types excepted), out / keys / a table / workspace not 8-byte or types / labels not 4-byte
+ *           aligned, batch != 1, N < 1, T outside 1..16, R outside 1..32, SB outside 1..32, stride outside 0..2, kh or kw < 1.  HVN_E_SIZE: T T R > 4096,
+ *           the histograms and labels above 143360 bytes of LDS, y2.sn too small, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
+ *           too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
