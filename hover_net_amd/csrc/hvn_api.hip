@@ -563,6 +563,37 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.edges & 7) return hvn_fail(HVN_E_ARG, "nbr_regions: misaligned edge table (8)");
         return hvn_launch_status(hvn_launch_nbr_regions(a, s), "nbr_regions");
     }
+    case HVN_OP_NBR_MARGINS: {
+        NbrMarginsArgs a;
+        a.table = (const double *)op->w;
+        a.seg = (const double *)op->bias;
+        a.w2 = (const double *)op->w2;
+        a.seg_region = (const int *)op->res.base;
+        a.rows = (const int *)op->y2.base;
+        a.workspace = op->x2.base;
+        a.out = op->y.base;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw; a.T = op->cout; a.G = op->_rsv; a.S = op->res.h; a.B = op->cout2; a.no_cull = op->stride != 0;
+        if (!a.workspace || !a.out) return hvn_fail(HVN_E_ARG, "nbr_margins: null pointer");
+        if (!a.seg) return hvn_fail(HVN_E_ARG, "nbr_margins: null segment table (bias)");
+        if (!a.w2) return hvn_fail(HVN_E_ARG, "nbr_margins: null table of squared widths (w2)");
+        if (!a.seg_region) return hvn_fail(HVN_E_ARG, "nbr_margins: null table of segment regions (res)");
+        if (!a.rows) return hvn_fail(HVN_E_ARG, "nbr_margins: null row lists (y2)");
+        if (a.B < 1 || a.B > HVN_NBR_MARGINS_MAX_B) return hvn_fail(HVN_E_ARG, "nbr_margins: %d widths outside 1..16", a.B);
+        if (a.T < 1 || a.T > 16) return hvn_fail(HVN_E_ARG, "nbr_margins: %d types outside 1..16", a.T);
+        if (a.G < 1 || a.G > HVN_NBR_MARGINS_MAX_G) return hvn_fail(a.G < 1 ? HVN_E_ARG : HVN_E_SIZE, "nbr_margins: %d regions outside 1..4096", a.G);
+        if (a.S < 1) return hvn_fail(HVN_E_ARG, "nbr_margins: %d segments, fewer than one", a.S);
+        if (a.S > HVN_NBR_MARGINS_MAX_S) return hvn_fail(HVN_E_SIZE, "nbr_margins: %d segments above 2^22", a.S);
+        if (op->y2.sn < 0) return hvn_fail(HVN_E_ARG, "nbr_margins: row lists of %ld entries, fewer than none", (long)op->y2.sn);
+        if (int rc = nbr_common("nbr_margins", op, batch)) return rc;
+        if ((long)op->y2.sn > HVN_NBR_MARGINS_MAX_ENTRIES(a.S, a.ncy))
+            return hvn_fail(HVN_E_SIZE, "nbr_margins: row lists of %ld entries, more than 8 S + kh = %ld", (long)op->y2.sn, HVN_NBR_MARGINS_MAX_ENTRIES(a.S, a.ncy));
+        a.M = (int)op->y2.sn;
+        if ((long)op->y.sn < HVN_NBR_MARGINS_OUT_BYTES(a.N, a.G, a.B, a.T))
+            return hvn_fail(HVN_E_SIZE, "nbr_margins: output of %ld bytes, %ld needed", (long)op->y.sn, HVN_NBR_MARGINS_OUT_BYTES(a.N, a.G, a.B, a.T));
+        if (((uintptr_t)a.seg_region | (uintptr_t)a.rows) & 3) return hvn_fail(HVN_E_ARG, "nbr_margins: misaligned seg_region or rows (4)");
+        if (((uintptr_t)a.seg | (uintptr_t)a.w2 | (uintptr_t)a.out) & 7) return hvn_fail(HVN_E_ARG, "nbr_margins: misaligned segment table, widths or out (8)");
+        return hvn_launch_status(hvn_launch_nbr_margins(a, s), "nbr_margins");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

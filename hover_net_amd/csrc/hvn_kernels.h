@@ -349,6 +349,25 @@ struct NbrRegionsArgs {
     int N, ncy, ncx, T, G, E, M;
 };
 int hvn_launch_nbr_regions(const NbrRegionsArgs &a, hipStream_t stream);
+// hvn_margins.hip: the points by distance to the boundary segments of G regions, in B bands (hover_net_amd/margins.py)
+#define HVN_NBR_MARGINS_MAX_B 16
+#define HVN_NBR_MARGINS_MAX_G 4096
+#define HVN_NBR_MARGINS_MAX_S (1 << 22)
+#define HVN_NBR_MARGINS_MAX_ENTRIES(S, ncy) (8L * (S) + (ncy))      // the row lists' total length
+#define HVN_NBR_MARGINS_OUT_BYTES(N, G, B, T) (16L * (N) + 8L * (G) * (B) * (T))
+struct NbrMarginsArgs {
+    const double *table;        // {x0, y0, c, r2}, as for the grid (r2 is not read)
+    const double *seg;          // [S][8] = (ax, ay, bx, by) with (ay, ax) <= (by, bx), then the box (x0, y0, x1, y1)
+    const double *w2;           // [B] squared widths, ascending
+    const int *seg_region;      // [S], ascending
+    const int *rows;            // row_start [ncy + 1], then the segment numbers of the row lists [M]
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    void *out;                  // near_d2 double [N], then int near [N], near_inside [N], hist [G][2][B][T]; hist is cleared in
+                                // stream order, then every element is written
+    int N, ncy, ncx, T, G, S, M, B;
+    int no_cull;                // != 0: the kernel form without the x-cull of the staged tile (same numbers; for measurements)
+};
+int hvn_launch_nbr_margins(const NbrMarginsArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

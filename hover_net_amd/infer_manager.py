@@ -122,19 +122,21 @@ def _given(run_args, *names):
 
 
 def _regions_dir(spec):
-    """run_args["regions"]: None -> None, {"dir": d} with an optional "scale" -> (d, scale); ValueError / TypeError otherwise."""
+    """run_args["regions"]: None -> None, {"dir": d} with an optional "scale" and an optional "margin": [w_0, ..] (margins.py's widths)
+    -> (d, scale, widths | None); ValueError / TypeError otherwise."""
+    from . import margins as MG
     from . import regions as RG
 
     if spec is None:
         return None
-    if not isinstance(spec, dict) or not isinstance(spec.get("dir"), (str, os.PathLike)) or not set(spec) <= {"dir", "scale"}:
-        raise ValueError('regions=%r: None or {"dir": directory of <name>.geojson files} with an optional "scale"' % (spec,))
-    return os.fspath(spec["dir"]), RG._check_scale(spec.get("scale", 1.0))
+    if not isinstance(spec, dict) or not isinstance(spec.get("dir"), (str, os.PathLike)) or not set(spec) <= {"dir", "scale", "margin"}:
+        raise ValueError('regions=%r: None or {"dir": directory of <name>.geojson files} with an optional "scale" and an optional "margin"' % (spec,))
+    return os.fspath(spec["dir"]), RG._check_scale(spec.get("scale", 1.0)), MG.check_widths(spec["margin"]) if "margin" in spec else None
 
 
 def _regions_spec(regions, name):
-    """The `regions` argument of one image or slide: {"regions": <dir>/<name>.geojson, "scale": s}, or None (logged) where that file is
-    missing: the image is then processed without regions."""
+    """The `regions` argument of one image or slide: {"regions": <dir>/<name>.geojson, "scale": s} (and "margin" where the run asks for
+    it), or None (logged) where that file is missing: the image is then processed without regions."""
     import logging
 
     if regions is None:
@@ -143,7 +145,7 @@ def _regions_spec(regions, name):
     if not os.path.isfile(path):
         logging.warning("regions: %s is missing; %s is processed without regions", path, name)
         return None
-    return {"regions": path, "scale": regions[1]}
+    return dict({"regions": path, "scale": regions[1]}, **({} if regions[2] is None else {"margin": list(regions[2])}))
 
 
 class InferManager:
@@ -190,7 +192,10 @@ class InferManager:
         dict over the image); `json/` is as without it; regions (default None): {"dir": d} with an optional "scale"
         (hover_net_amd/regions.py) -- an image with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels
         of the image) gets "region" on every nucleus of `json/` and rank 0 writes `regions/<name>.npz` (`regions.save`: which region
-        holds which nucleus, typed counts per region); an image without that file is logged and processed as without the argument.
+        holds which nucleus, typed counts per region); with "margin": [w_0, ..] in that dict (hover_net_amd/margins.py; widths in pixels
+        of the image) every nucleus also gets "margin" (the nearest region's name and the signed distance to its boundary) and the .npz
+        the margin_* arrays (the typed counts per region, side and distance band); an image without that file is logged and processed
+        as without the argument.
         Returns the list of image names written, in processing order (rank 0; [] on the other ranks)."""
         import psutil
 
@@ -336,7 +341,8 @@ class WsiManager(InferManager):
         dict (`WsiInference(ripley=...)`); the json is as without it; regions (default None): {"dir": d} with an optional "scale"
         (hover_net_amd/regions.py) -- a slide with a `<d>/<name>.geojson` of annotation polygons (its vertices times `scale` are pixels at proc_mag) gets
         "region" on every nucleus of the json and rank 0 writes `regions/<name>.npz` (`regions.save`) from the merged slide dict
-        (`WsiInference(regions=...)`); a slide without that file is logged and processed as without the argument.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
+        (`WsiInference(regions=...)`); with "margin": [w_0, ..] in that dict (hover_net_amd/margins.py; widths in pixels at proc_mag)
+        every nucleus also gets "margin" and the .npz the margin_* arrays; a slide without that file is logged and processed as without the argument.  Returns {name: "done" | "skip" | "empty mask" | "crash"}."""
         import logging
 
         from . import infer_tile, infer_wsi, tissue_mask

@@ -524,6 +524,9 @@ class WsiInference:
         in pixels of the processed slide after the scale: `self.regions` holds the slide's `regions.RegionCounts` -- which annotated region
         holds which nucleus of the merged dict, and the typed counts per region -- on rank 0 (None elsewhere and before the first slide),
         computed last, once after the merge; every entry of the dict gains "region" (the smallest region that holds it, or -1).
+        With "margin": [w_0, ..] (hover_net_amd/margins.py; widths in pixels of the processed slide) `self.regions` holds a
+        `regions.RegionMargins` instead -- that RegionCounts and the `margins.Margins`: per nucleus the nearest region's boundary
+        within the largest width, per region the typed counts by side and distance band -- and every entry also gains "margin".
         stain_norm: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py).  `run` fits ONCE per slide, from
         `slide.thumbnail(8)` (`fit_stain`): where a mask is given, only thumbnail pixels whose nearest mask cell is non-zero count
         (`stain.thumbnail_mask`: floor(y * mask_h / thumb_h), likewise for x).  `raw_prediction` then applies the slide's tables to every

@@ -44,6 +44,7 @@ OP_NBR_DENSITY = 17     # nucleus density maps over the same grid (density.py): 
 OP_NBR_PAIRS = 18       # typed pair counts by distance bin over the same grid (ripley.py): never part of a plan
 OP_NBR_REGIONS = 19     # point-in-polygon against annotated regions over the same grid (regions.py): never part of a plan
 OP_NBR_PAIRS_SIM = 20   # the pair counts of OP_NBR_PAIRS under a batch of random relabellings (ripley.py): never part of a plan
+OP_NBR_MARGINS = 21     # distance bands around the boundaries of annotated regions over the same grid (margins.py): never part of a plan
 
 
 @dataclass

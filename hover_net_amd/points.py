@@ -26,7 +26,8 @@ into one `PointSpecs` by each module's own `resolve`, in this order; a bad spec 
                 with "sims": S and an optional "seed" the `ripley.LabelSims` of the random-labelling test
     regions     {"regions": RegionSet | list | GeoJSON path} with an optional "scale" (the managers take {"dir": d} and read
                 `<d>/<name>.geojson`): the `regions.RegionCounts` of the dict against annotated polygons (`regions.of_info`); every
-                entry gains "region" (`regions.annotate`)
+                entry gains "region" (`regions.annotate`); with "margin": [w_0, ..] the result is a `regions.RegionMargins`, which
+                adds the `margins.Margins` -- the distance bands around every region's boundary -- and every entry gains "margin" too
 Radii, steps and windows are pixels of the processed image.  The first two ANNOTATE (`annotate`) and imply the instance dict;
 `post_proc.process` and `infer_tile.process_images` take only them.  The last three are SUMMARIES, one row each of the table
 `_SUMMARIES`: the name (which is the field of PointSpecs and of PointResults, the output sub-directory and the module that saves it) and
@@ -273,7 +274,7 @@ ARGS = ("neighbours", "clusters", "density", "ripley", "regions")
 
 class PointSpecs(collections.namedtuple("PointSpecs", ARGS)):
     """The five resolved arguments of the module docstring, None where off: (r, k), (r, m, types tuple | None), (r, step),
-    (radii tuple, window tuple | None) or (radii, window, sims, seed), a `regions.RegionSet`."""
+    (radii tuple, window tuple | None) or (radii, window, sims, seed), a `regions.RegionSet` or `regions.RegionSpec`."""
     __slots__ = ()
 
     @property

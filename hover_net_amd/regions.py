@@ -61,7 +61,10 @@ oracle culls nothing.
 
 The pipeline (`resolve`, `of_info`, `annotate`, `save`): `regions` = None or {"regions": RegionSet | list of regions | GeoJSON path or
 dict} with an optional "scale", which multiplies every vertex once, in float64, before canonicalisation (QuPath exports level-0
-pixels; the pipeline's points are pixels at proc_mag).
+pixels; the pipeline's points are pixels at proc_mag).  An optional "margin": [w_0, ..] (ascending widths in pixels of the processed
+image, margins.py) adds the distance bands around every region's boundary: `resolve` then returns a `RegionSpec` (the RegionSet and the
+widths), `of_info` of it a `RegionMargins` (the RegionCounts and the `margins.Margins`), `annotate` of that also sets "margin" on every
+entry and `save` adds the margin_* arrays.  Without the key everything is as it was.
 """
 import collections
 import json
@@ -76,6 +79,8 @@ ROW_POINTS = 256                # points per grid row that `cell_side` aims at: 
 _PAIRS = 1 << 22                # point-edge pairs per round of `regions_host`
 
 RegionCounts = collections.namedtuple("RegionCounts", "first hits count names area")
+RegionSpec = collections.namedtuple("RegionSpec", "regions widths")            # what `resolve` returns for a spec with "margin"
+RegionMargins = collections.namedtuple("RegionMargins", "counts margins")      # what `of_info` returns for a RegionSpec
 
 
 def max_entries(n_edges, ncy):
@@ -410,18 +415,29 @@ def regions(xy, types, rs, nr_types=None, device=None, cell=None):
 # ---- what a user reads ---------------------------------------------------------------------------
 def resolve(spec):
     """What a `regions` argument of the pipeline names: None -> None (off), {"regions": RegionSet | list of regions | GeoJSON dict or
-    path} with an optional "scale" -> RegionSet.  ValueError / TypeError otherwise, before any work."""
+    path} with an optional "scale" -> RegionSet; with a "margin": [w_0, ..] (margins.py's widths) -> RegionSpec(RegionSet, widths).
+    ValueError / TypeError otherwise, before any work (the widths before the regions are read)."""
     if spec is None:
         return None
-    if not isinstance(spec, dict) or "regions" not in spec or not set(spec) <= {"regions", "scale"}:
-        raise ValueError('regions=%r: None or {"regions": RegionSet | list | path} with an optional "scale"' % (spec,))
-    return as_regions(spec["regions"], spec.get("scale", 1.0))
+    if not isinstance(spec, dict) or "regions" not in spec or not set(spec) <= {"regions", "scale", "margin"}:
+        raise ValueError('regions=%r: None or {"regions": RegionSet | list | path} with an optional "scale" and an optional "margin"' % (spec,))
+    if "margin" not in spec:
+        return as_regions(spec["regions"], spec.get("scale", 1.0))
+    from . import margins as MG
+
+    widths = MG.check_widths(spec["margin"])
+    return RegionSpec(as_regions(spec["regions"], spec.get("scale", 1.0)), widths)
 
 
 def of_info(info, rs, nr_types, device=None):
     """The RegionCounts of an instance dict (`post_proc.process` / `process_images` / `WsiInference.run`): the centroids are the points,
     entry["type"] the types, as in `neighbours.annotate` (nr_types=None: untyped, T = 1); first / hits follow dict order.  An empty dict
-    gives zero counts.  device=None: `regions_host`."""
+    gives zero counts.  device=None: `regions_host`.  A RegionSpec for `rs` gives RegionMargins(that RegionCounts, the `margins.Margins`
+    of the same dict for the spec's widths)."""
+    if isinstance(rs, RegionSpec):
+        from . import margins as MG
+
+        return RegionMargins(of_info(info, rs.regions, nr_types, device), MG.of_info(info, rs.regions, rs.widths, nr_types, device))
     _check_set(rs)
     _, t = _check_counts(rs, None, 0, nr_types)
     if not info:
@@ -431,7 +447,19 @@ def of_info(info, rs, nr_types, device=None):
 
 
 def annotate(info, rc):
-    """Every entry of the dict that `rc` was made of gains "region": the int `first` of its nucleus (-1: in no region)."""
+    """Every entry of the dict that `rc` was made of gains "region": the int `first` of its nucleus (-1: in no region).  With a
+    RegionMargins every entry also gains "margin": {"region": the name of the nearest region within the largest width | None,
+    "distance": the distance to its boundary, negative inside it | None}."""
+    if isinstance(rc, RegionMargins):
+        from . import margins as MG
+
+        annotate(info, rc.counts)
+        m = rc.margins
+        if len(info) != m.near.shape[0]:
+            raise ValueError("%d entries, %d points in the Margins" % (len(info), m.near.shape[0]))
+        for entry, g, d in zip(info.values(), m.near.tolist(), MG.signed_distance(m).tolist()):
+            entry["margin"] = {"region": m.names[g] if g >= 0 else None, "distance": float(d) if g >= 0 else None}
+        return info
     if len(info) != rc.first.shape[0]:
         raise ValueError("%d entries, %d points in the RegionCounts" % (len(info), rc.first.shape[0]))
     for entry, f in zip(info.values(), rc.first.tolist()):
@@ -448,6 +476,11 @@ def per_area(rc):
 
 
 def save(path, rc):
-    """A RegionCounts as an .npz of its five fields (what the managers write under regions/)."""
+    """A RegionCounts as an .npz of its five fields (what the managers write under regions/); a RegionMargins adds margin_widths,
+    margin_count, margin_near, margin_d2 and margin_inside."""
+    extra = {}
+    if isinstance(rc, RegionMargins):
+        rc, m = rc
+        extra = dict(margin_widths=np.asarray(m.widths, np.float64), margin_count=m.count, margin_near=m.near, margin_d2=m.near_d2, margin_inside=m.near_inside)
     np.savez_compressed(path, count=rc.count, first=rc.first, hits=rc.hits, names=np.array(list(rc.names), dtype=np.str_).reshape(-1),
-                        area=np.asarray(rc.area, np.float64))
+                        area=np.asarray(rc.area, np.float64), **extra)

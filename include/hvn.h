@@ -41,7 +41,7 @@ typedef struct hvn_view {
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
        HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19,
-       HVN_OP_NBR_PAIRS_SIM = 20 };
+       HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -217,6 +217,40 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: a null pointer, out / edge_region / rows not 4-byte or edges / table / workspace not 8-byte aligned, batch != 1,
  *           N < 1, T outside 1..16, G < 1, E < 1, M < 1, kh or kw < 1.  HVN_E_SIZE: G > 4096, E > 2^22, M > 8 E + kh, N > 2^26, kh or
  *           kw > 4096 or kh * kw > 2^22, x2.sn too small.
+ *     NBR_MARGINS    the points by distance to the BOUNDARY of G annotated regions, in B bands: per point the nearest region within the
+ *           largest width, the squared distance and the side; per (region, side, band, type) the ring counts (hover_net_amd/margins.py
+ *           holds the definition; csrc/hvn_margins.hip).  Runs after NBR_GRID on the same stream and reads the workspace as that op left
+ *           it for the same N, kh, kw and table (x.base is not read; table[3] is not read either); x.h, kh, kw, w, x2.base and x2.sn are
+ *           the shared fields above.  The extra tables take fields the family leaves free: cout = T in 1..16; `_rsv` = G in 1..4096;
+ *           cout2 = B in 1..16; w2 = float64 squared widths [B], ascending, on the device (8-byte aligned; read as doubles whatever the
+ *           pointer's declared type, as w is); bias = float64 segments [S][8] on the device (8-byte aligned; read as doubles likewise):
+ *           (ax, ay, bx, by) with (ay, ax) <= (by, bx), EVERY ring edge, horizontal ones included, then the segment's box (x0, y0, x1,
+ *           y1) = (min(ax, bx) - W, ay - W, max(ax, bx) + W, by + W) as the caller rounded it, W the largest width; res.base = int32
+ *           seg_region [S] (4-byte aligned), ascending, and res.h = S in 1..2^22; y2.base = int32 rows (4-byte aligned): row_start
+ *           [kh + 1] followed by the segment numbers of the row lists, and y2.sn = M, the lists' total length, in 0..8 S + kh: the
+ *           segments of grid row k are rows[kh + 1 + j] for row_start[k] <= j < row_start[k + 1], and the caller lists a segment in
+ *           every row from that of y0 to that of y1 of its box (NBR_GRID's row formula, which is monotone; a segment that no point can be
+ *           near or cross may be left out), the segments of one region adjacent and the regions ascending (the library does not check
+ *           that); y.base = the output (8-byte aligned) of y.sn BYTES >= 16 N + 8 G B T: float64 near_d2 [N], then int32 near [N],
+ *           near_inside [N], hist [G][2][B][T].  Point (px, py) crosses a segment by NBR_REGIONS' rule and is inside region g when it
+ *           crosses an odd number of g's segments.  It is in a segment's box when x0 <= px <= x1 and y0 <= py <= y1; then, in float64,
+ *           one rounding per operation, no fused multiply-add, with ux = bx - ax, uy = by - ay, vx = px - ax, vy = py - ay, dot =
+ *           ux * vx + uy * vy, len2 = ux * ux + uy * uy: d2 = vx * vx + vy * vy if dot <= 0, (px - bx) * (px - bx) + (py - by) * (py -
+ *           by) if dot >= len2, else (c * c) / len2 with c = ux * vy - uy * vx; the segment is near the point when d2 <= w2[B - 1], and
+ *           dmin2(i, g) is the smallest d2 over g's segments near point i.  near[i] = the g with the smallest dmin2, ties to the smallest
+ *           g, or -1; near_d2[i] = that dmin2 or +inf; near_inside[i] = 1 | 0 for that region or -1; hist[g][side][k][t] = the points of
+ *           type t, inside (side 1) or outside (side 0) g, for which k is the smallest index with dmin2 <= w2[k] (the RING counts: the
+ *           caller forms running sums over k); i is a position in NBR_GRID's x.  A type outside [0, T) is counted nowhere and the point
+ *           still gets near; a region id outside [0, G) is committed nowhere.  EVERY element of the output is written, whatever it held
+ *           before: the op clears hist itself, in stream order.  M = 0 is run like any other list: all -1 / +inf / 0.  stride != 0
+ *           selects the kernel form that does not cull the staged segments by x (the same numbers; tools/margins_bench.py times the
+ *           two against each other).  Integer sums and
+ *           minima under a total order (a 32-bit LDS histogram per region run, flushed into global atomics): a function of the inputs
+ *           alone.  Row starts are clamped to [0, M], segment numbers to [0, S), the walk of a workgroup's rows ends after 256 rounds:
+ *           tables or a workspace the caller did not fill give wrong numbers, no access outside the arrays and no loop without an end.
+ *           HVN_E_ARG: a null pointer, seg_region / rows not 4-byte or segments / widths / out / table / workspace not 8-byte aligned,
+ *           batch != 1, N < 1, B or T outside 1..16, G < 1, S < 1, M < 0, kh or kw < 1.  HVN_E_SIZE: G > 4096, S > 2^22, M > 8 S + kh,
+ *           y.sn too small, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn too small.
  *     NBR_PAIRS_SIM  the border-corrected counts of NBR_PAIRS under a BATCH of SB random relabellings of the points: the integers behind
  *           the random-labelling envelopes of Ripley's cross-type K (hover_net_amd/ripley.py holds the definition, `sims_host`;
  *           csrc/hvn_pairs_sim.hip).  Runs after NBR_GRID on the same stream and reads the workspace as that op left it for the same N,
