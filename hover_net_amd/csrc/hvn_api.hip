@@ -594,6 +594,33 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if (((uintptr_t)a.seg | (uintptr_t)a.w2 | (uintptr_t)a.out) & 7) return hvn_fail(HVN_E_ARG, "nbr_margins: misaligned segment table, widths or out (8)");
         return hvn_launch_status(hvn_launch_nbr_margins(a, s), "nbr_margins");
     }
+    case HVN_OP_NBR_GRAPH: {
+        NbrGraphArgs a;
+        a.table = (const double *)op->w;
+        a.workspace = op->x2.base;
+        a.fill = op->_rsv;
+        a.degree = a.fill ? nullptr : (int *)op->y.base;
+        a.indices = a.fill ? (int *)op->y.base : nullptr;
+        a.indptr = a.fill ? (const long long *)op->y2.base : nullptr;
+        a.first = a.fill ? nullptr : (int *)op->y2.base;
+        a.width = op->stride;
+        a.E = (long long)op->y.sn;
+        a.N = op->x.h; a.ncy = op->kh; a.ncx = op->kw;
+        if (a.fill != 0 && a.fill != 1) return hvn_fail(HVN_E_ARG, "nbr_graph: `_rsv` = %d is no mode (0: count, 1: fill)", a.fill);
+        if (!a.workspace) return hvn_fail(HVN_E_ARG, "nbr_graph: null pointer");
+        if (!a.fill && !a.degree) return hvn_fail(HVN_E_ARG, "nbr_graph: null degree (y) of the count pass");
+        if (a.first && (a.width < 1 || a.width > HVN_NBR_GRAPH_MAX_WIDTH))
+            return hvn_fail(HVN_E_ARG, "nbr_graph: a table (y2) of %d slots per point outside 1..64 (stride)", a.width);
+        if (a.fill && !a.indices) return hvn_fail(HVN_E_ARG, "nbr_graph: null indices (y) of the fill pass");
+        if (a.fill && !a.indptr) return hvn_fail(HVN_E_ARG, "nbr_graph: null indptr (y2) of the fill pass");
+        if (a.fill && a.E < 1) return hvn_fail(HVN_E_ARG, "nbr_graph: indices of %ld entries, fewer than one", (long)a.E);
+        if (a.fill && a.E > HVN_NBR_GRAPH_MAX_E) return hvn_fail(HVN_E_SIZE, "nbr_graph: indices of %ld entries reach 2^31", (long)a.E);
+        if (int rc = nbr_common("nbr_graph", op, batch)) return rc;
+        if ((uintptr_t)op->y.base & 3) return hvn_fail(HVN_E_ARG, "nbr_graph: misaligned degree or indices (4)");
+        if (a.fill && ((uintptr_t)a.indptr & 7)) return hvn_fail(HVN_E_ARG, "nbr_graph: misaligned indptr (8)");
+        if ((uintptr_t)a.first & 3) return hvn_fail(HVN_E_ARG, "nbr_graph: misaligned table (y2) of the count pass (4)");
+        return hvn_launch_status(hvn_launch_nbr_graph(a, s), "nbr_graph");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

@@ -368,6 +368,23 @@ struct NbrMarginsArgs {
     int no_cull;                // != 0: the kernel form without the x-cull of the staged tile (same numbers; for measurements)
 };
 int hvn_launch_nbr_margins(const NbrMarginsArgs &a, hipStream_t stream);
+// hvn_graph.hip: the Gabriel edges of length <= r among the points, as a CSR graph in two passes (hover_net_amd/graph.py)
+#define HVN_NBR_GRAPH_LIST_CAP 512               // neighbours of one point that a wave keeps on chip; above it the slower exact path runs
+#define HVN_NBR_GRAPH_MAX_E ((1L << 31) - 1)
+#define HVN_NBR_GRAPH_MAX_WIDTH 64
+struct NbrGraphArgs {
+    const double *table;        // {x0, y0, c, r2}, as for the grid
+    void *workspace;            // as hvn_launch_nbr_grid left it for the same N, ncy, ncx
+    int *degree;                // count: [N] by position; every row with a point is written
+    int *first;                 // count: NULL or [N][width] by position: the first `width` edges of every row as the wave finds them
+    const long long *indptr;    // fill: [N + 1] by position, the exclusive running sum of degree
+    int *indices;               // fill: [E]; row i's positions in any order
+    long long E;                // fill: the length of indices
+    int N, ncy, ncx;
+    int width;                  // count with `first`: 1..HVN_NBR_GRAPH_MAX_WIDTH
+    int fill;                   // 0: count, 1: fill
+};
+int hvn_launch_nbr_graph(const NbrGraphArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

@@ -147,20 +147,32 @@ def edges(knn):
 
 def resolve(spec):
     """What a `neighbours` argument of the pipeline names: None -> None (off), {"radius": r, "k": k} -> (r, k), in pixels of the
-    processed image.  ValueError / TypeError otherwise, before any work."""
+    processed image; with "graph": "gabriel" (graph.py: the cell graph at the same radius) -> (r, k, "gabriel").  ValueError /
+    TypeError otherwise, before any work."""
     if spec is None:
         return None
-    if not isinstance(spec, dict) or set(spec) != {"radius", "k"}:
-        raise ValueError('neighbours=%r: None or {"radius": r, "k": k}' % (spec,))
-    return P.check_radius(spec["radius"]), _check_k(spec["k"])
+    if not isinstance(spec, dict) or set(spec) - {"graph"} != {"radius", "k"}:
+        raise ValueError('neighbours=%r: None or {"radius": r, "k": k} with an optional "graph": "gabriel"' % (spec,))
+    rk = P.check_radius(spec["radius"]), _check_k(spec["k"])
+    if "graph" not in spec:
+        return rk
+    from . import graph as GR
+
+    return rk + (GR.check_kind(spec["graph"]),)
 
 
-def annotate(info, radius, k, nr_types, device=None):
+def annotate(info, radius, k, nr_types, device=None, graph=None):
     """Adds "neighbours" to every entry of an instance dict (`post_proc.process` / `WsiInference.run`) and returns the dict.
     Positions follow dict order; the centroids are the points, entry["type"] the types (nr_types=None: untyped, one column).
     entry["neighbours"] = {"count": [T ints], "knn": [labels], "knn_dist": [floats], "nearest_of_type": [label | None],
     "nearest_of_type_dist": [float | None]}: instance labels instead of positions, the padding of knn removed, plain Python values
-    (JSON-serialisable as they are).  An empty dict is returned unchanged.  device=None: `query_host`."""
+    (JSON-serialisable as they are).  graph="gabriel" adds two keys to that dict: "graph": [labels], the nucleus's neighbours in the
+    cell graph of graph.py at the same radius, in ascending (d2, j), and "graph_dist": [floats], their distances in that order.  An
+    empty dict is returned unchanged.  device=None: `query_host` (and `gabriel_host`)."""
+    if graph is not None:
+        from . import graph as GR
+
+        GR.check_kind(graph)
     if not info:
         return info
     labels, xy, types = P.from_info(info, nr_types)
@@ -173,4 +185,10 @@ def annotate(info, radius, k, nr_types, device=None):
         info[lab]["neighbours"] = {"count": count[i], "knn": [labels[j] for j in knn[i][:m]], "knn_dist": kd[i][:m],
                                    "nearest_of_type": [labels[j] if j >= 0 else None for j in near[i]],
                                    "nearest_of_type_dist": [d if j >= 0 else None for j, d in zip(near[i], nd[i])]}
+    if graph is not None:
+        g = GR.gabriel(xy, radius, device)
+        ptr, idx, dist = g.indptr.tolist(), g.indices.tolist(), GR.lengths(xy, g).tolist()
+        for i, lab in enumerate(labels):
+            info[lab]["neighbours"]["graph"] = [labels[j] for j in idx[ptr[i]:ptr[i + 1]]]
+            info[lab]["neighbours"]["graph_dist"] = dist[ptr[i]:ptr[i + 1]]
     return info

@@ -41,7 +41,7 @@ typedef struct hvn_view {
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
        HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19,
-       HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21 };
+       HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21, HVN_OP_NBR_GRAPH = 22 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -281,6 +281,31 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: a null pointer (types excepted), out / keys / a table / workspace not 8-byte or types / labels not 4-byte
  *           aligned, batch != 1, N < 1, T outside 1..16, R outside 1..32, SB outside 1..32, stride outside 0..2, kh or kw < 1.  HVN_E_SIZE: T T R > 4096,
  *           the histograms and labels above 143360 bytes of LDS, y2.sn too small, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
+ *           too small.
+ *     NBR_GRAPH      the cell graph of the points: the Gabriel edges of length <= r, as a CSR graph in two passes of one op
+ *           (hover_net_amd/graph.py holds the definition; csrc/hvn_graph.hip).  Runs after NBR_GRID on the same stream and reads the
+ *           workspace as that op left it for the same N, kh, kw and table (x.base is not read); x.h, kh, kw, w, x2.base and x2.sn are
+ *           the shared fields above.  With the neighbour relation of NBR_QUERY (j != i and d2 <= r2) and dot(i, j, k) = ((xi - xk) *
+ *           (xj - xk)) + ((yi - yk) * (yj - yk)) in float64, one rounding per operation and no fused multiply-add: k blocks (i, j)
+ *           when k != i, k != j, k is a neighbour of i AND of j and dot(i, j, k) < 0; (i, j) is an edge when j is a neighbour of i and
+ *           no k blocks it.  The relation is symmetric.  `_rsv` = the mode.  0, COUNT: y.base = int32 degree [N] (4-byte aligned),
+ *           degree[i] = the number of edges of i, i a position in NBR_GRID's x; y.sn is not read; y2.base = NULL, or an int32 table
+ *           first [N][W] (4-byte aligned) with W = `stride` in 1..64 (not read without the table): the positions of the first
+ *           min(degree[i], W) graph neighbours of i that the kernel finds go to first[i][0 ..), the rest of the row is left as it
+ *           was; a caller whose largest degree is at most W has the whole graph after this pass.  1, FILL: y2.base = int64
+ *           indptr [N + 1] (8-byte aligned), the exclusive running sum of degree that the caller formed; y.base = int32 indices [E]
+ *           (4-byte aligned) and y.sn = E in [1, 2^31): the positions of i's graph neighbours are written to indices[indptr[i] ..
+ *           indptr[i + 1]); `stride` is not read.  Rows of the table and of indices are in NO particular order (the caller sorts a
+ *           row; graph.py orders it by (d2, j)), so that no output depends on the order of the points inside a cell.  There is no cap
+ *           on a degree or on the size of a neighbourhood: a wave keeps up to 512 neighbours of its point in LDS, and above that a
+ *           slower path walks the candidate runs in global memory and gives the same integers.  Loops are bounded by cell_start
+ *           values clamped to [0, N]; a point whose position in the workspace is outside [0, N) writes nothing; every store of the
+ *           fill pass is bounded by its row's own end and by E, every store into the table by its row's W slots: a workspace NBR_GRID
+ *           did not fill or an indptr that is not the count pass's gives wrong numbers, no access outside the arrays and no loop
+ *           without an end.
+ *           HVN_E_ARG: `_rsv` outside 0..1, a null pointer (degree in count; indices or indptr in fill), a table with W outside
+ *           1..64, E < 1 in fill, degree / indices / the table not 4-byte or indptr / the grid's table / workspace not 8-byte
+ *           aligned, batch != 1, N < 1, kh or kw < 1.  HVN_E_SIZE: E >= 2^31, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
  *           too small.
  */
 typedef struct hvn_op {
