@@ -621,6 +621,39 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.first & 3) return hvn_fail(HVN_E_ARG, "nbr_graph: misaligned table (y2) of the count pass (4)");
         return hvn_launch_status(hvn_launch_nbr_graph(a, s), "nbr_graph");
     }
+    case HVN_OP_NBR_FOREST: {
+        NbrForestArgs a;
+        a.xy = (const double *)op->x.base;
+        a.indptr = (const long long *)op->w;
+        a.indices = (const int *)op->res.base;
+        a.component = (int *)op->y.base;
+        a.tree = (unsigned char *)op->y2.base;
+        a.workspace = op->x2.base;
+        a.E = (long long)op->res.sn;
+        a.N = op->x.h; a.phase = op->_rsv; a.round = op->stride; a.no_filter = op->cout != 0;
+        if (a.phase < 0 || a.phase > 3) return hvn_fail(HVN_E_ARG, "nbr_forest: `_rsv` = %d is no phase (0: all, 1: start, 2: one round, 3: end)", a.phase);
+        if (a.phase == 2 && (a.round < 0 || a.round >= HVN_NBR_FOREST_MAX_ROUNDS))
+            return hvn_fail(HVN_E_ARG, "nbr_forest: round %d outside 0..25 (stride)", a.round);
+        if (!a.xy) return hvn_fail(HVN_E_ARG, "nbr_forest: null xy (x)");
+        if (!a.indptr) return hvn_fail(HVN_E_ARG, "nbr_forest: null indptr (w)");
+        if (!a.component) return hvn_fail(HVN_E_ARG, "nbr_forest: null component (y)");
+        if (!a.workspace) return hvn_fail(HVN_E_ARG, "nbr_forest: null workspace (x2)");
+        if (a.N < 1) return hvn_fail(HVN_E_ARG, "nbr_forest: N = %d, fewer than one point", a.N);
+        if (a.N > HVN_NBR_MAX_N) return hvn_fail(HVN_E_SIZE, "nbr_forest: N = %d above 2^26", a.N);
+        if (a.E < 0) return hvn_fail(HVN_E_ARG, "nbr_forest: indices of %ld entries, fewer than none", (long)a.E);
+        if (a.E > HVN_NBR_FOREST_MAX_E) return hvn_fail(HVN_E_SIZE, "nbr_forest: indices of %ld entries reach 2^31", (long)a.E);
+        if (a.E > 0 && !a.indices) return hvn_fail(HVN_E_ARG, "nbr_forest: null indices (res) of %ld entries", (long)a.E);
+        if (a.E > 0 && !a.tree) return hvn_fail(HVN_E_ARG, "nbr_forest: null tree (y2) of %ld entries", (long)a.E);
+        if (batch != 1) return hvn_fail(HVN_E_ARG, "nbr_forest: batch %d, not 1", batch);
+        if ((long)op->x2.sn < HVN_NBR_FOREST_WORKSPACE_BYTES(a.N))
+            return hvn_fail(HVN_E_SIZE, "nbr_forest: workspace of %ld bytes, %ld needed", (long)op->x2.sn, HVN_NBR_FOREST_WORKSPACE_BYTES(a.N));
+        if ((uintptr_t)a.xy & 7) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned xy (8)");
+        if ((uintptr_t)a.indptr & 7) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned indptr (8)");
+        if ((uintptr_t)a.workspace & 7) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned workspace (8)");
+        if ((uintptr_t)a.indices & 3) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned indices (4)");
+        if ((uintptr_t)a.component & 3) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned component (4)");
+        return hvn_launch_status(hvn_launch_nbr_forest(a, s), "nbr_forest");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

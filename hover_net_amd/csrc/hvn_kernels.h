@@ -385,6 +385,27 @@ struct NbrGraphArgs {
     int fill;                   // 0: count, 1: fill
 };
 int hvn_launch_nbr_graph(const NbrGraphArgs &a, hipStream_t stream);
+// hvn_forest.hip: the minimum spanning forest and the connected components of a CSR graph over the points, Boruvka rounds
+// (hover_net_amd/forest.py).  The one workspace, 8-byte aligned, by position: best_d2 and best_pair (uint64 [N] each), parent, comp and
+// minpos (int32 [N] each), then 64 control words: hooks[32], the rounds word, found[26]
+#define HVN_NBR_FOREST_MAX_ROUNDS 26             // max(1, ceil(log2 N)) for N <= 2^26
+#define HVN_NBR_FOREST_MAX_E ((1L << 31) - 1)
+#define HVN_NBR_FOREST_WORKSPACE_BYTES(N) (28L * (N) + 256)
+#define HVN_NBR_FOREST_ROUNDS_AT(N) (28L * (N) + 128)       // the byte offset of the int32 that counts the rounds that hooked anything
+struct NbrForestArgs {
+    const double *xy;           // [N][2] = (x, y) by position
+    const long long *indptr;    // [N + 1]
+    const int *indices;         // [E], NULL iff E = 0
+    int *component;             // [N] out: the smallest position of i's connected component
+    unsigned char *tree;        // [E] out: 1 for both directed entries of a forest edge, else 0; every element is written
+    void *workspace;            // HVN_NBR_FOREST_WORKSPACE_BYTES(N); every word read is written first
+    long long E;
+    int N;
+    int phase;                  // 0: the whole forest; 1: the start only; 2: round `round` only; 3: the end only (forest.py times them apart)
+    int round;                  // phase 2: 0..HVN_NBR_FOREST_MAX_ROUNDS - 1 (not read otherwise)
+    int no_filter;              // != 0: the kernel form whose atomicMin is not preceded by a read of the word (same numbers; for measurements)
+};
+int hvn_launch_nbr_forest(const NbrForestArgs &a, hipStream_t stream);
 
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)

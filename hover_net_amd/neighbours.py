@@ -147,28 +147,36 @@ def edges(knn):
 
 def resolve(spec):
     """What a `neighbours` argument of the pipeline names: None -> None (off), {"radius": r, "k": k} -> (r, k), in pixels of the
-    processed image; with "graph": "gabriel" (graph.py: the cell graph at the same radius) -> (r, k, "gabriel").  ValueError /
-    TypeError otherwise, before any work."""
+    processed image; with "graph": "gabriel" (graph.py: the cell graph at the same radius) -> (r, k, "gabriel"); with "forest": True
+    next to it (forest.py: that graph's minimum spanning forest and components) -> (r, k, "gabriel", True).  ValueError / TypeError
+    otherwise, before any work."""
     if spec is None:
         return None
-    if not isinstance(spec, dict) or set(spec) - {"graph"} != {"radius", "k"}:
+    if not isinstance(spec, dict) or set(spec) - {"graph", "forest"} != {"radius", "k"}:
         raise ValueError('neighbours=%r: None or {"radius": r, "k": k} with an optional "graph": "gabriel"' % (spec,))
+    if "forest" in spec and (spec["forest"] is not True or "graph" not in spec):
+        raise ValueError('neighbours=%r: "forest" is True or absent, and needs "graph"' % (spec,))
     rk = P.check_radius(spec["radius"]), _check_k(spec["k"])
     if "graph" not in spec:
         return rk
     from . import graph as GR
 
-    return rk + (GR.check_kind(spec["graph"]),)
+    return rk + (GR.check_kind(spec["graph"]),) + ((True,) if "forest" in spec else ())
 
 
-def annotate(info, radius, k, nr_types, device=None, graph=None):
+def annotate(info, radius, k, nr_types, device=None, graph=None, forest=False):
     """Adds "neighbours" to every entry of an instance dict (`post_proc.process` / `WsiInference.run`) and returns the dict.
     Positions follow dict order; the centroids are the points, entry["type"] the types (nr_types=None: untyped, one column).
     entry["neighbours"] = {"count": [T ints], "knn": [labels], "knn_dist": [floats], "nearest_of_type": [label | None],
     "nearest_of_type_dist": [float | None]}: instance labels instead of positions, the padding of knn removed, plain Python values
     (JSON-serialisable as they are).  graph="gabriel" adds two keys to that dict: "graph": [labels], the nucleus's neighbours in the
-    cell graph of graph.py at the same radius, in ascending (d2, j), and "graph_dist": [floats], their distances in that order.  An
-    empty dict is returned unchanged.  device=None: `query_host` (and `gabriel_host`)."""
+    cell graph of graph.py at the same radius, in ascending (d2, j), and "graph_dist": [floats], their distances in that order.
+    forest=True, which needs `graph`, adds two more (forest.py): "component": the instance label of the smallest position in the
+    nucleus's connected component of that graph, and "tree": [labels], the part of "graph" that lies in the graph's minimum spanning
+    forest, in the same order.  The graph is computed once; on a device the forest runs on the graph's own buffers.  An empty dict is
+    returned unchanged.  device=None: `query_host` (and `gabriel_host`, `forest_host`)."""
+    if forest is not False and (forest is not True or graph is None):
+        raise ValueError("forest=%r: True or False, and True needs `graph`" % (forest,))
     if graph is not None:
         from . import graph as GR
 
@@ -186,9 +194,23 @@ def annotate(info, radius, k, nr_types, device=None, graph=None):
                                    "nearest_of_type": [labels[j] if j >= 0 else None for j in near[i]],
                                    "nearest_of_type_dist": [d if j >= 0 else None for j, d in zip(near[i], nd[i])]}
     if graph is not None:
-        g = GR.gabriel(xy, radius, device)
+        if forest:
+            from . import forest as FO
+
+            g, f = FO.of_points(xy, radius, device)
+        else:
+            g = GR.gabriel(xy, radius, device)
         ptr, idx, dist = g.indptr.tolist(), g.indices.tolist(), GR.lengths(xy, g).tolist()
         for i, lab in enumerate(labels):
             info[lab]["neighbours"]["graph"] = [labels[j] for j in idx[ptr[i]:ptr[i + 1]]]
             info[lab]["neighbours"]["graph_dist"] = dist[ptr[i]:ptr[i + 1]]
+        if forest:
+            n = len(labels)
+            rows, cols = GR.edge_index(g)
+            e = f.edges.astype(np.int64)
+            in_tree = np.isin(np.minimum(rows, cols) * n + np.maximum(rows, cols), e[:, 0] * n + e[:, 1]).tolist()
+            comp = f.component.tolist()
+            for i, lab in enumerate(labels):
+                info[lab]["neighbours"]["component"] = labels[comp[i]]
+                info[lab]["neighbours"]["tree"] = [labels[idx[p]] for p in range(ptr[i], ptr[i + 1]) if in_tree[p]]
     return info

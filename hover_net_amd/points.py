@@ -19,7 +19,9 @@ the second op and reads them back (`result`).
 The pipeline (`ARGS`, `resolve_specs`, `annotate`, `summaries`, `save_results`, `output_dirs`).  Five arguments, None = off, resolved
 into one `PointSpecs` by each module's own `resolve`, in this order; a bad spec is refused there, before any work:
     neighbours  {"radius": r, "k": k}: every entry of the instance dict gains "neighbours" (`neighbours.annotate`); with "graph":
-                "gabriel" that entry also lists the nucleus's neighbours in the cell graph at the same radius (graph.py)
+                "gabriel" that entry also lists the nucleus's neighbours in the cell graph at the same radius (graph.py), and with
+                "forest": True next to it the nucleus's component of that graph and its neighbours in the graph's minimum spanning
+                forest (forest.py)
     clusters    {"radius": r, "min_pts": m} with an optional "types": [ints], which needs nr_types: every entry gains "cluster"
                 (`clusters.annotate`)
     density     {"radius": r, "step": s}, `step` an integer >= 1: a `density.DensityMap` of the dict over the image (`density.of_info`)
@@ -274,7 +276,7 @@ ARGS = ("neighbours", "clusters", "density", "ripley", "regions")
 
 
 class PointSpecs(collections.namedtuple("PointSpecs", ARGS)):
-    """The five resolved arguments of the module docstring, None where off: (r, k) or (r, k, "gabriel"), (r, m, types tuple | None), (r, step),
+    """The five resolved arguments of the module docstring, None where off: (r, k), (r, k, "gabriel") or (r, k, "gabriel", True), (r, m, types tuple | None), (r, step),
     (radii tuple, window tuple | None) or (radii, window, sims, seed), a `regions.RegionSet` or `regions.RegionSpec`."""
     __slots__ = ()
 
@@ -310,7 +312,8 @@ def annotate(info, specs, nr_types, device):
     from . import neighbours as NB
 
     if specs.neighbours is not None:
-        NB.annotate(info, specs.neighbours[0], specs.neighbours[1], nr_types, device=_device(device), graph=specs.neighbours[2] if len(specs.neighbours) == 3 else None)
+        NB.annotate(info, specs.neighbours[0], specs.neighbours[1], nr_types, device=_device(device), graph=specs.neighbours[2] if len(specs.neighbours) >= 3 else None,
+                    forest=len(specs.neighbours) == 4)
     if specs.clusters is not None:
         CL.annotate(info, specs.clusters[0], specs.clusters[1], nr_types, specs.clusters[2], device=_device(device))
     return info

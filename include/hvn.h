@@ -41,7 +41,8 @@ typedef struct hvn_view {
 enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN_OP_PREDMAP = 5, HVN_OP_WINO_IN = 6, HVN_OP_WINO_OUT = 7, HVN_OP_CHAIN = 8, HVN_OP_VIEW = 9, HVN_OP_TTA = 10,
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
        HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19,
-       HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21, HVN_OP_NBR_GRAPH = 22 };
+       HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21, HVN_OP_NBR_GRAPH = 22,
+       HVN_OP_NBR_FOREST = 23 };
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -307,6 +308,29 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           1..64, E < 1 in fill, degree / indices / the table not 4-byte or indptr / the grid's table / workspace not 8-byte
  *           aligned, batch != 1, N < 1, kh or kw < 1.  HVN_E_SIZE: E >= 2^31, N > 2^26, kh or kw > 4096 or kh * kw > 2^22, x2.sn
  *           too small.
+ *     NBR_FOREST     the minimum spanning forest and the connected components of a symmetric CSR graph over the points, by Boruvka
+ *           rounds (hover_net_amd/forest.py holds the definition; csrc/hvn_forest.hip).  It needs no grid and does not read NBR_GRID's
+ *           workspace: x.base = float64 [N][2] = (x, y) by position (8-byte aligned), x.h = N in [1, 2^26]; w = int64 indptr [N + 1]
+ *           on the device (8-byte aligned; read as 64-bit integers whatever the pointer's declared type); res.base = int32 indices [E]
+ *           (4-byte aligned) and res.sn = E in [0, 2^31), NULL iff E = 0: the graph as NBR_GRAPH's caller holds it, rows in any order,
+ *           symmetric, without self-loops and without a position twice in a row (the library does not check that); y.base = int32
+ *           component [N] (4-byte aligned); y2.base = uint8 tree [E], NULL iff E = 0; x2.base = a workspace of the op's own (8-byte
+ *           aligned) of x2.sn BYTES >= 28 N + 256.  The op writes every word of it that it reads.  The key of an undirected edge {i, j}
+ *           is (d2(i, j), min(i, j), max(i, j)), compared lexicographically, d2 as NBR_QUERY forms it; {i, j} is in the forest when its
+ *           ends are not connected by edges of strictly smaller key.  tree[e] = 1 for BOTH directed entries of a forest edge and 0 for
+ *           every other entry; component[i] = the smallest position in i's connected component.  EVERY element of both is written,
+ *           whatever it held before.  The int32 at byte 28 N + 128 of the workspace holds the number of rounds that joined anything.
+ *           `_rsv` = 0 is that op, in stream order and without a readback: max(1, ceil(log2 N)) rounds of four launches, of which those
+ *           after a round that joined nothing return at once.  1, 2 and 3 are its parts, so that they can be timed apart and a caller can
+ *           read the workspace between them (tools/forest_bench.py): 1 the start, 2 the one round `stride` in 0..25 (the int32 at byte
+ *           28 N + 4 stride of the workspace then counts what that round joined), 3 the end.  cout != 0 selects the kernel form whose
+ *           atomic minima are not preceded by a read of the word (the same numbers).  kh, kw and every other field are not read.
+ *           Integer minima under a strict total order: a function of the inputs alone.  Every indptr value is clamped into [0, E], an
+ *           indices entry outside [0, N) is skipped, the walks are bounded by a row's length, by N and by the number of rounds: a graph
+ *           that is not symmetric gives wrong numbers, no access outside the arrays and no loop without an end.
+ *           HVN_E_ARG: `_rsv` outside 0..3, `stride` outside 0..25 with `_rsv` = 2, a null pointer (xy, indptr, component, the workspace;
+ *           indices or tree with E > 0), N < 1, E < 0, batch != 1, xy / indptr / workspace not 8-byte or indices / component not 4-byte
+ *           aligned.  HVN_E_SIZE: N > 2^26, E >= 2^31, x2.sn too small.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
