@@ -15,6 +15,9 @@ static_assert(sizeof(hvn_pack_desc) == sizeof(PackArgs) && offsetof(hvn_pack_des
 
 static inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 static inline bool view_ok(const hvn_view &v) { return v.base && al16(v.base) && ((v.sn | v.sy | v.sx) & 3) == 0 && (v.c & 3) == 0; }
+// The kernels of BN, UPADD_BWD and HEAD_BWD take N, H, W, C from ONE view and walk the others with them: every other view must
+// have the extent that view implies (include/hvn.h, "extent rules"), or the kernel would read and write outside it.
+static inline bool same_extent(const hvn_view &v, int h, int w, int c) { return v.h == h && v.w == w && v.c == c; }
 
 // The arguments of the three op kinds that end in a cross-workgroup sum, filled from the descriptor (shared by the launch path and by
 // hvn_train_workspace_bytes, so that both see the same launch shape).
@@ -51,6 +54,51 @@ static int head_bwd_args(const hvn_top *t, int batch, HeadBwdArgs &a)
     a.dl = (const float *)t->p[0]; a.w = (const float *)t->p[1]; a.dw = (float *)t->p[2]; a.db = (float *)t->p[3];
     a.N = batch; a.H = t->x.h; a.W = t->x.w; a.Cout = t->cout;
     return 0;
+}
+
+// The extent rules of include/hvn.h for one op.  hvn_run_train_plan_ws applies them to EVERY op of the list before it launches the
+// first one, so that a list with a bad descriptor anywhere leaves the device untouched.
+static int extent_rules(const hvn_top *t, int batch)
+{
+    switch (t->kind) {
+    case HVN_T_BN_FWD:
+    case HVN_T_BN_BWD: {
+        const int h = t->x.h, w = t->x.w, c = t->x.c;
+        if (h <= 0 || w <= 0 || c <= 0) return hvn_fail(HVN_E_ARG, "bn: z has an empty extent (h = %d, w = %d, c = %d)", h, w, c);
+        if (!same_extent(t->y, h, w, c))
+            return hvn_fail(HVN_E_ARG, "bn: the a view's extent (%d, %d, %d) differs from z's (%d, %d, %d)", t->y.h, t->y.w, t->y.c, h, w, c);
+        if (t->kind == HVN_T_BN_FWD) {
+            if ((long)batch * h * w < 2)
+                return hvn_fail(HVN_E_ARG, "bn forward: one value per channel has no unbiased variance (batch * h * w = %ld < 2)", (long)batch * h * w);
+            return HVN_OK;
+        }
+        if (!same_extent(t->dy, h, w, c))
+            return hvn_fail(HVN_E_ARG, "bn backward: the da view's extent (%d, %d, %d) differs from z's (%d, %d, %d)", t->dy.h, t->dy.w, t->dy.c, h, w, c);
+        if (t->dx.base && !same_extent(t->dx, h, w, c))
+            return hvn_fail(HVN_E_ARG, "bn backward: the dz view's extent (%d, %d, %d) differs from z's (%d, %d, %d)", t->dx.h, t->dx.w, t->dx.c, h, w, c);
+        return HVN_OK;
+    }
+    case HVN_T_UPADD_BWD: {
+        const int h = t->dy.h, w = t->dy.w, c = t->dy.c;
+        if (!t->dx.base && !t->y.base) return hvn_fail(HVN_E_ARG, "upadd backward: both dlo and dskip are NULL");
+        if (h <= 0 || w <= 0 || c <= 0 || (h | w) & 1) return hvn_fail(HVN_E_ARG, "upadd backward: extent must be even (dy is %d x %d x %d)", h, w, c);
+        if (t->dx.base && !same_extent(t->dx, h / 2, w / 2, c))
+            return hvn_fail(HVN_E_ARG, "upadd backward: dlo must be (h / 2, w / 2, c) of dy (dlo is %d x %d x %d, dy %d x %d x %d)", t->dx.h, t->dx.w,
+                            t->dx.c, h, w, c);
+        if (t->y.base && !same_extent(t->y, h, w, c))
+            return hvn_fail(HVN_E_ARG, "upadd backward: dskip must be (h, w, c) of dy (dskip is %d x %d x %d, dy %d x %d x %d)", t->y.h, t->y.w, t->y.c,
+                            h, w, c);
+        return HVN_OK;
+    }
+    case HVN_T_HEAD_BWD:
+        if (t->x.h <= 0 || t->x.w <= 0) return hvn_fail(HVN_E_ARG, "head backward: x has an empty extent (h = %d, w = %d)", t->x.h, t->x.w);
+        if (!same_extent(t->dx, t->x.h, t->x.w, t->x.c))
+            return hvn_fail(HVN_E_ARG, "head backward: the dx view's extent (%d, %d, %d) differs from x's (%d, %d, %d)", t->dx.h, t->dx.w, t->dx.c, t->x.h,
+                            t->x.w, t->x.c);
+        return HVN_OK;
+    default:
+        return HVN_OK;
+    }
 }
 
 // ws / ws_floats: the deterministic-reduce workspace of hvn_run_train_plan_ws (NULL: atomics)
@@ -184,6 +232,8 @@ int hvn_run_train_plan_ws(const hvn_top *ops, int n_ops, int batch, void *stream
 {
     if (!ops || n_ops <= 0 || batch <= 0) return hvn_fail(HVN_E_ARG, "run_train_plan_ws: ops NULL, or n_ops or batch < 1");
     if (workspace && !al16(workspace)) return hvn_fail(HVN_E_ARG, "run_train_plan_ws: workspace must be 16-byte aligned");
+    for (int i = 0; i < n_ops; ++i)          // every extent rule, over the whole list, before the first launch
+        if (int rc = extent_rules(&ops[i], batch)) return hvn_fail_in_op(rc, "train", i);
     for (int i = 0; i < n_ops; ++i) {
         int rc = run_top(&ops[i], batch, (hipStream_t)stream, (float *)workspace, workspace ? (long)(workspace_bytes / sizeof(float)) : 0);
         if (rc) return hvn_fail_in_op(rc, "train", i);

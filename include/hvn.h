@@ -621,6 +621,15 @@ HVN_API int hvn_viz_strip(const uint8_t *img, int n, int ih, int iw, const float
  *   SPLIT_X3     p[0] = fp32 weight packings (batch_stride[0] granules of 32 floats, any concatenation of PACK_W outputs), p[1] = their
  *                three bf16 planes, [3][32] bf16 per granule: what a CONV with act_dtype 2 | 3 reads (the weights of a training step
  *                change every step, so the planes are made on the device after the PACK_W ops)
+ * Extent rules (checked over the WHOLE list before its first op is launched: a list with a descriptor that breaks one, at any index,
+ * is refused with HVN_E_ARG and the rule's own text and nothing runs; the kernels take N, H, W, C from ONE view and walk the others
+ * with them):
+ *   BN_FWD / BN_BWD  (h, w, c) come from x = z; y, and for BN_BWD dy and a non-NULL dx, must have exactly that (h, w, c).
+ *                BN_FWD needs batch * h * w >= 2: the running variance is the unbiased one, which one value per channel does not
+ *                have (torch.nn.BatchNorm2d raises for it in train() mode)
+ *   UPADD_BWD    (h, w, c) come from dy, h and w even; a non-NULL dx must be (h / 2, w / 2, c), a non-NULL y (h, w, c); dx and y both
+ *                NULL is refused (nothing to do)
+ *   HEAD_BWD     (h, w) come from x (c = 64, h and w positive); dx must be (h, w, 64)
  */
 enum { HVN_T_NET = 1, HVN_T_PACK_W = 2, HVN_T_BN_FWD = 3, HVN_T_BN_BWD = 4, HVN_T_WGRAD = 5, HVN_T_CONV0_WGRAD = 6,
        HVN_T_UPADD_BWD = 7, HVN_T_HEAD_BWD = 8, HVN_T_WINO_DY = 9, HVN_T_WINO_DW = 10, HVN_T_SPLIT_X3 = 11, HVN_T_PACK_MULTI = 12 };

@@ -213,15 +213,33 @@ def run_dot_conv(n, x, wt, *, stride=1, pad=(0, 0), x3=0, force_tile=None, x2=No
     return got, np.ascontiguousarray(a.numpy())[None], np.ascontiguousarray(wk.reshape(cout, -1))[None], A
 
 
-def view_of(t, step=1):
-    """hvn_view over a whole contiguous [N, H, W, C] cuda tensor (every step-th pixel)."""
+def view_of(t, y0=0, x0=0, h=None, w=None, c0=0, c=None, step=1):
+    """hvn_view over a contiguous [N, H, W, C] cuda tensor: the window that starts at pixel (y0, x0) and channel c0, h x w pixels (default:
+    to the end) of c channels, every step-th pixel."""
     from hover_net_amd import lib as L
     n, H, W, C = t.shape
     v = L.hvn_view()
-    v.base = t.data_ptr()
+    h = (H - y0 + step - 1) // step if h is None else h
+    w = (W - x0 + step - 1) // step if w is None else w
+    c = C - c0 if c is None else c
+    v.base = t.data_ptr() + t.element_size() * ((y0 * W + x0) * C + c0)
     v.sn, v.sy, v.sx = H * W * C, step * W * C, step * C
-    v.h, v.w, v.c, v.sc = (H + step - 1) // step, (W + step - 1) // step, C, 1
+    v.h, v.w, v.c, v.sc = h, w, c, 1
     return v
+
+
+def run_tops(tops, batch):
+    """hvn_run_train_plan over `tops` (a list of hvn_top) on the current stream; asserts success and synchronises."""
+    import ctypes
+
+    from hover_net_amd import lib as L
+    L.require_gpu()
+    arr = (L.hvn_top * len(tops))()
+    for i, t in enumerate(tops):
+        ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(t), ctypes.sizeof(L.hvn_top))
+    rc = L.lib().hvn_run_train_plan(arr, len(tops), batch, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, L.lib().hvn_train_last_error().decode()
+    torch.cuda.synchronize()
 
 
 def run_train_ops(tops, batch, stored_parts=False):

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_util import run_tops, view_of
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():        # the training oracle's CPU runs start now, behind the GPU tests collected before this module
@@ -27,30 +29,6 @@ def _L():
     from hover_net_amd import lib as L
     L.require_gpu()
     return L
-
-
-def view_of(t, y0=0, x0=0, h=None, w=None, c0=0, c=None, step=1):
-    """hvn_view over a contiguous [N,H,W,C] cuda tensor."""
-    from hover_net_amd import lib as L
-    n, H, W, C = t.shape
-    v = L.hvn_view()
-    h = (H - y0 + step - 1) // step if h is None else h
-    w = (W - x0 + step - 1) // step if w is None else w
-    c = C - c0 if c is None else c
-    v.base = t.data_ptr() + t.element_size() * ((y0 * W + x0) * C + c0)
-    v.sn, v.sy, v.sx = H * W * C, step * W * C, step * C
-    v.h, v.w, v.c, v.sc = h, w, c, 1
-    return v
-
-
-def run_tops(tops, batch):
-    L = _L()
-    arr = (L.hvn_top * len(tops))()
-    for i, t in enumerate(tops):
-        ctypes.memmove(ctypes.addressof(arr[i]), ctypes.addressof(t), ctypes.sizeof(L.hvn_top))
-    rc = L.lib().hvn_run_train_plan(arr, len(tops), batch, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.lib().hvn_train_last_error().decode()
-    torch.cuda.synchronize()
 
 
 def close(got, want, rtol, what=""):
