@@ -654,6 +654,31 @@ int hvn_internal_run_one(const hvn_op *op, int batch, hipStream_t s)
         if ((uintptr_t)a.component & 3) return hvn_fail(HVN_E_ARG, "nbr_forest: misaligned component (4)");
         return hvn_launch_status(hvn_launch_nbr_forest(a, s), "nbr_forest");
     }
+    case HVN_OP_INST_TEXTURE: {
+        InstTextureArgs a;
+        a.image = (const uint8_t *)op->x.base;
+        a.inst = (const int32_t *)op->res.base;
+        a.rec = (const hvn_inst_rec *)op->w;
+        a.out = (int32_t *)op->y.base;
+        a.N = batch; a.H = op->x.h; a.W = op->x.w; a.max_inst = op->cout;
+        a.fixed = op->_rsv; a.merge = op->stride;
+        if (!a.image) return hvn_fail(HVN_E_ARG, "inst_texture: null image (x)");
+        if (!a.inst) return hvn_fail(HVN_E_ARG, "inst_texture: null inst (res)");
+        if (!a.rec) return hvn_fail(HVN_E_ARG, "inst_texture: null records (w)");
+        if (!a.out) return hvn_fail(HVN_E_ARG, "inst_texture: null output (y)");
+        if (a.H < 1 || a.W < 1 || a.max_inst < 1) return hvn_fail(HVN_E_ARG, "inst_texture: n, h, w or max_inst < 1 (h = %d, w = %d, max_inst = %d)", a.H, a.W, a.max_inst);
+        if ((long)a.H * a.W >= (1L << 31)) return hvn_fail(HVN_E_ARG, "inst_texture: h * w >= 2^31 (h = %d)", a.H);
+        if (op->x.c != 3 || op->x_dtype != 0) return hvn_fail(HVN_E_ARG, "inst_texture: the image view is not c = 3 uint8 (c = %d, x_dtype = %d)", op->x.c, op->x_dtype);
+        // strides in bytes as VIEW; 0 = dense, and dense is the only form this op reads
+        if ((op->x.sx != 0 && op->x.sx != 3) || (op->x.sy != 0 && op->x.sy != 3L * a.W) || (op->x.sn != 0 && op->x.sn != 3L * a.H * a.W))
+            return hvn_fail(HVN_E_ARG, "inst_texture: the image view is not dense (sy = %ld)", (long)op->x.sy);
+        if (a.fixed != 0 && a.fixed != 1) return hvn_fail(HVN_E_ARG, "inst_texture: `_rsv` = %d is no scale mode (0: range, 1: fixed)", a.fixed);
+        if (a.merge != 0 && a.merge != 1) return hvn_fail(HVN_E_ARG, "inst_texture: `stride` = %d is no accumulation form (0: plain, 1: merged)", a.merge);
+        if (((uintptr_t)a.out & 7) || ((uintptr_t)a.rec & 7)) return hvn_fail(HVN_E_ARG, "inst_texture: misaligned output or records (8)");
+        if ((uintptr_t)a.inst & 3) return hvn_fail(HVN_E_ARG, "inst_texture: misaligned inst (4)");
+        if ((long)a.N * a.max_inst >= (1L << 31)) return hvn_fail(HVN_E_SIZE, "inst_texture: n * max_inst >= 2^31 (%ld slots)", (long)a.N * a.max_inst);
+        return hvn_launch_status(hvn_launch_inst_texture(a, s), "inst_texture");
+    }
     default:
         return hvn_fail(HVN_E_ARG, "unknown op kind %d", op->kind);
     }

@@ -407,6 +407,18 @@ struct NbrForestArgs {
 };
 int hvn_launch_nbr_forest(const NbrForestArgs &a, hipStream_t stream);
 
+// hvn_texture.hip: per-nucleus grey-level co-occurrence counts over the label map (hover_net_amd/texture.py), one wave per record slot
+struct InstTextureArgs {
+    const uint8_t *image;       // [N][H][W][3] RGB, dense
+    const int32_t *inst;        // [N][H][W]
+    const hvn_inst_rec *rec;    // [N][max_inst]
+    int32_t *out;               // [N][max_inst][HVN_TEX_WORDS]; every word is written
+    int N, H, W, max_inst;
+    int fixed;                  // 0: levels over the nucleus's own grey range; 1: over 0..255
+    int merge;                  // 0: one LDS add per pair; 1: equal keys are merged on chip before the LDS add (the same numbers, slower)
+};
+int hvn_launch_inst_texture(const InstTextureArgs &a, hipStream_t stream);
+
 struct WinoArgs {
     const float *x;       // WINO_IN: input view; WINO_OUT: M [n*n][tiles][C] per sample (n = m + 4)
     long xsn, xsy, xsx;

@@ -180,7 +180,9 @@ class InferManager:
         patch_input_shape, patch_output_shape (+ nr_inference_workers, nr_post_proc_workers: ignored); device_overlay (default
         False): rank 0 draws `overlay/` on the GPU (`viz.visualize_instances_dict(device=...)`, the same pixels); save_features
         (default False): every nucleus of `json/` gains "features" (`features.derive`: shape and colour; `.mat`, overlay and
-        qupath are as without it); tta (default None): a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids) --
+        qupath are as without it); save_texture (default None): True | "range" | "fixed" -- every nucleus of `json/` gains "texture"
+        (`texture.derive`: grey-level co-occurrence and first-order grey statistics of the image as given; True means "range");
+        tta (default None): a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids) --
         every network step averages the views' outputs on the GPU (`Engine.run_tta`); stain_norm (default None): "macenko" or a
         `stain.StainFit` of a target image -- every image is fitted on itself and Macenko-normalised on the GPU before its patches
         are cut (hover_net_amd/stain.py); neighbours, clusters, density (default None): the point-pattern
@@ -213,7 +215,12 @@ class InferManager:
         save_qupath = bool(run_args.get("save_qupath", False))
         save_raw_map = bool(run_args.get("save_raw_map", False))
         save_features = bool(run_args.get("save_features", False))
-        tta = TT.views(run_args.get("tta"))                 # ValueError before any file is touched
+        save_texture = run_args.get("save_texture") or None
+        if save_texture is not None:
+            from . import texture as TX
+
+            save_texture = TX.check_scale(save_texture)     # ValueError before any file is touched
+        tta = TT.views(run_args.get("tta"))                 # likewise
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         point_args = {k: run_args.get(k) for k in PT.ARGS}
         specs = PT.resolve_specs(**dict(point_args, regions=None), typed=self.nr_types is not None)   # likewise
@@ -230,7 +237,8 @@ class InferManager:
                 rm_n_mkdir("%s/%s/" % (output_dir, sub))
         process = self.process_fn or (lambda images: infer_tile.process_images(
             images, self.model, nr_types=self.nr_types, batch_size=batch_size, return_centroids=True, return_raw=save_raw_map,
-            **({"return_features": True} if save_features else {}), **({"tta": tta} if tta is not None else {}),
+            **({"return_features": True} if save_features else {}), **({"return_texture": save_texture} if save_texture is not None else {}),
+            **({"tta": tta} if tta is not None else {}),
             **({"stain_norm": stain_norm} if stain_norm is not None else {}),
             **_given(run_args, "neighbours", "clusters")))
         done = []
@@ -331,7 +339,8 @@ class WsiManager(InferManager):
         {slide stem: number} mapping (a slide the mapping lacks is a "crash") -- a slide whose base_mag differs from proc_mag is resampled to proc_mag as it is read
         (`open_slide`); absent = the files are taken as they are; device_mask (default False): a slide without a mask file takes its
         tissue mask from the GPU (`tissue_mask.simple_get_mask(device=...)`, the same bytes on every rank); save_features (default False): every nucleus of the json
-        gains "features" (`features.derive`, shape features only: colour features on slides are out of scope); tta (default None): a view set of
+        gains "features" (`features.derive`, shape features only: colour features on slides are out of scope); save_texture: REFUSED with a ValueError before any
+        file is touched -- stage 2 holds the prediction map, not the slide's pixels, so texture on slides is out of scope like the colour features; tta (default None): a view set of
         hover_net_amd.tta -- every stage-1 network step averages the views' outputs on the GPU (`Engine.run_tta`); stain_norm (default None): "macenko"
         or a `stain.StainFit` of a target image -- every slide is fitted once from its thumbnail and its regions are Macenko-normalised on the GPU
         (`WsiInference(stain_norm=...)`); neighbours, clusters, density (default None): the point-pattern analyses of hover_net_amd/points.py, in
@@ -351,6 +360,9 @@ class WsiManager(InferManager):
         from . import stain as ST
         from . import tta as TT
 
+        if run_args.get("save_texture"):
+            raise ValueError("run_args['save_texture'] is not available for whole slides: the instance stage (stage 2) holds the prediction map, not the "
+                             "slide's pixels, and texture needs the pixels (it is a tile-mode key: process_file_list)")
         tta = TT.views(run_args.get("tta"))                 # ValueError before any slide is opened
         stain_norm = ST.resolve(run_args.get("stain_norm"))  # likewise
         point_args = {k: run_args.get(k) for k in PT.ARGS}

@@ -302,9 +302,10 @@ def result_to_arrays(inst_h, rec_h, nr_types, contours_flat=None):
     return [np.ascontiguousarray(inst_h, np.int32), rec_h.view(np.uint8).reshape(rec_h.shape[0], rec_h.dtype.itemsize), pts, offs]
 
 
-def arrays_to_result(arrs, nr_types, with_info=True, shift_xy=None, *, feat_b=None, with_colour=False):
+def arrays_to_result(arrs, nr_types, with_info=True, shift_xy=None, *, feat_b=None, with_colour=False, tex_b=None):
     """`feat_b`: the item's feature bytes (`PostProc.features`, uint8 [max_inst, sizeof(hvn_inst_feat)]) -- the dict entries gain
-    "features" (`post_proc.records_to_dict(feat_host=...)`)."""
+    "features" (`post_proc.records_to_dict(feat_host=...)`); `tex_b`: its texture bytes (`PostProc.texture`, uint8 [max_inst, 1104])
+    -- they gain "texture" (`tex_host=...`)."""
     from . import post_proc
 
     inst_h, rec_b, pts, offs = arrs
@@ -312,7 +313,8 @@ def arrays_to_result(arrs, nr_types, with_info=True, shift_xy=None, *, feat_b=No
         return np.array(inst_h), None
     rec_h = np.ascontiguousarray(rec_b).view(post_proc._REC_DTYPE).reshape(-1)
     return np.array(inst_h), post_proc.records_to_dict(rec_h, nr_types, contours_flat=(np.array(pts), np.array(offs)), shift_xy=shift_xy,
-                                                       feat_host=feat_b, with_colour=with_colour)
+                                                       feat_host=feat_b, with_colour=with_colour,
+                                                       **({} if tex_b is None else {"tex_host": tex_b}))
 
 
 def run_sharded(items, step_fn, batch_size, gather=True):
@@ -334,7 +336,7 @@ def run_sharded(items, step_fn, batch_size, gather=True):
 
 # --------------------------------------------------------------------------------------------
 def process_images(images, model, nr_types=None, batch_size=32, return_centroids=True, return_raw=False, max_patches=16384, *,
-                   return_features=False, tta=None, stain_norm=None, neighbours=None, clusters=None):
+                   return_features=False, tta=None, stain_norm=None, neighbours=None, clusters=None, return_texture=None):
     """images: list of uint8 [H,W,3] arrays (RGB).  Returns a list of (pred_inst int32 [H,W] numpy, inst_info_dict | None)
     in input order: complete on rank 0 (the writer); the other ranks hold their own images' results and None elsewhere.
     `return_raw=True` appends the stitched float32 prediction map [H,W,3|4] to each tuple (`--save_raw_map`,
@@ -342,6 +344,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     `return_features=True` (implies the instance dict) adds "features" to every dict entry: shape and colour features of the
     nucleus (`features.derive`) from one more pass over the instance map and the image this call uploaded anyway
     (`PostProc.features`); the feature bytes travel to rank 0 as one more array of the item.
+    `return_texture="range" | "fixed"` (True means "range"; implies the instance dict) adds "texture" to every dict entry: the
+    chromatin texture of the nucleus (`texture.derive`) from `PostProc.texture`'s pass over the instance map and the uploaded image;
+    the texture bytes travel to rank 0 as one more array of the item, after the feature bytes, across ranks too.  Like the colour
+    features it reads the image AS GIVEN, not the stain-normalised copy.
     `tta`: None, or a view set of hover_net_amd.tta ("flips", "rot", "d4" or a tuple of view ids): every network step is the
     test-time-augmented one (`Engine.run_tta`); the sharding is the same, the augmentation lives inside the step.
     `stain_norm`: None, "macenko" or a `stain.StainFit` of a target image (hover_net_amd/stain.py): every image is fitted on itself
@@ -363,6 +369,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
         stain_norm = ST.resolve(stain_norm)
     from . import points as PT
 
+    if return_texture is not None:
+        from . import texture as TX
+
+        return_texture = TX.check_scale(return_texture)
     specs = PT.resolve_specs(neighbours, clusters, typed=nr_types is not None)
     return_centroids = return_centroids or specs.any_annotation
     win = 270 if (model.module if hasattr(model, "module") and not hasattr(model, "engine") else model).mode == "original" else 256
@@ -384,8 +394,10 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
             more["tta"] = tta
         if stain_norm is not None:
             more["stain_norm"] = stain_norm
-        for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size, return_centroids or return_features,
-                                                    return_raw, **more)):
+        if return_texture is not None:
+            more["return_texture"] = return_texture
+        for i, res in zip(grp, _process_image_group([images[i] for i in grp], model, nr_types, batch_size,
+                                                    return_centroids or return_features or return_texture is not None, return_raw, **more)):
             out[i] = res
     if specs.any_annotation and _dist()[1] == 0:
         net = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
@@ -396,14 +408,16 @@ def process_images(images, model, nr_types=None, batch_size=32, return_centroids
     return out
 
 
-def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False, tta=None, stain_norm=None):
+def _process_image_group(images, model, nr_types, batch_size, return_centroids, return_raw, return_features=False, tta=None, stain_norm=None,
+                         return_texture=None):
     """One group of `process_images` (`stain_norm`: None or the resolved target, a `stain.StainFit`).
 
     Pipeline per call: patch extraction -> sharded HIP network (`run_desc.infer_step_device`)
     -> one all_to_all of the per-patch maps to the images' owners (`route_to_owners`) -> per-image stitch on the GPU -> on-GPU instance
     separation + instance table (`post_proc.process_batch_device`) for the images this rank owns
     -> tensor gather of instance maps / record tables / contours to rank 0 (`gather_items_to_rank0`).
-    An item's arrays: [0:4] `result_to_arrays`, [4] the raw map with `return_raw`, LAST the feature bytes with `return_features`."""
+    An item's arrays: [0:4] `result_to_arrays`, [4] the raw map with `return_raw`, then the feature bytes with `return_features`, LAST
+    the texture bytes with `return_texture`."""
     from . import post_proc, run_desc
     from . import stain as ST
 
@@ -422,8 +436,8 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
                 tab = ST.tables_or_none(img_dev, stain_norm)
                 src_dev = img_dev if tab is None else ST.apply_device(img_dev, tab)
             patches.append(extract_patches_device(src_dev, info, win, pad_tl))
-            if return_features and i % world == rank:
-                uploaded[i] = img_dev           # the colour features of the images this rank owns read it again
+            if (return_features or return_texture is not None) and i % world == rank:
+                uploaded[i] = img_dev           # the colour features and the texture of the images this rank owns read it again
         else:                       # host geometry (CPU tests of the sharding logic)
             if stain_norm is not None:
                 tab = ST.tables_or_none(np.ascontiguousarray(img[..., :3]), stain_norm)
@@ -445,10 +459,16 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
         n = counts[i]
         if i % world == rank:
             full = stitch(pred[k:k + n], infos[i], img.shape).contiguous()
-            if return_features:
+            feat = tex = None
+            if return_features or return_texture is not None:
                 img_dev = uploaded.pop(i) if i in uploaded else torch.from_numpy(np.ascontiguousarray(img)).to(full.device)
-                inst, rec, _, feat = post_proc.process_batch_device(full.unsqueeze(0), nr_types, True, return_features=True,
-                                                                    image=img_dev.unsqueeze(0))
+                more = {"return_features": True} if return_features else {}
+                if return_texture is not None:
+                    more["return_texture"] = return_texture
+                res = post_proc.process_batch_device(full.unsqueeze(0), nr_types, True, image=img_dev.unsqueeze(0), **more)
+                inst, rec = res[0], res[1]
+                feat = res[3] if return_features else None
+                tex = res[-1] if return_texture is not None else None
             else:
                 inst, rec, _ = post_proc.process_batch_device(full.unsqueeze(0), nr_types, return_centroids)
             inst_h = inst[0].cpu().numpy()
@@ -458,6 +478,8 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
                 mine[i].append(full.cpu().numpy())
             if return_features:
                 mine[i].append(feat[0].cpu().numpy())
+            if return_texture is not None:
+                mine[i].append(tex[0].cpu().numpy())
             k += n
     every = gather_items_to_rank0(mine, device=dev)          # the instance maps + record tables + contours travel as tensors to rank 0
     if every is None:                            # not rank 0: keeps only what it computed itself
@@ -468,6 +490,7 @@ def _process_image_group(images, model, nr_types, batch_size, return_centroids, 
             out.append(None)
             continue
         res = arrays_to_result(every[i][:4], nr_types, with_info=(return_centroids or nr_types is not None),
-                               feat_b=every[i][-1] if return_features else None, with_colour=True)
+                               feat_b=every[i][-2 if return_texture is not None else -1] if return_features else None, with_colour=True,
+                               **({} if return_texture is None else {"tex_b": every[i][-1]}))
         out.append(res + (np.array(every[i][4]),) if return_raw else res)
     return out

@@ -22,7 +22,7 @@ VARIANTS = {
 CSRC = os.path.join(_HERE, "csrc")
 HEADERS = ("hvn_conv_common.h", "hvn_env.h", "hvn_error.h", "hvn_kernels.h")
 SOURCES = ("hvn_conv.hip", "hvn_conv_chain.hip", "hvn_conv_chain_x3.hip", "hvn_conv_chain_x3r.hip", "hvn_conv_bf16.hip", "hvn_conv_bf16g.hip", "hvn_conv_chain_bf16.hip", "hvn_conv_x3.hip", "hvn_conv_x3g.hip", "hvn_net_ops.hip", "hvn_postproc.hip", "hvn_api.hip", "hvn_train.hip", "hvn_wgrad_x3.hip", "hvn_targets.hip", "hvn_wsi_merge.hip",
-           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_contour_dev.hip", "hvn_metrics.hip", "hvn_valid.hip", "hvn_overlay.hip", "hvn_resample.hip", "hvn_tissue.hip", "hvn_viz.hip", "hvn_features.hip", "hvn_tta.hip", "hvn_stain.hip", "hvn_neighbours.hip", "hvn_clusters.hip", "hvn_density.hip", "hvn_pairs.hip", "hvn_pairs_sim.hip", "hvn_regions.hip", "hvn_margins.hip", "hvn_graph.hip", "hvn_forest.hip")
+           "hvn_augment.hip", "hvn_train_api.hip", "hvn_contour.cpp", "hvn_contour_dev.hip", "hvn_metrics.hip", "hvn_valid.hip", "hvn_overlay.hip", "hvn_resample.hip", "hvn_tissue.hip", "hvn_viz.hip", "hvn_features.hip", "hvn_tta.hip", "hvn_stain.hip", "hvn_neighbours.hip", "hvn_clusters.hip", "hvn_density.hip", "hvn_pairs.hip", "hvn_pairs_sim.hip", "hvn_regions.hip", "hvn_margins.hip", "hvn_graph.hip", "hvn_forest.hip", "hvn_texture.hip")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                "-fvisibility=hidden", "-Wno-unused-value", "-pthread")
 

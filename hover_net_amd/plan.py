@@ -47,6 +47,7 @@ OP_NBR_PAIRS_SIM = 20   # the pair counts of OP_NBR_PAIRS under a batch of rando
 OP_NBR_MARGINS = 21     # distance bands around the boundaries of annotated regions over the same grid (margins.py): never part of a plan
 OP_NBR_GRAPH = 22       # the cell graph (Gabriel edges of length <= r) over the same grid, count and fill (graph.py): never part of a plan
 OP_NBR_FOREST = 23      # the minimum spanning forest and the components of a cell graph, Boruvka rounds (forest.py): never part of a plan
+OP_INST_TEXTURE = 24    # per-nucleus grey-level co-occurrence counts over a label map (texture.py): never part of a plan
 
 
 @dataclass

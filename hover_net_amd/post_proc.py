@@ -25,6 +25,7 @@ import torch
 
 from . import features as F
 from . import lib as L
+from . import texture as TX
 
 
 def _check_image(image, nhw, device):
@@ -149,6 +150,36 @@ class PostProc:
                max_inst, feat.data_ptr(), self._fws.data_ptr() if need else None, need, L.stream_ptr(self.device))
         return feat
 
+    def texture(self, inst, rec, image, scale="range", form=0):
+        """The grey-level co-occurrence counts of every record (HVN_OP_INST_TEXTURE, hover_net_amd/texture.py) on the current
+        stream, no host sync.  inst: int32 device tensor [N,h,w]; rec: `table`'s records [N,max_inst,sizeof(rec)]; image: uint8
+        device tensor [N,h,w,3] (RGB), mandatory; scale: "range" (levels over the nucleus's own grey range) or "fixed" (over
+        0..255).  -> uint8 device tensor [N,max_inst,1104]: `texture.TEX_DTYPE` slots parallel to the records, every byte written;
+        `texture.derive` makes the float features of them on the host.  Any label map is valid; a table that was not made from
+        `inst` shows as seen != area.  form: 0 = the product's kernel form (one LDS add per pair), 1 = the one that lost (equal keys
+        merged first; tools/texture_bench.py)."""
+        from . import plan as PL
+
+        mode = TX.SCALES[TX.check_scale(scale)]
+        if not (torch.is_tensor(inst) and inst.dtype == torch.int32 and inst.dim() == 3 and inst.is_cuda):
+            raise ValueError("inst must be an int32 device tensor [N,h,w]")
+        n, h, w = inst.shape
+        if not (torch.is_tensor(rec) and rec.dtype == torch.uint8 and rec.dim() == 3 and rec.is_cuda and rec.shape[0] == n
+                and rec.shape[2] == ctypes.sizeof(L.hvn_inst_rec)):
+            raise ValueError("record table does not belong to %d maps" % n)
+        if image is None:
+            raise ValueError("texture needs the image")
+        _check_image(image, (n, h, w), inst.device)
+        inst, rec, image = inst.contiguous(), rec.contiguous(), image.contiguous()
+        max_inst = rec.shape[1]
+        tex = torch.empty((n, max_inst, TX.TEX_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        op = L.hvn_op()
+        op.kind, op.cout, op._rsv, op.stride = PL.OP_INST_TEXTURE, max_inst, mode, int(form)
+        op.x.base, op.x.h, op.x.w, op.x.c = image.data_ptr(), h, w, 3
+        op.res.base, op.w, op.y.base = inst.data_ptr(), rec.data_ptr(), tex.data_ptr()
+        L.call("hvn_run_op", ctypes.addressof(op), n, L.stream_ptr(self.device))
+        return tex
+
     def _pinned(self, like):
         """Pinned host buffers for `contours`' three outputs (kept: pinned allocations are slow)."""
         if self._cpin is None or any(b.numel() < t.numel() for b, t in zip(self._cpin, like)):
@@ -168,15 +199,21 @@ def _pp(device):
     return _DEFAULT[key]
 
 
-def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False, *, return_features=False, image=None):
+def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return_contours=False, *, return_features=False, image=None,
+                         return_texture=None):
     """pred_dev [N,h,w,3|4] float32 on the GPU -> (inst int32 [N,h,w] device tensor,
     records device tensor | None, counts device tensor | None); with return_contours=True the tuple gains
     `PostProc.contours`' (pts, offs, status) device tensors (None each when there is no record table); records, pts and offs
     in that form are what `viz.overlay_from_records` draws without leaving the device.  return_features=True appends
     `PostProc.features`' tensor as the LAST element (None when there is no record table); `image` (uint8 device tensor
-    [N,h,w,3]) adds the colour sums."""
-    if image is not None and not return_features:
-        raise ValueError("image is only used with return_features=True")
+    [N,h,w,3]) adds the colour sums.  return_texture="range" | "fixed" appends `PostProc.texture`'s tensor as the LAST element, after
+    the features tensor when both are asked for (None when there is no record table); it needs `image`."""
+    if return_texture is not None:
+        return_texture = TX.check_scale(return_texture)
+        if image is None:
+            raise ValueError("return_texture needs the image")
+    if image is not None and not return_features and return_texture is None:
+        raise ValueError("image is only used with return_features=True or return_texture")
     if image is not None:       # refuse a bad image before anything is launched
         _check_image(image, tuple(pred_dev.shape[:3]), pred_dev.device)
     pp = _pp(pred_dev.device)
@@ -188,6 +225,8 @@ def process_batch_device(pred_dev, nr_types=None, return_centroids=False, return
         out += pp.contours(inst, out[1]) if out[1] is not None else (None, None, None)
     if return_features:
         out += (pp.features(inst, out[1], image) if out[1] is not None else None,)
+    if return_texture is not None:
+        out += (pp.texture(inst, out[1], image, return_texture) if out[1] is not None else None,)
     return out
 
 
@@ -258,7 +297,8 @@ def trace_contours(inst_host, rec_host):
     return {int(rec_host["label"][i]): pts[offs[i]:offs[i + 1]].copy() for i in range(rec_host.shape[0]) if rec_host["area"][i] > 0}
 
 
-def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shift_xy=None, *, feat_host=None, with_colour=False):
+def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shift_xy=None, *, feat_host=None, with_colour=False,
+                    tex_host=None):
     """One tile's records (numpy structured array) -> the reference's inst_info_dict.  With `inst_host`
     the contours are traced too (or taken from `contours_flat` = trace_contours_flat's result, e.g. traced on another
     rank) and, like the reference (post_proc.py:140-143), instances whose contour
@@ -269,9 +309,15 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
     the reference's quirk, kept) -- vectorised here instead of three small-array additions per instance there.
     `feat_host` (`features.FEAT_DTYPE` slots parallel to `rec_host`, from `PostProc.features`) adds "features": {...}
     (`features.derive`; the colour entries with `with_colour`) to every entry; they are translation-invariant, `shift_xy` does
-    not touch them."""
+    not touch them.  `tex_host` (`texture.TEX_DTYPE` slots parallel to `rec_host`, from `PostProc.texture`) adds "texture": {...}
+    (`texture.derive`) likewise."""
     r = rec_host[rec_host["area"] > 0]
-    feats = None
+    feats = texs = None
+    if tex_host is not None:
+        tex_host = np.ascontiguousarray(tex_host).view(TX.TEX_DTYPE).reshape(-1)
+        if tex_host.shape != rec_host.shape:
+            raise ValueError("tex_host %s is not parallel to the records %s" % (tex_host.shape, rec_host.shape))
+        texs = TX.to_dicts(TX.derive(tex_host[rec_host["area"] > 0]))
     if feat_host is not None:
         feat_host = np.ascontiguousarray(feat_host).view(F.FEAT_DTYPE).reshape(-1)
         if feat_host.shape != rec_host.shape:
@@ -307,15 +353,20 @@ def records_to_dict(rec_host, nr_types, inst_host=None, contours_flat=None, shif
                     "type_prob": None if tprob is None else tprob[i], "type": None if types is None else types[i]}
         if feats is not None:
             out[lab]["features"] = feats[i]
+        if texs is not None:
+            out[lab]["texture"] = texs[i]
     return out
 
 
-def process(pred_map, nr_types=None, return_centroids=False, contours="host", *, features=False, image=None, neighbours=None, clusters=None):
+def process(pred_map, nr_types=None, return_centroids=False, contours="host", *, features=False, image=None, neighbours=None, clusters=None,
+            texture=None):
     """Reference signature (post_proc.py:94): one host map [H,W,3|4] float32.  contours="device" traces the contours on
     the GPU (`trace_contours_device`) instead of on the host; the result is the same.  features=True adds "features" to every
     entry of the dict (`features.derive`; it implies return_centroids); `image` (host uint8 [H,W,3], RGB) adds mean_rgb / std_rgb.
     neighbours / clusters: the point-pattern analyses of hover_net_amd/points.py on the finished dict, on the GPU (they imply
-    return_centroids)."""
+    return_centroids).  texture=True | "range" | "fixed" (True means "range") adds "texture" to every entry of the dict
+    (`texture.derive` of `PostProc.texture`'s counts; it implies return_centroids); it needs `image` and raises ValueError before
+    any launch without one."""
     from . import points as PT
     from . import clusters as CL
     from . import neighbours as NB
@@ -325,9 +376,13 @@ def process(pred_map, nr_types=None, return_centroids=False, contours="host", *,
     specs = PT.resolve_specs(neighbours, clusters, typed=nr_types is not None)
     return_centroids = return_centroids or specs.any_annotation
     img_dev = None
+    if texture is not None:
+        texture = TX.check_scale(texture)
+        if image is None:
+            raise ValueError("texture needs the image")
     if image is not None:
-        if not features:
-            raise ValueError("image is only used with features=True")
+        if not features and texture is None:
+            raise ValueError("image is only used with features=True or texture")
         image = np.asarray(image)
         if image.dtype != np.uint8:
             raise TypeError("image must be uint8, got %s" % image.dtype)
@@ -335,13 +390,15 @@ def process(pred_map, nr_types=None, return_centroids=False, contours="host", *,
             raise ValueError("image %s does not match the map: expected %s" % (image.shape, tuple(np.shape(pred_map)[:2]) + (3,)))
         img_dev = torch.from_numpy(np.ascontiguousarray(image)).unsqueeze(0).to("cuda")
     pred = torch.from_numpy(np.ascontiguousarray(pred_map, np.float32)).unsqueeze(0).to("cuda")
-    inst, rec, _ = process_batch_device(pred, nr_types, return_centroids or features)
+    inst, rec, _ = process_batch_device(pred, nr_types, return_centroids or features or texture is not None)
     feat = _pp(pred.device).features(inst, rec, img_dev) if features and rec is not None else None
+    tex = _pp(pred.device).texture(inst, rec, img_dev, texture) if texture is not None and rec is not None else None
     flat = trace_contours_device(inst, rec)[0] if rec is not None and contours == "device" else None
     pred_inst = inst[0].cpu().numpy()
     info = None
     if rec is not None:
         info = records_to_dict(rec[0].cpu().numpy().view(_REC_DTYPE).reshape(-1), nr_types, pred_inst, contours_flat=flat,
-                               feat_host=None if feat is None else feat[0].cpu().numpy(), with_colour=image is not None)
+                               feat_host=None if feat is None else feat[0].cpu().numpy(), with_colour=image is not None,
+                               **({} if tex is None else {"tex_host": tex[0].cpu().numpy()}))
         PT.annotate(info, specs, nr_types, pred.device)
     return pred_inst, info

@@ -42,7 +42,10 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
        HVN_OP_STAIN_HIST = 11, HVN_OP_STAIN_COMPACT = 12, HVN_OP_STAIN_APPLY = 13, HVN_OP_NBR_GRID = 14, HVN_OP_NBR_QUERY = 15,
        HVN_OP_NBR_CLUSTER = 16, HVN_OP_NBR_DENSITY = 17, HVN_OP_NBR_PAIRS = 18, HVN_OP_NBR_REGIONS = 19,
        HVN_OP_NBR_PAIRS_SIM = 20, HVN_OP_NBR_MARGINS = 21, HVN_OP_NBR_GRAPH = 22,
-       HVN_OP_NBR_FOREST = 23 };
+       HVN_OP_NBR_FOREST = 23, HVN_OP_INST_TEXTURE = 24 };
+
+#define HVN_TEX_LEVELS 8     /* grey levels of HVN_OP_INST_TEXTURE */
+#define HVN_TEX_WORDS 276    /* int32 words per record slot of its output: 12 + HVN_TEX_LEVELS + 4 * HVN_TEX_LEVELS^2 */
 
 /*
  * One fused launch of the network plan (hover_net_amd/plan.py lowers
@@ -331,6 +334,32 @@ enum { HVN_OP_CONV0 = 1, HVN_OP_CONV = 2, HVN_OP_UPADD = 3, HVN_OP_HEAD = 4, HVN
  *           HVN_E_ARG: `_rsv` outside 0..3, `stride` outside 0..25 with `_rsv` = 2, a null pointer (xy, indptr, component, the workspace;
  *           indices or tree with E > 0), N < 1, E < 0, batch != 1, xy / indptr / workspace not 8-byte or indices / component not 4-byte
  *           aligned.  HVN_E_SIZE: N > 2^26, E >= 2^31, x2.sn too small.
+ *   INST_TEXTURE   per-nucleus grey-level co-occurrence counts: the integers under the chromatin texture features (hover_net_amd/texture.py
+ *           holds the definition; csrc/hvn_texture.hip).  Never part of a plan; the third pass over a label map, next to
+ *           hvn_instance_table and hvn_instance_features, whose inputs it reuses.  batch = n maps; x = the image view, uint8
+ *           [n][h][w][3] RGB (x_dtype 0, c = 3, x.h = h, x.w = w), dense: strides in BYTES as VIEW, each 0 or the dense value (sx 0 | 3,
+ *           sy 0 | 3 w, sn 0 | 3 h w); res.base = inst, int32 [n][h][w] (4-byte aligned); w = the records, hvn_inst_rec
+ *           [n][max_inst] as hvn_instance_table left them (8-byte aligned; read as records whatever the pointer's declared type);
+ *           cout = max_inst; y.base = the output, int32 [n][max_inst][HVN_TEX_WORDS] (8-byte aligned); `_rsv` = the scale mode, 0
+ *           "range" | 1 "fixed"; `stride` = the accumulation form, 0 = one LDS add per pair, 1 = equal keys merged on chip before the
+ *           LDS add (the same numbers, slower; tools/texture_bench.py times the two against each other).  No other field is read.
+ *           The mask of a label is inst == label INSIDE the record's bbox clamped to the map, as in hvn_instance_features: any label
+ *           map is valid, and a stale or foreign table cannot make the kernel read outside the map.  The grey value of a pixel is
+ *           g = (77 R + 150 G + 29 B + 128) >> 8, its level q = ((g - lo) * 8) / span, span = hi - lo + 1, in 0..7, with (lo, hi) =
+ *           the smallest and largest grey value of the mask in mode 0 and (0, 255) in mode 1.  The offsets (dx, dy), y down, are
+ *           d = 0: (1, 0), 1: (1, 1), 2: (0, 1), 3: (-1, 1); glcm[d][a][b] = the mask pixels p of level a whose neighbour p + offset_d
+ *           is a mask pixel of the same label and has level b: ORDERED pairs, not symmetrised, every unordered pair once.  A slot, in
+ *           int32 words (slot j describes label j + 1, parallel to the records): 0..7 gsum = int64 [4], the sums of g, g^2, g^3, g^4
+ *           over the mask (255^4 (2^31 - 1) < 2^63); 8 seen = the mask pixels found (== rec.area for a table made from this map);
+ *           9, 10 = the nucleus's OWN smallest and largest grey value in BOTH modes (the mode only decides whether the level formula
+ *           uses them or 0 and 255; both 0 when seen = 0); 11 = 0; 12..19 hist[8] = the mask pixels per level; 20..275 glcm[4][8][8].
+ *           A slot with area <= 0 or an empty clamped bbox is 276 zero words.  EVERY word of every slot is written, whatever it held
+ *           before: the caller clears nothing.  One wave per slot, the counts in a per-wave LDS block, no global atomics, no
+ *           workspace, integer sums: a function of the inputs alone.  Every loop is bounded by the map extent.  A refusal launches
+ *           nothing and leaves the output untouched.
+ *           HVN_E_ARG: a null image, inst, records or output; n (batch), h, w or max_inst < 1; h * w >= 2^31; an image view that is
+ *           not c = 3 uint8, or not dense; a scale mode other than 0 or 1; an accumulation form other than 0 or 1; output or records
+ *           not 8-byte, inst not 4-byte aligned.  HVN_E_SIZE: n * max_inst >= 2^31.
  */
 typedef struct hvn_op {
     int32_t kind, kh, kw, stride, pad_t, pad_l, relu, cout, tile_n, x_dtype, groups, _rsv;
